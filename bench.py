@@ -16,6 +16,10 @@ utterances per GPU, inputs resident in HBM, device Philox noise.
   --config c5            configs[4], one GPU's share scaled down: 32 references x 8 targets, 50-step DDIM (+ 2 x 50-step f0
                          loops), per-reference style cache, hipGraph replay
 Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, ...). `--full` adds what takes runs
+of its own: the strict one-batch-at-a-time figure, the kernel roofline, the CPU baseline, parity against the reference goldens and, for
+the default c2 line, the other configs as `secondary`. `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -98,10 +102,48 @@ def parse():
                          "(all K batches still start and finish inside the timed region; measured on MI355X at C2 with the round-2 kernels: "
                          "1 stream 400 ms/step, 2: 360-367, 3: 358, 4: 358). 1 = strictly one batch at a time.")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default c2 run on one GPU: do NOT append the other single-GPU BASELINE configs (c5 share, c4) as `secondary`")
+                    help="--full c2 run on one GPU: do NOT append the other single-GPU BASELINE configs (c5 share, c4) as `secondary`")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="extra thread count for the CPU oracle sweep; 16 is the fastest setting on the 2x64-core EPYC GPU-box host")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: one_batch_at_a_time, roofline, cpu_baseline, parity, secondary "
+                         "(each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 10**6} MB in all: larger outputs as a fixed seeded sample of their elements)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Writes every tensor of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 kept, everything else as float32. If they do not fit in
+    `limit` bytes together, the smaller arrays are written whole and each larger one as the sample of its flattened elements at the sorted
+    distinct positions of numpy default_rng(DUMP_SAMPLE_SEED).integers(0, numel, k): the same positions on every run of the same shapes.
+    Returns what was written, per array."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    left = limit - 1024 * len(host)          # room for the .npy headers
+    info = {}
+    for n_left, name in zip(range(len(host), 0, -1), sorted(host, key=lambda k: host[k].nbytes)):
+        a = host[name]
+        share = left // n_left
+        rec = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share:
+            pos = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[pos]
+            rec["sampled_elements"] = int(a.size)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        info[name] = rec
+    return info
 
 
 def _free_port():
@@ -521,7 +563,7 @@ def parity_block(mode, dev):
 
 
 def secondary_configs():
-    """The other single-GPU BASELINE configs, one step each, so that the driver's default run observes them too (round-2 verdict):
+    """The other single-GPU BASELINE configs, one step each, so that a `--full` run of the default line observes them too (round-2 verdict):
     c5 = one GPU's share of the style-transfer sweep (50-step DDIM), c4 = 32 x 30 s, 1000-step mel diffusion, bf16-operand MFMA.
     Each runs in its own process AFTER the c2 line's timed region (own plans / graphs / precision mode, memory returned on exit) and
     reports value, ms_per_step, dtype and its own live roofline block; c4 (fp16sd), c4x2 (fp16x2), c4q, c4bf16x2 (all meet north_star) carry
@@ -532,7 +574,7 @@ def secondary_configs():
         # within minutes; `python bench.py --config c4bf16` still measures it)
         # (c5: a step is a whole 2048-pair sweep, ~45 s: no untimed warm-up sweep - the first timed step carries the one-off graph captures, ~2 s)
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "0" if name == "c5" else "1" if streams == 1 else "3",
-               "--streams", str(streams), "--no-cpu-baseline", "--no-secondary"]
+               "--streams", str(streams), "--full", "--no-cpu-baseline", "--no-secondary"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
@@ -757,11 +799,19 @@ def main():
     last = {}
     shard_out, shard_events = {}, []
 
+    def keep_last_batch(r_idx, t_idx, mel, f0, wav):
+        # --dump-outputs in the sweep: views of the current batch's outputs, replaced when the next batch begins (the last one survives the step)
+        if last.get("sweep_t") != t_idx:
+            last["sweep_t"], last["sweep_rows"] = t_idx, []
+        last["sweep_rows"].append((mel, f0, wav))
+
     def step(i, r=None):
         r = rank if r is None else r
         if sweep_mode:
             st = {}
-            n_pairs, n_frames = style_transfer_sweep(infer, refs, targets, rank=0, world=1, batch=B, ddim_steps=cfg["ddim_steps"], seed=1234 + i, stats=st)
+            emit = keep_last_batch if args.dump_outputs and i == args.steps - 1 else None
+            n_pairs, n_frames = style_transfer_sweep(infer, refs, targets, rank=0, world=1, batch=B, ddim_steps=cfg["ddim_steps"], seed=1234 + i, stats=st,
+                                                     emit=emit)
             last["frames"] = n_frames
             last["sweep_stats"] = st
             return None
@@ -772,7 +822,7 @@ def main():
         e1.record()
         gather_events.append((e0, e1))
         own = slice(r * B, (r + 1) * B) if world > 1 else slice(None)   # the gathered buffer is rank-major: rows of shard r
-        last["mel"], last["r"] = mel, r
+        last["mel"], last["f0"], last["lens"], last["r"] = mel, f0, lens, r
         if n_emul > 1:
             shard_out[r] = (mel, f0, lens)
         if voc_stream is None:
@@ -833,9 +883,19 @@ def main():
     dt = float(tmax.item())
     if wav is not None:
         assert torch.isfinite(wav).all(), "non-finite waveform"
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything else runs on the plans' workspaces
+        if sweep_mode:
+            rows = last["sweep_rows"]
+            arrays = {"mel": torch.stack([m for m, _, _ in rows]), "f0": torch.stack([f for _, f, _ in rows])}
+            if rows[0][2] is not None:
+                arrays["wav"] = torch.stack([w for _, _, w in rows])
+        else:
+            arrays = {"mel": last["mel"], "f0": last["f0"], "lens": last["lens"], "wav": wav}
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(arrays, args.dump_outputs)}
     # reference point, outside the timed region: the same steps strictly one batch at a time (no overlap between batches)
     single = None
-    if step_streams is not None and not sweep_mode and n_emul == 1:
+    if args.full and step_streams is not None and not sweep_mode and n_emul == 1:
         n1 = min(args.steps, 3)
         sync()
         t1 = time.perf_counter()
@@ -938,7 +998,7 @@ def main():
                            "allgather_ms": gather_ms, "allgather_bytes_per_rank": B * T * 82 * 4}
         if args.checksum:
             out["checksum"] = {"mel_items": mel_items}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             rl = kernel_roofline(infer, B, T, bf16)
             rl["launches_per_step"] = 20 * S_mel
             # the whole time budget from this round's committed rocprofv3 summaries (read at run time; shares are of GPU time of THAT profiled
@@ -967,21 +1027,23 @@ def main():
                 mel_exec = MEL_FLOP_PER_FRAME_STEP - MEL_COND_FLOP - MEL_GATE_FLOP * wino_saved
                 rl["mel_loop_in_run"] = mel_loop_in_run(infer, B, T, S_mel, mel_exec, peak)
             out["roofline"] = rl
-        if world == 1 and not args.no_cpu_baseline and n_emul == 1:
+        if args.full and world == 1 and not args.no_cpu_baseline and n_emul == 1:
             out["cpu_baseline"] = cpu_baseline(dict(timesteps=100, K_step=100, f0_timesteps=100), args.cpu_threads)
         if x3:
             out["parity"] = {"pinned": True, "mel_l1_vs_reference_goldens": {"100_steps": 7.6e-7, "1000_steps": 1.0e-6}, "north_star_mel_l1": 1e-4,
                              "meets_north_star": True, "measured_on": "tests/test_gpu_round3.py::test_bf16x3_mode_matches_the_reference_golden_chain, "
                                                                        "profiles/r03_parity.json"}
-        if split:
+        if args.full and split:
             out["parity"] = parity_block("fp16sd" if getattr(infer.model, "sd", False) else "fp16q4" if getattr(infer.model, "q4", False) else "fp16x2" if getattr(infer.model, "f16", False) else "bf16x2", dev)
-        elif bf16:   # no reference arithmetic exists for bf16 operands: the distance to the fp32 reference is a measured fact, not parity
+        elif args.full and bf16:   # no reference arithmetic exists for bf16 operands: the distance to the fp32 reference is a measured fact, not parity
             live = measure_parity_on_1000_step_golden("bf16", dev)
             out["parity"] = {"pinned": False, "measured_in_this_run": live, "mel_l1_vs_fp32_reference": live["mel_l1"], "north_star_mel_l1": 1e-4,
                              "meets_north_star": live["mel_l1"] <= 1e-4}
-        if world == 1 and n_emul == 1 and args.config == "c2" and not args.no_secondary and not (args.batch or args.frames or args.diff_steps):
+        if args.full and world == 1 and n_emul == 1 and args.config == "c2" and not args.no_secondary and not (args.batch or args.frames or args.diff_steps):
             torch.cuda.empty_cache()
             out["secondary"] = secondary_configs()
+        if dumped is not None:
+            out["outputs"] = dumped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

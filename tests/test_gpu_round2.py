@@ -246,6 +246,26 @@ def test_bench_two_ranks_on_one_device_matches_single_process():
     assert two3["checksum"]["mel_items"] == one3["checksum"]["mel_items"], (two3["checksum"], one3["checksum"])
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned (mel, f0, lens, wav) as float32 .npy files: the mel is the one the
+    step's checksum was taken of, and a second run with the same arguments writes the same arrays bit for bit. A plain run carries only the
+    headline: the measurements of `--full` stay out of its line."""
+    import numpy as np
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "0", "--batch", "2", "--frames", "192", "--diff-steps", "4", "--checksum"]
+    a = _run_bench(small + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run_bench(small + ["--dump-outputs", str(tmp_path / "b")])
+    assert a["steps"] == 2 and a["ms_per_step"] > 0 and a["value"] > 0
+    assert not {"one_batch_at_a_time", "roofline", "cpu_baseline", "parity", "secondary"} & set(a)
+    assert sorted(a["outputs"]["arrays"]) == ["f0", "lens", "mel", "wav"]
+    for name in ("mel", "f0", "lens", "wav"):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape[0] == 2 and np.isfinite(x).all(), name
+        assert np.array_equal(x, y), name
+    mel = np.load(tmp_path / "a" / "mel.npy").astype(np.float64)
+    assert mel.shape[2] == 80
+    np.testing.assert_allclose(mel.sum(axis=(1, 2)), a["checksum"]["mel_items"], rtol=1e-9, atol=1e-9 * np.abs(mel).sum())
+
+
 def _gemm_bf16(A, Wp, **kw):
     from stylesinger_amd import lib as L
     L.gemm_bf16(A, Wp, **kw)

@@ -4,7 +4,7 @@
 # Output goes to gpurun_out/ (scratch, merged back by gpurun); what is quoted in DESIGN.md / README.md is copied to profiles/.
 # Sections:
 #   tests            python -m pytest tests -m gpu            (the parity tests proper; measured distances -> parity_measurements.jsonl)
-#   bench [args]     python bench.py [args]                   (the driver's line; default = c2 + cpu_baseline + secondary c5 / c4)
+#   bench [args]     python bench.py [args]                   (the headline line; with --full: + roofline, cpu_baseline, parity, secondary c5 / c4)
 #   profile [args]   rocprofv3 --kernel-trace --stats of `bench.py --streams 1 --steps 4 --warmup 1 --no-cpu-baseline --no-secondary [args]`
 #   pmc-gate         PMC passes on the dominant kernel launch (one counter block per pass, --kernel-trace --pmc only)
 #   pmc-gate-c4x2    the same for the split-operand (bf16x2) 256x256 gate kernel at the C4 shape (tools/pmc_split.sh)
