@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SS_ABI_VERSION 19 /* 19: the residual stream of ss_layer512 as (H, fp16 remainder) instead of an fp32 copy (ss_layer512_args.cur_bias; P halves); 18: fp16 addend sets of ss_layer512 (ss_layer512_args.e_f16, ss_layer512_tile_addend_f16, ss_layer512_addend_halfs, ss_wavenet.n_esets), knob skip_dense; 17: compact gate rows (ss_layer512_args.g_compact, ss_gemm_bf16_args.a_compact), compact one-term skip weights (ss_gemm_bf16_args.one_product = 2, ss_wavenet.w_skipall_c); 16: ss_layer512 (one launch per residual layer of the fp16x2 mel denoiser: gate + residual projection with G kept in LDS), ss_layer512_pack_gate / _pack_res / _tile_addend, ss_wavenet.w_dil_f / w_out_f, knob layer512, ss_round_f16_rows takes the items' own lengths, ss_set_q4_guard, ss_mel_denorm reports non-finite frames, "fp16sd" (ss_wavenet.n_wsets / mfma_products / ws_*, ss_layer512_args.n_products); 15: ss_f0track (f0 tracker of the input producers), ss_f0track_params, ss_vad_trim, ss_normalize_volume, ss_round_f16_rows, knob q4_force; removed ss_gemm_bf16_tile128 and the knobs tile128 / skip_deep (measured: no gain); 14: fp16q4 gate (ss_gemm_bf16_args.split = 3 + q_scale, ss_gemm_bf16_gate128q, ss_gate128q_kindex), ss_gemm_bf16_gate128 / _tile128, tuning knobs gate128 / tile128 / skip_deep; 13: fp16x2 mode (ss_gemm_bf16_args.split = 2 + out_scale, ss_split_f16, ss_wavenet.mfma_split = 2 + mfma_out_scale); 12: bf16x2 split-operand mode (ss_gemm_bf16_args.split, ss_split_bf16, ss_wavenet.mfma_split), DDIM eta + double schedule, tuning knob table; 2: grouped launches + Winograd weights; 3: mfma_bf16 fields, samplers, front end, writer; 4: deferred skip; 5: folded skip projection; 6: PLMS step_hi, per-item Philox counters, ss_fill_normal_rows, ProDiff sampler, emotion LSTM; 7: bf16-in-HBM GEMM + bf16 weight copies; 9: input producers (ss_norm_interp_f0, ss_spec_power, ss_reflect_pad), ss_wino43_gate16, ss_gemm16_res; 10: ss_wino43_conv + Winograd packs in ss_hifigan; 11: bf16x3 mode (ss_wino43_gate16x, ss_split3_weights, ss_wavenet.w_dil_x3), ss_wino43_gate16w + ss_pack_gate16_weights */
+#define SS_ABI_VERSION 20 /* 20: removed the knobs htile, wino_tn, wino_v1, res_tile, skip_tile, res16, skip16, e16 and the static wave-priority knob (A/B switches for superseded forms; each now does what its default did); 19: the residual stream of ss_layer512 as (H, fp16 remainder) instead of an fp32 copy (ss_layer512_args.cur_bias; P halves); 18: fp16 addend sets of ss_layer512 (ss_layer512_args.e_f16, ss_layer512_tile_addend_f16, ss_layer512_addend_halfs, ss_wavenet.n_esets), knob skip_dense; 17: compact gate rows (ss_layer512_args.g_compact, ss_gemm_bf16_args.a_compact), compact one-term skip weights (ss_gemm_bf16_args.one_product = 2, ss_wavenet.w_skipall_c); 16: ss_layer512 (one launch per residual layer of the fp16x2 mel denoiser: gate + residual projection with G kept in LDS), ss_layer512_pack_gate / _pack_res / _tile_addend, ss_wavenet.w_dil_f / w_out_f, knob layer512, ss_round_f16_rows takes the items' own lengths, ss_set_q4_guard, ss_mel_denorm reports non-finite frames, "fp16sd" (ss_wavenet.n_wsets / mfma_products / ws_*, ss_layer512_args.n_products); 15: ss_f0track (f0 tracker of the input producers), ss_f0track_params, ss_vad_trim, ss_normalize_volume, ss_round_f16_rows, knob q4_force; removed ss_gemm_bf16_tile128 and the knobs tile128 / skip_deep (measured: no gain); 14: fp16q4 gate (ss_gemm_bf16_args.split = 3 + q_scale, ss_gemm_bf16_gate128q, ss_gate128q_kindex), ss_gemm_bf16_gate128 / _tile128, tuning knobs gate128 / tile128 / skip_deep; 13: fp16x2 mode (ss_gemm_bf16_args.split = 2 + out_scale, ss_split_f16, ss_wavenet.mfma_split = 2 + mfma_out_scale); 12: bf16x2 split-operand mode (ss_gemm_bf16_args.split, ss_split_bf16, ss_wavenet.mfma_split), DDIM eta + double schedule, tuning knob table; 2: grouped launches + Winograd weights; 3: mfma_bf16 fields, samplers, front end, writer; 4: deferred skip; 5: folded skip projection; 6: PLMS step_hi, per-item Philox counters, ss_fill_normal_rows, ProDiff sampler, emotion LSTM; 7: bf16-in-HBM GEMM + bf16 weight copies; 9: input producers (ss_norm_interp_f0, ss_spec_power, ss_reflect_pad), ss_wino43_gate16, ss_gemm16_res; 10: ss_wino43_conv + Winograd packs in ss_hifigan; 11: bf16x3 mode (ss_wino43_gate16x, ss_split3_weights, ss_wavenet.w_dil_x3), ss_wino43_gate16w + ss_pack_gate16_weights */
 #define SS_MAX_TAPS 16
 #define SS_MAX_LAYERS 32
 
@@ -37,26 +37,22 @@ int ss_device_info(int dev, int* n_cu, char* arch, int arch_len);
 /* out[0..2] = sizeof(ss_conv_gemm_args), sizeof(ss_wavenet), sizeof(ss_hifigan) (+ out[3] = sizeof(ss_gemm_bf16_args) when n >= 4):
  * lets a binding verify its mirror */
 int ss_struct_sizes(int64_t* out, int n);
-/* process-wide performance knobs (results never change): "wave_prio" = 0|1|2 static per-workgroup wave priority in the MFMA
- * kernels (0 = none, 1 = (blockIdx/256)%3, 2 = blockIdx%3); "gate16" = 0|1|2|3 tiling of the F(4,3) gate launches inside the
+/* process-wide performance knobs (results never change): "gate16" = 0|1|2|3 tiling of the F(4,3) gate launches inside the
  * denoiser loops (1 = per-launch pick, default; 0 = 32x32x2 tiles; 2|3 = force 16x16x4 tiles of 16*MT quads); "gate16_ks" = 0|1
- * the 16x16x4 gate kernel stages one Winograd component per barrier (0) or all six of a K chunk at once (1, default); "res_tile" /
- * "skip_tile" = SS_TILE_* override for the residual-half projection / the K = L*C skip GEMM (0 = built-in choice); "gate256" = 0|1 bf16 GATE launches on the 256x256 LDS-DMA kernel when they
- * qualify (default 1); "res16" / "skip16" = 0|1|4|6|8
- * residual-half projection on ss_gemm16_res / skip GEMM on ss_gemm16_store (1 = on, row tile picked per launch, default; 0 =
- * ss_conv_gemm; 4|6|8 = force 16*mt rows); experiment switches "htile" = 0|64|128 (row tile of the generic bf16 kernel), "wino_tn" = 0|1|2 and
- * "wino_v1" = 0|1 (F(2,3) gate: column tile, round-1 kernel); "voc_wino_max_mb" = 1..2048: vocoder items whose stage panel reaches this many MiB
- * take the direct conv kernel instead of the grouped-Winograd one (32-bit offsets; default 2048 = the real limit, tests lower it); "e16" = 0|1
- * the fp32 denoiser loops hand the 16x16x4 gate its conditioner addend in fetch order (ss_gate16_tile_addend once per forward; default 1);
- * "mel_tail" = 0|1 small launches (<= 8 frames per CU) run the mel sampler's output projection + update + next input projection as one launch;
- * "gate128" = 0|1 fp16x2 GATE launches of very many tiles on ss_gemm_bf16_gate128 (two workgroups per CU; default 1); "q4_force" = 0|1 the
- * fp16q4 kernels (ss_gemm_bf16_gate128q / _tile256q) take any launch they can compute, not only those that fill the chip (default 0; the parity
- * tests run one 30 s item through them); "layer512" = 0|1|2 the fp16x2 mel stack as one ss_layer512 launch per layer when the shape qualifies
- * (default 1; 0 = the gate + residual-projection launch pair; 2 = also for launches that do not fill the chip: the parity tests run one item through it); "layer512_tail" = 0|1|2 ss_layer512 runs the tiles of
- * an under-filled last round as half tiles (default 1: the even workgroups take their half tile FIRST, which puts the two halves of the chip half a tile period out of phase - one
- * streams through HBM while the other multiplies; 2: every half tile last; 0: whole tiles only; identical results); "skip_dense" = 0|1 (default 1) the skip GEMM with both operands compact (a_compact and one_product = 2) runs 64 channels per
- * step with every DMA lane live; 0 keeps the 32-channel steps (identical results). The library reads NO environment variable: a direct C caller sets knobs here (the Python binding
- * forwards SS_* variables once at load). */
+ * the 16x16x4 gate kernel stages one Winograd component per barrier (0) or all six of a K chunk at once (1, default); "gate256" = 0|1
+ * bf16 GATE launches on the 256x256 LDS-DMA kernel when they qualify (default 1); "voc_wino_max_mb" = 1..2048: vocoder items whose stage
+ * panel reaches this many MiB take the direct conv kernel instead of the grouped-Winograd one (32-bit offsets; default 2048 = the real limit,
+ * tests lower it); "mel_tail" = 0|1 small launches (<= 8 frames per CU) run the mel sampler's output projection + update + next input
+ * projection as one launch (default 1); "gate128" = 0|1 fp16x2 GATE launches of very many tiles on ss_gemm_bf16_gate128 (two workgroups per
+ * CU; default 1); "q4_force" = 0|1 the fp16q4 kernels (ss_gemm_bf16_gate128q / _tile256q) take any launch they can compute, not only those
+ * that fill the chip (default 0; the parity tests run one 30 s item through them); "layer512" = 0|1|2 the fp16x2 mel stack as one
+ * ss_layer512 launch per layer when the shape qualifies (default 1; 0 = the gate + residual-projection launch pair; 2 = also for launches
+ * that do not fill the chip: the parity tests run one item through it); "layer512_tail" = 0|1|2 ss_layer512 runs the tiles of an
+ * under-filled last round as half tiles (default 1: the even workgroups take their half tile FIRST, which puts the two halves of the chip
+ * half a tile period out of phase - one streams through HBM while the other multiplies; 2: every half tile last; 0: whole tiles only;
+ * identical results); "skip_dense" = 0|1 (default 1) the skip GEMM with both operands compact (a_compact and one_product = 2) runs 64
+ * channels per step with every DMA lane live; 0 keeps the 32-channel steps (identical results). The library reads NO environment variable:
+ * a direct C caller sets knobs here (the Python binding forwards SS_* variables once at load). */
 int ss_set_tuning(const char* key, int value);
 /* current value of a tuning knob (>= 0), or < 0 for an unknown key */
 int ss_get_tuning(const char* key);

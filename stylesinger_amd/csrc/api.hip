@@ -14,26 +14,20 @@ void ss_set_error(const char* fmt, ...) {
 
 extern "C" const char* ss_last_error(void) { return g_err; }
 
-SsTuning g_ss_tuning = {0, nullptr, 1, 0, 0, 1, 1, 1, 1, 0, 0, 0, 2048, 1, 1, 1, 0, 1, 1, 1};
+SsTuning g_ss_tuning = {nullptr, 1, 1, 1, 2048, 1, 1, 0, 1, 1, 1};
 
 namespace {
 struct Knob { const char* key; int* slot; bool (*ok)(int); };
 bool ok_01(int v) { return v == 0 || v == 1; }
 bool ok_012(int v) { return v >= 0 && v <= 2; }
 bool ok_0123(int v) { return v >= 0 && v <= 3; }
-bool ok_mt(int v) { return v == 0 || v == 1 || v == 4 || v == 6 || v == 8; }
-bool ok_tile(int v) { return v >= SS_TILE_AUTO && v <= SS_TILE_128x32; }
-bool ok_htile(int v) { return v == 0 || v == 64 || v == 128; }
 bool ok_mb(int v) { return v >= 1 && v <= 2048; }
 const Knob* knobs(int* n) {
   static const Knob k[] = {
-      {"wave_prio", &g_ss_tuning.wave_prio, ok_012},   {"gate16", &g_ss_tuning.gate16, ok_0123},     {"gate16_ks", &g_ss_tuning.gate16_ks, ok_01},
-      {"gate256", &g_ss_tuning.gate256, ok_01},        {"res16", &g_ss_tuning.res16, ok_mt},          {"skip16", &g_ss_tuning.skip16, ok_mt},
-      {"res_tile", &g_ss_tuning.res_tile, ok_tile},    {"skip_tile", &g_ss_tuning.skip_tile, ok_tile}, {"htile", &g_ss_tuning.htile, ok_htile},
-      {"wino_tn", &g_ss_tuning.wino_tn, ok_012},       {"wino_v1", &g_ss_tuning.wino_v1, ok_01},      {"voc_wino_max_mb", &g_ss_tuning.voc_wino_max_mb, ok_mb},
-      {"e16", &g_ss_tuning.e16, ok_01},                {"mel_tail", &g_ss_tuning.mel_tail, ok_01},     {"gate128", &g_ss_tuning.gate128, ok_01},
-      {"q4_force", &g_ss_tuning.q4_force, ok_01},      {"layer512", &g_ss_tuning.layer512, ok_012},
-      {"layer512_tail", &g_ss_tuning.layer512_tail, ok_012},       {"skip_dense", &g_ss_tuning.skip_dense, ok_01},
+      {"gate16", &g_ss_tuning.gate16, ok_0123},         {"gate16_ks", &g_ss_tuning.gate16_ks, ok_01},     {"gate256", &g_ss_tuning.gate256, ok_01},
+      {"voc_wino_max_mb", &g_ss_tuning.voc_wino_max_mb, ok_mb}, {"mel_tail", &g_ss_tuning.mel_tail, ok_01}, {"gate128", &g_ss_tuning.gate128, ok_01},
+      {"q4_force", &g_ss_tuning.q4_force, ok_01},       {"layer512", &g_ss_tuning.layer512, ok_012},      {"layer512_tail", &g_ss_tuning.layer512_tail, ok_012},
+      {"skip_dense", &g_ss_tuning.skip_dense, ok_01},
   };
   *n = (int)(sizeof(k) / sizeof(k[0]));
   return k;

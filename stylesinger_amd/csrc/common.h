@@ -39,24 +39,14 @@ void ss_set_error(const char* fmt, ...);
 static inline int ss_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Run-time tuning knobs (ss_set_tuning): process-wide, read at launch time, never change results.
-//   wave_prio: 0 = all waves at priority 0; 1 = static s_setprio((blockIdx / 256) % 3); 2 = s_setprio(blockIdx % 3).
-//     The blocks sharing a CU then differ in priority, so the matrix pipe of a SIMD serves them one after the other instead
-//     of round-robin: their non-MFMA phases (staging, barrier) stop coinciding (launch structure).
 //   gate16: tiling of the Winograd F(4,3) gate launch. 1 (default) = pick per launch (ss_wino43_gate16_pick: 16x16x4 tiles of
 //     16*MT quads when that fills the chip better, else the 32x32x2 kernel); 0 = always the 32x32x2 kernel; 2 / 3 = force MT.
-//   res_tile / skip_tile: SS_TILE_* override of the residual-half projection / the K = L*C skip GEMM of the denoiser loops
-//     (0 = the built-in choice); validated by ss_set_tuning.
-//   res16: 1 (default) = the residual-half projection of the deferred-skip loops runs on ss_gemm16_res (16x16x4 tiles, LDS-DMA);
-//     0 = ss_conv_gemm; 4 / 6 / 8 = force the row tile.
-//   skip16: the same switch for the K = L*C skip GEMM (ss_gemm16_store).
 //   gate16_ks: 1 (default) = the 16x16x4 gate kernel stages all six Winograd components of a K chunk at once (one barrier per K chunk, 48 / 72 KB
 //     of LDS); 0 = one component per barrier (8 / 12 KB).
 //   gate256: 1 (default) = bf16 GATE launches that qualify (ss_gemm_bf16_gate256_ok) run on the 256x256 LDS-DMA kernel; 0 = always the
 //     generic bf16 kernel.
-//   htile: row tile of the generic bf16 kernel (0 = built-in choice, 64 | 128 = force); wino_tn: column tile of the F(2,3) gate (0 = pick,
-//     1 = 64, 2 = 128 columns); wino_v1: 1 = the round-1 F(2,3) kernel (A/B against v2).
-//   e16: 1 (default) = the fp32 denoiser loops re-lay the conditioner addend of every 16x16x4 gate launch in that kernel's fetch order once per
-//     forward (ss_gate16_tile_addend); 0 = the gate reads the row-major slab (A/B; results are bit-identical).
+//   gate128: 1 (default) = fp16x2 GATE launches of very many tiles that qualify (ss_gemm_bf16_gate128_ok) run on ss_gemm_bf16_gate128 (two
+//     workgroups per CU); 0 = never.
 //   mel_tail: 1 (default) = for launches of at most 8 frames per CU (one short utterance) the mel sampler runs output projection + DDPM update +
 //     the next input projection as one VALU launch (mel_tail_kernel); 0 = always the two matrix-core launches.
 //   voc_wino_max_mb: the vocoder's grouped-Winograd convs address an item with 32-bit byte offsets; items whose stage panel (+ halo) reaches
@@ -72,8 +62,8 @@ static inline int ss_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 //     with dead DMA lanes (A/B; results are identical: the same products enter every accumulator in the same order).
 //   q4_force: 0 (default) = the fp16q4 kernels take only launches that fill the chip (their _ok rules); 1 = any launch they can compute (parity tests run
 //     one 30 s item through them).
-struct SsTuning { int wave_prio; unsigned long long* clock_probe; int gate16; int res_tile; int skip_tile; int res16; int skip16; int gate256; int gate16_ks;
-                  int htile; int wino_tn; int wino_v1; int voc_wino_max_mb; int e16; int mel_tail; int gate128; int q4_force; int layer512; int layer512_tail; int skip_dense; };
+struct SsTuning { unsigned long long* clock_probe; int gate16; int gate256; int gate16_ks; int voc_wino_max_mb; int mel_tail; int gate128; int q4_force;
+                  int layer512; int layer512_tail; int skip_dense; };
 extern SsTuning g_ss_tuning;
 // fp16q4 range guard (ss_set_q4_guard): while non-null, every fp16q4 launch first reduces max |a| / (6 q_scale) over the fp16 operand it is about
 // to convert to fp4 into guard[which] (which = 0 gate, 1 skip GEMM; float bits, atomicMax): > 1 means the fixed scale saturates
@@ -86,14 +76,6 @@ int ss_n_cu();
 struct ss_conv_gemm_args;
 // gemm16.hip, library-internal: split-K skip GEMM without its reduction launch (the tail kernels of diffusion.hip add the slices)
 int ss_gemm16_store_partials(const ss_conv_gemm_args* args, int mt, int ksplit, float* partials, void* stream);
-
-// static per-block wave priority (wave-uniform; s_setprio takes an immediate)
-__device__ __forceinline__ void ss_apply_wave_prio(int mode) {
-  if (mode == 0) return;
-  const int p = mode == 1 ? (int)((blockIdx.x >> 8) % 3u) : (int)(blockIdx.x % 3u);
-  if (p == 1) __builtin_amdgcn_s_setprio(1);
-  else if (p == 2) __builtin_amdgcn_s_setprio(2);
-}
 
 // ----------------------------------------------------------------------------------------------
 // Device math. Activations follow the torch CPU definitions the reference relies on.

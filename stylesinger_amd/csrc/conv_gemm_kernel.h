@@ -71,7 +71,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_gemm_kernel(const
 #ifdef SS_KERNEL_TIMESTAMPS  // per-wave phase stamps for tools/phase_times.py; never compiled into the shipped library
   const unsigned long long ts0 = (dbg & 16) ? __builtin_readcyclecounter() : 0ull;
 #endif
-  ss_apply_wave_prio(dbg & 3);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -614,16 +613,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_gemm_kernel(const
 #endif
 }
 
-inline int dbg_flags() {  // bits 0-1: wave priority mode (ss_set_tuning); bit 4: timestamps (debug builds only)
+inline int dbg_flags() {  // bit 4: timestamps (debug builds only)
 #ifdef SS_KERNEL_TIMESTAMPS
   static int v = -1;
   if (v < 0) {
     const char* e = getenv("SS_DBG");
-    v = e ? (atoi(e) & ~3) : 0;
+    v = e ? atoi(e) : 0;
   }
-  return v | (g_ss_tuning.wave_prio & 3);
+  return v;
 #else
-  return g_ss_tuning.wave_prio & 3;
+  return 0;
 #endif
 }
 

@@ -89,12 +89,12 @@ WsLayout ws_layout(const ss_wavenet* net, int B, int T, void* base) {
   const bool h = hmode(net);
   w.GA = (net->w_skipall && !h) ? take(rows * net->L * net->C) : nullptr;
   // fp32 F(4,3) loops on the 16x16x4 gate kernel: every layer's slab of E is re-laid once per forward in that kernel's fetch order
-  // (ss_gate16_tile_addend), so that a wave's addend fetch is 1 KB contiguous per instruction instead of 8 lines x 32 B ("e16" knob)
+  // (ss_gate16_tile_addend), so that a wave's addend fetch is 1 KB contiguous per instruction instead of 8 lines x 32 B
   for (int l = 0; l < SS_MAX_LAYERS; ++l) {
     w.E16[l] = nullptr;
     w.mt16[l] = 0;
   }
-  if (!h && !net->mfma_bf16 && !net->mfma_x3 && net->wino_m == 4 && g_ss_tuning.gate16 != 0 && g_ss_tuning.e16 != 0)
+  if (!h && !net->mfma_bf16 && !net->mfma_x3 && net->wino_m == 4 && g_ss_tuning.gate16 != 0)
     for (int l = 0; l < net->L && l < SS_MAX_LAYERS; ++l) {
       if (!net->w_dil_wino[l] || !net->w_dil_wino16[l]) continue;
       const int d = 1 << (l % net->dil_cycle);
@@ -105,7 +105,7 @@ WsLayout ws_layout(const ss_wavenet* net, int B, int T, void* base) {
       w.E16[l] = take(fl);
       w.mt16[l] = mt;
     }
-  w.ksplit = (net->w_skipall && !h && !net->mfma_bf16 && g_ss_tuning.skip16 != 0 && (net->C & 3) == 0) ? ss_gemm16_ksplit_pick(B, T, net->C, net->L * net->C) : 1;
+  w.ksplit = (net->w_skipall && !h && !net->mfma_bf16 && (net->C & 3) == 0) ? ss_gemm16_ksplit_pick(B, T, net->C, net->L * net->C) : 1;
   w.KP = w.ksplit > 1 ? take((int64_t)w.ksplit * rows * net->C) : nullptr;
   const int planes = smode(net) ? 2 : 1;
   w.Yh = h ? (uint16_t*)take((rows * net->C * planes + 1) / 2) : nullptr;
@@ -397,7 +397,7 @@ int stack_entry_h(const ss_wavenet* net, int step, const int32_t* lens, int B, i
 // partials_ok: the caller's next kernel (f0_tail_kernel / mel_tail_kernel) can add the split-K slices of the skip GEMM itself (skip_partials()
 // tells it whether it has to): the reduction launch is then left out
 inline bool skip_partials(const ss_wavenet* net, const WsLayout& w) {
-  return w.ksplit > 1 && net->skipall_folded && !hmode(net) && !net->mfma_bf16 && g_ss_tuning.skip16 != 0 && !(net->mfma_x3 && net->w_skipall_x3);
+  return w.ksplit > 1 && net->skipall_folded && !hmode(net) && !net->mfma_bf16 && !(net->mfma_x3 && net->w_skipall_x3);
 }
 int run_residual_stack(const ss_wavenet* net, int step, const int32_t* lens, int B, int T, const WsLayout& w,
                        hipStream_t stream, bool partials_ok = false) {
@@ -473,7 +473,7 @@ int run_residual_stack(const ss_wavenet* net, int step, const int32_t* lens, int
     o.Cin = C;
     o.W = net->w_out[l];
     o.N = defer ? C : 2 * C;  // deferred skip: only the residual half (the first C packed rows) runs per layer
-    if (defer) o.tile = g_ss_tuning.res_tile > 0 ? g_ss_tuning.res_tile : SS_TILE_64x64;
+    if (defer) o.tile = SS_TILE_64x64;
     o.Np = 2 * C;
     o.Kp = round_up32(C);
     o.epi = SS_EPI_RESSKIP;
@@ -496,12 +496,11 @@ int run_residual_stack(const ss_wavenet* net, int step, const int32_t* lens, int
       o.w_group_stride = net->gs_w_out;
       o.bias_group_stride = net->gs_b_out;
     }
-    const int r16 = g_ss_tuning.res16;
-    if (defer && r16 != 0 && !net->mfma_bf16 && (C == 192 || C == 256) && net->w_out16[l]) {   // weights in the kernel's fetch order
+    if (defer && !net->mfma_bf16 && (C == 192 || C == 256) && net->w_out16[l]) {   // weights in the kernel's fetch order
       o.w_group_stride = net->gs_w_out16;
-      SS_PROPAGATE(ss_gemm16_resw(&o, net->w_out16[l], r16 == 1 ? 0 : r16, stream));
-    } else if (defer && r16 != 0 && !net->mfma_bf16 && (C == 192 || C == 256)) {
-      SS_PROPAGATE(ss_gemm16_res(&o, r16 == 1 ? 0 : r16, stream));   // 16x16x4 tiles, balanced single round (gemm16.hip)
+      SS_PROPAGATE(ss_gemm16_resw(&o, net->w_out16[l], 0, stream));
+    } else if (defer && !net->mfma_bf16 && (C == 192 || C == 256)) {
+      SS_PROPAGATE(ss_gemm16_res(&o, 0, stream));   // 16x16x4 tiles, balanced single round (gemm16.hip)
     } else {
       SS_PROPAGATE(ss_conv_gemm(&o, stream));
     }
@@ -521,30 +520,30 @@ int run_residual_stack(const ss_wavenet* net, int step, const int32_t* lens, int
     k.C = w.S;
     k.ldc = C;
     k.c_batch_stride = (int64_t)T * C;
-    k.tile = g_ss_tuning.skip_tile > 0 ? g_ss_tuning.skip_tile : SS_TILE_64x64;
+    k.tile = SS_TILE_64x64;
     k.mfma_bf16 = net->mfma_bf16;
     if (net->n_groups > 1) {
       k.group_size = B / net->n_groups;
       k.w_group_stride = net->gs_w_skipall;
       k.bias_group_stride = net->gs_b_skipall;
     }
-    int s16 = g_ss_tuning.skip16;
-    const bool use16 = s16 != 0 && !net->mfma_bf16 && k.Kp == k.Cin;   // 16x16x4 tiles, both operands by LDS-DMA (gemm16.hip)
-    // long-K launch: when 64-row tiles also fit one round at three workgroups per CU they beat the 96-row pick (mel at C2: 240.7 vs 250.7 us)
-    if (s16 == 1 && (long)((T + 63) / 64) * B * ((C + 63) / 64) <= 3L * ss_n_cu() && !(net->mfma_x3 && net->w_skipall_x3)) s16 = 4;
+    const bool use16 = !net->mfma_bf16 && k.Kp == k.Cin;   // 16x16x4 tiles, both operands by LDS-DMA (gemm16.hip)
+    // row tile 16 * mt16 (0 = picked per launch). Long-K launch: when 64-row tiles also fit one round at three workgroups per CU they beat
+    // the 96-row pick (mel at C2: 240.7 vs 250.7 us)
+    const int mt16 = (long)((T + 63) / 64) * B * ((C + 63) / 64) <= 3L * ss_n_cu() && !(net->mfma_x3 && net->w_skipall_x3) ? 4 : 0;
     if (net->skipall_folded) {  // w_skipall already carries skip_projection / sqrt(L): this GEMM + ReLU is the stack's output
       k.act = SS_ACT_RELU;
       k.C = w.G;
       if (use16 && net->mfma_x3 && net->w_skipall_x3) {   // opt-in bf16x3 mode: split operands on the bf16 matrix cores (gemm16x.hip)
         k.w_group_stride = net->gs_w_skipall_x3;
-        return ss_gemm16x_store(&k, net->w_skipall_x3, s16 == 1 ? 0 : s16, stream);
+        return ss_gemm16x_store(&k, net->w_skipall_x3, mt16, stream);
       }
       if (use16 && w.ksplit > 1)   // one short utterance: split K over the idle CUs
         return partials_ok && skip_partials(net, w) ? ss_gemm16_store_partials(&k, 4, w.ksplit, w.KP, stream) : ss_gemm16_store_splitk(&k, 4, w.ksplit, w.KP, stream);
-      return use16 ? ss_gemm16_store(&k, s16 == 1 ? 0 : s16, stream) : ss_conv_gemm(&k, stream);
+      return use16 ? ss_gemm16_store(&k, mt16, stream) : ss_conv_gemm(&k, stream);
     }
     if (use16 && w.ksplit > 1) SS_PROPAGATE(ss_gemm16_store_splitk(&k, 4, w.ksplit, w.KP, stream));
-    else SS_PROPAGATE(use16 ? ss_gemm16_store(&k, s16 == 1 ? 0 : s16, stream) : ss_conv_gemm(&k, stream));
+    else SS_PROPAGATE(use16 ? ss_gemm16_store(&k, mt16, stream) : ss_conv_gemm(&k, stream));
   }
   // x = relu(skip_projection(sum(skip) / sqrt(L)))   (net.py:124-127)
   ss_conv_gemm_args s = base_args(B, T, lens);

@@ -23,12 +23,6 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// SS_R16_ABL (debug builds only, tools/ablate_r16.sh; results are wrong by design), gemm16_res_kernel: 1 = no weight preload, 2 = no A
-// DMA after the first two chunks, 3 = no MFMAs, 4 = no residual-stream loads, 5 = no output stores, 6 = no barriers in the loop
-#ifndef SS_R16_ABL
-#define SS_R16_ABL 0
-#endif
-
 namespace {
 
 constexpr int BK = 32;
@@ -56,8 +50,8 @@ __device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, float* lds_d
 // WL = weight layout: false = packed rows [Np][Kp]; true = the lane-contiguous repack of ss_pack_gemm16_weights
 // ([n tile][wave][K chunk][half][lane][4 floats]): one fetch instruction of a wave = 1 KB contiguous instead of 16 columns x 64 B
 // The kernel body as a device function of (workgroup id, LDS base of 3 * 16 MT * LD floats): the __global__ wrapper below passes blockIdx.x and its
-// static LDS; the dataflow experiment of fused_gate_res.hip (round 5) calls the same body from a launch that also holds the gate's workgroups.
-template <int MT, int KCH, bool WL, int A_AUX = 0>
+// static LDS.
+template <int MT, int KCH, bool WL>
 __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, const float* __restrict__ W16, int m_tiles_per_item, int m_tiles, int n_tiles,
                                                 const int block_id, float* __restrict__ lds_) {
   constexpr int BM = 16 * MT;
@@ -107,20 +101,15 @@ __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, cons
   float4 bw[3][2];
   auto load_w = [&](auto jtag) {
     constexpr int j = decltype(jtag)::value;
-    if constexpr (SS_R16_ABL == 1) {
-      bw[j % 3][0] = make_float4(0.01f * lane, 0.02f, 0.03f * j, 0.04f);
-      bw[j % 3][1] = make_float4(0.05f, 0.06f * lane, 0.07f, 0.08f * j);
+    if constexpr (WL) {
+      bw[j % 3][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff, j * 2048, 0));
+      bw[j % 3][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff, j * 2048 + 1024, 0));
     } else {
-      if constexpr (WL) {
-        bw[j % 3][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff, j * 2048, 0));
-        bw[j % 3][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff, j * 2048 + 1024, 0));
-      } else {
-        bw[j % 3][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff, j * (BK * 4), 0));
-        bw[j % 3][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + 16, j * (BK * 4), 0));
-      }
+      bw[j % 3][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff, j * (BK * 4), 0));
+      bw[j % 3][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + 16, j * (BK * 4), 0));
     }
   };
-  constexpr int WLD = SS_R16_ABL == 1 ? 0 : 2;   // VMEM instructions of one weight stage
+  constexpr int WLD = 2;   // VMEM instructions of one weight stage
   // ---- epilogue operands: residual-stream tile (rows 16 m + 4 kg + r, column col) and the bias
   const bool col_ok = col < a.N;
   const int oob = col_ok ? 0 : (int)0x80000000;
@@ -143,7 +132,7 @@ __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, cons
   auto dma = [&](float* buf, int c) {
 #pragma unroll
     for (int j = 0; j < DPW; ++j)
-      glds16<A_AUX>(rsrc_a, buf + (wave + 4 * j) * 8 * LD, a_voff[j], c * (BK * 4));
+      glds16<0>(rsrc_a, buf + (wave + 4 * j) * 8 * LD, a_voff[j], c * (BK * 4));
   };
   int a_rd[MT][2];
 #pragma unroll
@@ -175,9 +164,9 @@ __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, cons
     // RC+1 - the 4 MT residual loads and the bias load
     constexpr int RC = KCH >= 3 ? KCH - 3 : 0;   // the chunk that issues the residual-stream loads (before its DMA)
     if constexpr (c + 1 >= KCH) wait_vmcnt<0>();
-    else if constexpr (c == RC + 1 && KCH >= 3) wait_vmcnt<DPW + WLD + 1 + (SS_R16_ABL == 4 ? 0 : 4 * MT)>();
+    else if constexpr (c == RC + 1 && KCH >= 3) wait_vmcnt<DPW + WLD + 1 + 4 * MT>();
     else wait_vmcnt<DPW + WLD>();
-    if constexpr (SS_R16_ABL != 6) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     const float* Ac = bufs[c % NBUF];
     float4 af[MT][2];
 #pragma unroll
@@ -191,20 +180,15 @@ __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, cons
       for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          rv[m][r] = SS_R16_ABL == 4 ? 0.5f * r : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_r, r_base, (16 * m + r) * a.ldr * 4, 0));
+          rv[m][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_r, r_base, (16 * m + r) * a.ldr * 4, 0));
       bs = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_b, col * 4, 0, 0));   // col >= N: out of range -> 0
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (c + 2 < KCH) {
-      if constexpr (SS_R16_ABL != 2) dma(bufs[(c + 2) % NBUF], c + 2);
+      dma(bufs[(c + 2) % NBUF], c + 2);
       load_w(std::integral_constant<int, c + 2>{});
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (SS_R16_ABL == 3) {
-#pragma unroll
-      for (int m = 0; m < MT; ++m) acc[m][0] += af[m][0].x * bw[c % 3][0].x + af[m][1].w * bw[c % 3][1].w;
-      return;
-    }
     // MT independent accumulators per K step: consecutive MFMAs never touch the same one (40-cycle dependent latency, 32-cycle issue)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -241,7 +225,6 @@ __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, cons
     for (int r = 0; r < 4; ++r) {
       float o = (rv[m][r] + (acc[m][r] + bs)) * a.post_scale;
       if (!interior && t0 + 16 * m + 4 * kg + r >= row_lim) o = 0.f;
-      if (SS_R16_ABL == 5 && o != 123456.789f) continue;
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rsrc_c, c_base, (16 * m + r) * a.ldc * 4, 0);
     }
 }
@@ -467,8 +450,6 @@ __global__ void pack_gemm16_kernel(const float* __restrict__ src, float* __restr
 
 }  // namespace
 
-#ifndef SS_FUSED_TU   // fused_gate_res.hip includes this file for the kernel bodies above only
-
 // row-tile count (16*mt rows per workgroup) for a launch of B items x T rows x N columns: fewest workgroup layers per CU x rows per tile
 extern "C" int ss_gemm16_pick(int B, int T, int N) {
   const int n_tiles = ss_cdiv(N, BN);
@@ -581,4 +562,3 @@ extern "C" int ss_gemm16_ksplit_pick(int B, int T, int N, int K) {
   if (s > 16) s = 16;
   return s < 1 ? 1 : s;
 }
-#endif  // SS_FUSED_TU

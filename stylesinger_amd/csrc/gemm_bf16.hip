@@ -41,12 +41,6 @@ __device__ __forceinline__ uint16_t f2bf(float x) {  // RNE, like torch's .bfloa
 
 __device__ __forceinline__ float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 
-// SS_HABL (debug builds only, tools/ablate_h.sh): timing ablations. 1 = no global fetches in the loop, 2 = no MFMAs,
-// 3 = no addend loads in the epilogue, 4 = no epilogue stores. Results are wrong by design.
-#ifndef SS_HABL
-#define SS_HABL 0
-#endif
-
 // SPLIT = 1 ("bf16x2"): operands are (hi, mid) bf16 pairs interleaved by 32 channels - a 128-byte K chunk holds 32 channels of BOTH planes
 // (slots 0-3 hi, 4-7 mid), the fetch / staging code is the same, and a chunk feeds 2 k-steps x 3 products (mid*hi, hi*mid, hi*hi) instead of 4 x 1.
 // SPLIT = 2 ("fp16x2"): the same layouts with fp16 terms; the A operand's second plane is neither fetched nor read (2 products: hi*lo, hi*hi) and the
@@ -120,9 +114,6 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
     constexpr int ST = decltype(st_tag)::value;
     // a negative tap shift must stay in the VGPR offset (the range check has to see the row): one v_add per load, only for taps
     const int so = a_soff(c);
-#if SS_HABL == 1
-    if (c > 1) return;
-#endif
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
       if constexpr (W2) ra[ST][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (a_voff[i] + so) | dead | a_lo_dead, 0, 0);
@@ -200,11 +191,7 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
       for (int m = 0; m < TM; ++m)
 #pragma unroll
         for (int n = 0; n < TN; ++n) {
-#if SS_HABL == 2
-          asm volatile("" ::"v"(af[m]), "v"(bf[n]));
-#else
           acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], bf[n], acc[m][n], 0, 0, 0);
-#endif
         }
     }
     }
@@ -235,7 +222,7 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
     body(I1{}, c + 1);
   }
   // GATE: the conditioner addend (fp32, one HBM miss per element) is fetched under the last two chunks' MFMAs, into the registers the
-  // fetch stages no longer need; with the loads in the epilogue every workgroup of a round stalled on them (tools/ablate_h.sh: 56 of 276 us).
+  // fetch stages no longer need; with the loads in the epilogue every workgroup of a round stalled on them (timing ablation, DESIGN.md: 56 of 276 us).
   const int row_base = t0 + wm * 32 * TM + 4 * lh;
   const int col_base = n0 + wn * 32 * TN;
   [[maybe_unused]] float pe0[TM][TN / 2 > 0 ? TN / 2 : 1][16], pe1[TM][TN / 2 > 0 ? TN / 2 : 1][16];
@@ -254,13 +241,8 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ro = ((r & 3) + 8 * (r >> 2)) * lde4;
-#if SS_HABL == 3
-          pe0[m][n / 2][r] = (float)ro;
-          pe1[m][n / 2][r] = (float)eoff;
-#else
           pe0[m][n / 2][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_e, eoff + ro, 0, 0));
           pe1[m][n / 2][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_e, eoff + ro, 128, 0));
-#endif
         }
       }
     }
@@ -330,14 +312,9 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
           else g = act(acc[m][n][r] + b0 + pe0[m][n / 2][r], m0, s0, h0) * act(acc[m][n + 1][r] + b1 + pe1[m][n / 2][r], m1, s1, h1);
           if (row0 + rr >= row_lim) g = 0.f;
           const uint16_t gh = ss_f2t<W2>(g);
-#if SS_HABL == 4
-          if (g == 12345.678f)   // ablation build (tools/ablate_h.sh): no output stores
-#endif
-          {
-            __builtin_amdgcn_raw_buffer_store_b16(gh, rsrc_c, coff + rr * ldc2, 0, 0);   // rows >= T: out of range, dropped
-            // second term 32 elements further; fp16x2: the gate output is only ever a matrix-core A operand (hi term), its second term is not written
-            if constexpr (SPLIT == 1) __builtin_amdgcn_raw_buffer_store_b16(f2bf(g - bf2f(gh)), rsrc_c, coff + rr * ldc2, 64, 0);
-          }
+          __builtin_amdgcn_raw_buffer_store_b16(gh, rsrc_c, coff + rr * ldc2, 0, 0);   // rows >= T: out of range, dropped
+          // second term 32 elements further; fp16x2: the gate output is only ever a matrix-core A operand (hi term), its second term is not written
+          if constexpr (SPLIT == 1) __builtin_amdgcn_raw_buffer_store_b16(f2bf(g - bf2f(gh)), rsrc_c, coff + rr * ldc2, 64, 0);
         }
       }
     }
@@ -478,9 +455,6 @@ template <int EPI, int SPLIT>
 int launch_tiles_s(const ss_gemm_bf16_args& a, hipStream_t stream) {
   const int n_cols = (EPI == SS_HEPI_GATE) ? a.Np : a.N;
   const long big = (long)ss_cdiv(a.T, 128) * a.B * ss_cdiv(n_cols, 128);
-  const int env_tile = g_ss_tuning.htile;  // experiments: 64 / 128 force the row tile
-  if (env_tile == 64) return launch_h<64, 128, EPI, SPLIT>(a, stream);
-  if (env_tile == 128) return launch_h<128, 128, EPI, SPLIT>(a, stream);
   if (big >= 512) return launch_h<128, 128, EPI, SPLIT>(a, stream);
   return launch_h<64, 128, EPI, SPLIT>(a, stream);
 }

@@ -21,12 +21,6 @@
 typedef ss_f32x16 f32x16;
 typedef ss_bf16x8 bf16x8;
 
-// SS_G256_ABL (debug builds only; results wrong by design): 1 = no DMA inside the loop, 2 = no MFMAs, 3 = no barriers, 4 = no epilogue
-// loads/stores except one store per lane
-#ifndef SS_G256_ABL
-#define SS_G256_ABL 0
-#endif
-
 namespace {
 
 constexpr int BM = 256, BN = 256, BKH = 64;
@@ -344,10 +338,10 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
     // (no DMA is ever issued past the last step: the epilogue's addend quarters reuse this memory and must not race with zero fills)
     if constexpr (TAP == 2 && CC + 1 < CCS) wait_vmcnt<5>();   // the 5 pieces of A chunk cc+1, issued last step after its weight pieces
     else wait_vmcnt<0>();
-    if constexpr (SS_G256_ABL != 3) __builtin_amdgcn_s_barrier();
-    if constexpr (SS_G256_ABL != 1 && !LAST) dma_b(Bn, (S + 1) / 3, (S + 1) % 3, 0);
+    __builtin_amdgcn_s_barrier();
+    if constexpr (!LAST) dma_b(Bn, (S + 1) / 3, (S + 1) % 3, 0);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TAP == 1 && SS_G256_ABL != 1 && CC + 1 < CCS) dma_a(An, CC + 1, 0);
+    if constexpr (TAP == 1 && CC + 1 < CCS) dma_a(An, CC + 1, 0);
     if constexpr (LAST) {   // the first addend quarter flies under the last step (into A0 / B0, which that step does not read)
       __builtin_amdgcn_sched_barrier(0);
       dma_e(EQ0, 0);
@@ -375,10 +369,7 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
 #pragma unroll
       for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) {
-          if constexpr (SS_G256_ABL == 2) acc[m][n][0] += (float)af[ks & 1][m][0] * (float)bf[ks & 1][n][0];
-          else acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][m], bf[ks & 1][n], acc[m][n], 0, 0, 0);
-        }
+        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][m], bf[ks & 1][n], acc[m][n], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
     }

@@ -24,13 +24,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-// SS_G16_ABL (debug builds only, tools/ablate_g16.sh; results are wrong by design): 1 = no global fetches inside the loop, 2 = no LDS
-// stores, 3 = no MFMAs, 4 = no barriers in the loop, 5 = no conditioner-addend loads, 6 = no activations / exchange in the epilogue,
-// 7 = no weight fetches inside the loop, 8 = no raw-row fetches inside the loop
-#ifndef SS_G16_ABL
-#define SS_G16_ABL 0
-#endif
-
 namespace {
 
 constexpr int BK = 32;
@@ -57,11 +50,9 @@ __device__ __forceinline__ float2 vsub(const float2& a, const float2& b) { retur
 // WL = weight layout: false = the packed rows of ss_pack_conv_weight ([Np][6][Kp], shared with the 32x32x2 kernel); true = the
 // lane-contiguous repack of ss_pack_gate16_weights ([n tile][wave][K chunk][component][half][lane][4 floats]): one fetch instruction of
 // a wave is 1 KB contiguous (8 cache lines) instead of 16 columns x 64 B (16 lines).
-// The kernel body as a device function of (workgroup id, LDS base): the __global__ wrapper below passes blockIdx.x and its dynamic LDS; the
-// dataflow experiment of fused_gate_res.hip (round 5) calls the same body from a launch that also holds the residual projection's workgroups.
+// The kernel body as a device function of (workgroup id, LDS base): the __global__ wrapper below passes blockIdx.x and its dynamic LDS.
 // Returns false for the padding workgroups of the XCD-aligned grid (no tile).
-// ST_AUX: cache-policy bits of the output stores (0 in the product; 16 = sc1, write-through to memory: the publish form of the dataflow experiment)
-template <int MT, bool KS, bool WL, int ST_AUX = 0>
+template <int MT, bool KS, bool WL>
 __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, const float* __restrict__ W16, int q_tiles_per_item, int q_tiles, int n_tiles,
                                                    int log2d, unsigned long long* clock_probe, const int block_id, float* __restrict__ smem_) {
   constexpr int BQ = 16 * MT;
@@ -278,11 +269,6 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
   int ks_delta = 6 * SZC;
   auto mfma_half = [&](auto jtag, const float4 (&af)[MT], const float4& bf) {
     constexpr int J = decltype(jtag)::value;
-    if constexpr (SS_G16_ABL == 3) {
-#pragma unroll
-      for (int m = 0; m < MT; ++m) acc[J][m][0] += af[m].x * bf.x + af[m].w * bf.w;
-      return;
-    }
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[J][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m].x, bf.x, acc[J][m], 0, 0, 0);
 #pragma unroll
@@ -309,20 +295,20 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
     __builtin_amdgcn_sched_barrier(0);
     mfma_half(std::integral_constant<int, ORD[P]>{}, af0, bst[S][0]);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (decltype(stage_tag)::value && SS_G16_ABL != 2) {
+    if constexpr (decltype(stage_tag)::value) {
       if constexpr (KS) store_a(As + P * SZC, ptag);   // component of the same position, NEXT K chunk
       else store_a(As + (CUR ^ 1) * SZC, std::integral_constant<int, PN>{});
     }
     __builtin_amdgcn_sched_barrier(0);  // stores first, then the fetches into the SAME registers
-    if constexpr (decltype(fetch_b_tag)::value && SS_G16_ABL != 1 && SS_G16_ABL != 7)
+    if constexpr (decltype(fetch_b_tag)::value)
       load_b(std::integral_constant<int, (P + 2) % 3>{}, ORD[P2N], k + (P + 2) / 6);
-    if constexpr (decltype(fetch_rows_tag)::value && SS_G16_ABL != 1 && SS_G16_ABL != 8) load_rows((k + (KS ? 2 : 1)) * cs);
+    if constexpr (decltype(fetch_rows_tag)::value) load_rows((k + (KS ? 2 : 1)) * cs);
     __builtin_amdgcn_sched_barrier(0);
     mfma_half(std::integral_constant<int, ORD[P]>{}, af1, bst[S][1]);
     if constexpr (!KS) {
-      if constexpr (SS_G16_ABL != 4) __syncthreads();
+      __syncthreads();
     } else if constexpr (P == 5 && decltype(stage_tag)::value) {
-      if constexpr (SS_G16_ABL != 4) __syncthreads();
+      __syncthreads();
       // swap the halves: what was written becomes what is read
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
@@ -391,8 +377,7 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
       for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float4 v = SS_G16_ABL == 5 ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                           : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_t, lane_e * 16, tile_b + (m * 4 + r) * 1024, 0));
+          const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_t, lane_e * 16, tile_b + (m * 4 + r) * 1024, 0));
           pe[m][r][0] = v.x;
           pe[m][r][1] = v.y;
           pe[m][r][2] = v.z;
@@ -410,7 +395,7 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
         const int dr = r + 3 * (r & ~(d - 1));      // wave-uniform: frame of quad qm + r = tm + dr
 #pragma unroll
         for (int o = 0; o < 4; ++o)
-          pe[m][r][o] = SS_G16_ABL == 5 ? 0.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_e, e_base, (dr + o * d) * lde4, 0));
+          pe[m][r][o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_e, e_base, (dr + o * d) * lde4, 0));
       }
     }
   };
@@ -474,19 +459,15 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
         const float u2 = act(z2 + pe[m][r][2]);
         const float u3 = act(z3 + pe[m][r][3]);
         float g0, g1, g2, g3;
-        if constexpr (SS_G16_ABL == 6) {
-          g0 = z0 + pe[m][r][0]; g1 = z1 + pe[m][r][1]; g2 = z2 + pe[m][r][2]; g3 = z3 + pe[m][r][3];
-        } else {
-          g0 = u0 * partner(u0); g1 = u1 * partner(u1); g2 = u2 * partner(u2); g3 = u3 * partner(u3);
-        }
+        g0 = u0 * partner(u0); g1 = u1 * partner(u1); g2 = u2 * partner(u2); g3 = u3 * partner(u3);
         float ga = chi ? g2 : g0, gb = chi ? g3 : g1;
         if constexpr (!FAST) {
           const int ta = tm + dr + my_first;
           if (ta >= row_lim) ga = 0.f;
           if (ta + d >= row_lim) gb = 0.f;
         }
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ga), rsrc_c, c_base, dr * ldc4, ST_AUX);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gb), rsrc_c, c_base, (dr + d) * ldc4, ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ga), rsrc_c, c_base, dr * ldc4, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gb), rsrc_c, c_base, (dr + d) * ldc4, 0);
       }
     }
   };
@@ -531,8 +512,6 @@ int launch16(const ss_conv_gemm_args& a, const float* W16, int dilation, int log
 }
 
 }  // namespace
-
-#ifndef SS_FUSED_TU   // fused_gate_res.hip includes this file for the kernel bodies above only
 
 // Workgroups a tiling of `quads` rows launches, and the model used to pick one: a launch costs (work per wave tile) x (workgroup
 // layers per CU). MT = 0 in the return value means "the 32x32x2 kernel (wino43_gate.hip) is the better fit".
@@ -690,4 +669,3 @@ extern "C" int ss_gate16_tile_addend(const float* E, int lde, int64_t e_batch_st
   SS_CHECK_LAUNCH("ss_gate16_tile_addend");
   return SS_OK;
 }
-#endif  // SS_FUSED_TU

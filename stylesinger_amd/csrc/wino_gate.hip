@@ -15,7 +15,6 @@
 // through LDS.  Main-loop skeleton (LDS swizzle, buffer-resource fetch, MFMA-shadow scheduling) = conv_gemm_kernel.h.
 #include "common.h"
 #include "../../include/stylesinger_hip.h"
-#include <stdlib.h>
 #include <type_traits>
 // SS_TRACE (debug builds only, tools/wave_trace.py): every wave of wino_gate_kernel_v2<1> sums, over its K chunks, the shader-clock
 // time spent in each phase of a chunk and writes the sums at exit.
@@ -24,9 +23,6 @@ __device__ unsigned long long* g_wino_trace = nullptr;
 extern "C" int ss_debug_set_wino_trace(void* p) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wino_trace), &p, sizeof(p));
 }
-#endif
-#ifndef SS_ABL
-#define SS_ABL 0
 #endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -45,9 +41,8 @@ __device__ __forceinline__ int lds_slot(int row, int slot) { return row * LD + (
 // barrier: best for the mel net where 384 tiles still fill the chip).
 template <int TN>
 __global__ __launch_bounds__(256) void wino_gate_kernel(const ss_conv_gemm_args a, int p_tiles_per_item, int p_tiles,
-                                                        int n_tiles, int log2d, int prio_mode) {
+                                                        int n_tiles, int log2d) {
   constexpr int BN = 64 * TN;
-  ss_apply_wave_prio(prio_mode);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                  // [2][BP][LD]
   float* Bs = smem + 2 * BP * LD;    // [2][BN][LD]
@@ -376,9 +371,8 @@ __global__ __launch_bounds__(256) void wino_gate_kernel(const ss_conv_gemm_args 
 // version 1 otherwise.
 template <int TN>
 __global__ __launch_bounds__(256) void wino_gate_kernel_v2(const ss_conv_gemm_args a, int p_tiles_per_item, int p_tiles,
-                                                           int n_tiles, int log2d, int prio_mode, unsigned long long* clock_probe) {
+                                                           int n_tiles, int log2d, unsigned long long* clock_probe) {
   constexpr int BN = 64 * TN;
-  ss_apply_wave_prio(prio_mode);
   // ss_set_clock_probe: workgroup 0 reports how many shader cycles and 100 MHz ticks its first wave lived (-> sustained clock)
   const bool probing = clock_probe != nullptr && blockIdx.x == 0;
   unsigned long long probe_c0 = 0, probe_r0 = 0;
@@ -526,10 +520,6 @@ __global__ __launch_bounds__(256) void wino_gate_kernel_v2(const ss_conv_gemm_ar
     for (int n = 0; n < TN; ++n) bf.v[n] = *reinterpret_cast<const float4*>(Bc + b_row + n * 32 * LD + so);
   };
   auto mfma4 = [&](f32x16 (&c)[TN], const float4& af, const BF& bf) {
-#if SS_ABL == 3
-    asm volatile("" ::"v"(af.x), "v"(af.y), "v"(af.z), "v"(af.w), "v"(bf.v[0].x), "v"(bf.v[0].y), "v"(bf.v[0].z), "v"(bf.v[0].w));
-    return;
-#endif
 #pragma unroll
     for (int n = 0; n < TN; ++n) c[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.v[n].x, c[n], 0, 0, 0);
 #pragma unroll
@@ -545,7 +535,7 @@ __global__ __launch_bounds__(256) void wino_gate_kernel_v2(const ss_conv_gemm_ar
   // (component parameters `ld`, K byte offset `ci0b`, weight byte offset `cb`) is issued right behind them into the same
   // registers. A fetch therefore has two groups of this chunk + two of the next (>= 1024 MFMA cycles of this wave, ~3x that of
   // wall time with 3 waves per SIMD) before its data is needed, and stays in flight across the barrier. (Timing ablations,
-  // tools/ablate.sh: with the fetch issued at the top of the chunk that consumes it the loop waited ~10 us per launch for L2.)
+  // with the fetch issued at the top of the chunk that consumes it the loop waited ~10 us per launch for L2.)
   auto chunk = [&](auto cur_tag, auto store_tag, auto load_tag, f32x16 (&cacc)[TN], const Comp& st, const Comp& ld, int ci0b, int cb) {
     constexpr int CUR = decltype(cur_tag)::value;
     const float* Ac = As + CUR * BP * LD;
@@ -567,28 +557,19 @@ __global__ __launch_bounds__(256) void wino_gate_kernel_v2(const ss_conv_gemm_ar
     SS_CLK_VM(td);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (decltype(store_tag)::value) {
-#if SS_ABL != 2
       store_a(As + (CUR ^ 1) * BP * LD, st);
       store_b(Bs + (CUR ^ 1) * BN * LD);
-#else
-      const u32x4 s0 = ra[0][0] + ra[0][1] + ra[1][0] + ra[1][1] + rb[0] + rb[1];
-      asm volatile("" ::"v"(s0[0]), "v"(s0[1]), "v"(s0[2]), "v"(s0[3]), "v"(rpb.x));
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);  // stores first, then the fetch into the SAME registers (a second register set would cost a wave per SIMD)
     if constexpr (decltype(load_tag)::value) {
-#if SS_ABL != 1
       load_a(ld, ci0b);
       load_b(cb);
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
     mfma4(cacc, af0, bf0);
     mfma4(cacc, af1, bf1);
     SS_CLK(te);
-#if SS_ABL != 4
     __syncthreads();
-#endif
     SS_CLK(tf);
 #ifdef SS_TRACE
     tr_sum[0] += tb - ta; tr_sum[1] += tc - tb; tr_sum[2] += td - tc; tr_sum[3] += te - td; tr_sum[4] += tf - te; tr_sum[5] += 1;
@@ -808,37 +789,26 @@ extern "C" int ss_wino_gate(const ss_conv_gemm_args* args, int dilation, void* s
   // (752 / 376 blocks) TN=1 84.0 us; f0 pair (1152 / 576 blocks) TN=1 104.7 vs TN=2 112.0 us -> TN=1 while its grid is
   // at most two rounds; beyond that a makespan model picks (TN=2 wins once there are many rounds).
   int tn = a.tile == SS_TILE_64x128 ? 2 : a.tile == SS_TILE_64x64 ? 1 : 0;
-  const int env_tn = g_ss_tuning.wino_tn;  // experiments: force the tile of every auto launch
-  if (tn == 0 && (env_tn == 1 || env_tn == 2)) tn = env_tn;
   if (tn == 0) {
     const long b2 = (long)p_tiles * ss_cdiv(a.Np, 128), b1 = (long)p_tiles * (a.Np / 64);
     const double t2 = (double)ss_cdiv(b2, 256) * 2.0 / 0.92, t1 = (double)ss_cdiv(b1, 256) * 1.0 / 0.75;
     tn = ((a.Np % 128) == 0 && b1 > 2 * 768 && t2 <= t1) ? 2 : 1;
   }
-  // version 2 (VALU diet) needs whole 32-channel K chunks and an even chunk count; the "wino_v1" knob forces the first version (A/B)
-  const bool force_v1 = g_ss_tuning.wino_v1 != 0;
-  const bool v2 = !force_v1 && (a.Cin % BK) == 0 && a.Kp == a.Cin && ((a.Kp / BK) % 2) == 0;
+  // version 2 (VALU diet) needs whole 32-channel K chunks and an even chunk count
+  const bool v2 = (a.Cin % BK) == 0 && a.Kp == a.Cin && ((a.Kp / BK) % 2) == 0;
   if (tn == 2) {
     SS_CHECK_ARG((a.Np % 128) == 0, "ss_wino_gate: TN=2 needs Np multiple of 128");
     const int n_tiles = a.Np / 128;
     const int grid = ss_cdiv(p_tiles, 8) * 8 * n_tiles;
     const size_t lds = (size_t)2 * (BP + 128) * LD * sizeof(float);
-    if (v2) hipLaunchKernelGGL(wino_gate_kernel_v2<2>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d, g_ss_tuning.wave_prio, g_ss_tuning.clock_probe);
-    else hipLaunchKernelGGL(wino_gate_kernel<2>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d, g_ss_tuning.wave_prio);
+    if (v2) hipLaunchKernelGGL(wino_gate_kernel_v2<2>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d, g_ss_tuning.clock_probe);
+    else hipLaunchKernelGGL(wino_gate_kernel<2>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d);
   } else {
     const int n_tiles = a.Np / 64;
     const int grid = ss_cdiv(p_tiles, 8) * 8 * n_tiles;
-#ifdef SS_EXPERIMENT_KNOBS   // occupancy experiments of the ablation builds only (tools/ablate.sh)
-    static const size_t lds_pad = getenv("SS_WINO_LDS_PAD") ? (size_t)atoi(getenv("SS_WINO_LDS_PAD")) : 0;
-#else
-    const size_t lds_pad = 0;
-#endif
-    const size_t lds = (size_t)2 * (BP + 64) * LD * sizeof(float) + lds_pad;
-    if (lds_pad) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_gate_kernel_v2<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    if (v2) hipLaunchKernelGGL(wino_gate_kernel_v2<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d, g_ss_tuning.wave_prio, g_ss_tuning.clock_probe);
-    else hipLaunchKernelGGL(wino_gate_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d, g_ss_tuning.wave_prio);
+    const size_t lds = (size_t)2 * (BP + 64) * LD * sizeof(float);
+    if (v2) hipLaunchKernelGGL(wino_gate_kernel_v2<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d, g_ss_tuning.clock_probe);
+    else hipLaunchKernelGGL(wino_gate_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, p_tiles_per_item, p_tiles, n_tiles, log2d);
   }
   SS_CHECK_LAUNCH("ss_wino_gate");
   return SS_OK;

@@ -14,13 +14,13 @@ from stylesinger_amd import config, lib, spec, synth
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_loads_and_exports_header_symbols():
+def test_library_loads_at_abi_20_and_exports_header_symbols():
     l = lib.load()
     names = lib.declared_symbols()
     assert len(names) >= 30
     for n in names:
         assert hasattr(l, n), n
-    assert l.ss_abi_version() == lib.ABI_VERSION == 19
+    assert l.ss_abi_version() == lib.ABI_VERSION == 20
     assert l.ss_last_error() is not None
 
 
@@ -43,7 +43,7 @@ def test_argument_errors_are_reported_not_crashed():
     assert l.ss_vad_trim(None, 0, None, None, 0, 1, 1, 480, 8, 6, None, 0, None, None, None) != 0 and b"ss_vad_trim" in l.ss_last_error()
     assert l.ss_normalize_volume(None, None, None, 1, 1, -30.0, None) != 0
     assert l.ss_round_f16_rows(None, 0, 0, None, None, None, 0, 1, None) != 0
-    assert not hasattr(l, "ss_fused_gate_res")   # the dataflow-launch experiment is built from tools/experiments/, not shipped in the library
+    assert not hasattr(l, "ss_fused_gate_res")   # the dataflow-launch experiment of round 5 was never part of the library
     assert l.ss_set_tuning(b"q4_force", 1) == 0 and l.ss_get_tuning(b"q4_force") == 1 and l.ss_set_tuning(b"q4_force", 0) == 0
     assert l.ss_set_tuning(b"tile128", 1) != 0 and l.ss_set_tuning(b"skip_deep", 1) != 0      # removed in round 5
     # round-6 entry points
@@ -361,9 +361,25 @@ def test_forward_signature_equals_the_reference_operator_surface():
         assert f'ret["{ALIAS.get(k, k)}"]' in src or f"'{ALIAS.get(k, k)}'" in src, k
 
 
-def test_launch_planning_functions_of_the_library_run_without_a_gpu():
-    """The host-side launch planners of the C-ABI (no kernel launch): tiling picks, split-K slice count, size of the addend re-layout, the tuning
-    knob table. Without a device the CU count falls back to MI355X's 256, so the BASELINE shapes give their documented answers."""
+def test_tuning_knob_table_keeps_its_keys_and_refuses_the_removed_ones():
+    """ss_set_tuning / ss_get_tuning without a device: the surviving knobs round-trip, bad values and the keys removed with ABI 20 are refused."""
+    l = lib.load()
+    # knob table: every documented key round-trips, bad values are refused with a message
+    for key, val in ((b"gate16_ks", 0), (b"mel_tail", 0), (b"gate16", 3), (b"skip_dense", 0), (b"voc_wino_max_mb", 7), (b"layer512_tail", 2)):
+        before = l.ss_get_tuning(key)
+        assert before >= 0
+        assert l.ss_set_tuning(key, val) == 0 and l.ss_get_tuning(key) == val
+        assert l.ss_set_tuning(key, before) == 0
+    assert l.ss_set_tuning(b"gate16", 4) != 0 and b"gate16" in l.ss_last_error()
+    # A/B switches removed with ABI 20: refused, and unknown to ss_get_tuning
+    for key in (b"wave_prio", b"htile", b"wino_tn", b"wino_v1", b"res_tile", b"skip_tile", b"res16", b"skip16", b"e16"):
+        assert l.ss_set_tuning(key, 0) != 0 and l.ss_set_tuning(key, 1) != 0 and l.ss_get_tuning(key) < 0
+    assert l.ss_get_tuning(b"nope") < 0
+
+
+def test_launch_planners_of_the_library_run_without_a_gpu():
+    """The host-side launch planners of the C-ABI (no kernel launch): tiling picks, split-K slice count, size of the addend re-layout, the layer512
+    size rule. Without a device the CU count falls back to MI355X's 256, so the BASELINE shapes give their documented answers."""
     l = lib.load()
     # fp32 F(4,3) gate tiling (DESIGN 3.1e): C2 mel / f0 pair, one 4 s utterance (16-quad tiles), the C4 shape (32x32x2 kernel)
     assert l.ss_wino43_gate16_pick(8, 1500, 512, 2) == 2 and l.ss_wino43_gate16_pick(16, 1500, 384, 1) == 3
@@ -375,14 +391,6 @@ def test_launch_planning_functions_of_the_library_run_without_a_gpu():
     assert l.ss_gemm16_ksplit_pick(1, 750, 256, 5120) == 5 and l.ss_gemm16_ksplit_pick(8, 1500, 256, 5120) == 1 and l.ss_gemm16_ksplit_pick(1, 750, 256, 256) == 1
     # residual-projection row tile: 96 rows at C2 (16 row tiles per 8 s item), 32 rows for one short utterance
     assert l.ss_gemm16_pick(8, 1500, 256) == 6 and l.ss_gemm16_pick(1, 750, 256) == 2
-    # knob table: every documented key round-trips, bad values are refused with a message
-    for key, val in ((b"e16", 0), (b"mel_tail", 0), (b"gate16", 3), (b"htile", 128), (b"voc_wino_max_mb", 7), (b"wino_tn", 2)):
-        before = l.ss_get_tuning(key)
-        assert before >= 0
-        assert l.ss_set_tuning(key, val) == 0 and l.ss_get_tuning(key) == val
-        assert l.ss_set_tuning(key, before) == 0
-    assert l.ss_set_tuning(b"htile", 96) != 0 and b"htile" in l.ss_last_error()
-    assert l.ss_get_tuning(b"nope") < 0
     # round 6: the fused residual layer of the fp16x2 mel stack. Size rule = four rounds of 128-row tiles per CU (256 CUs without a device): the
     # BASELINE configs[3] shape qualifies (32 x 44 = 1408 tiles), C2's does not; the knob value 2 lifts the size rule (parity tests), never the shape rules
     assert l.ss_get_tuning(b"layer512") == 1 and l.ss_get_tuning(b"layer512_tail") == 1

@@ -49,15 +49,12 @@ def main():
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--T", type=int, default=1500)
     ap.add_argument("--e16", action="store_true", help="wino43_16: conditioner addend in the kernel's fetch order (ss_gate16_tile_addend)")
-    ap.add_argument("--prio", type=int, default=-1, help="ss_set_tuning('wave_prio', N)")
     ap.add_argument("--mt", default="-1,3,2", help="wino43_16: comma list of tilings (-1 = the 32x32x2 kernel, 0 = library pick, 2, 3)")
     ap.add_argument("--w16", type=int, default=1, help="wino43_16: 1 = weights in the kernel's fetch order (ss_wino43_gate16w), 0 = packed rows")
     ap.add_argument("--x3", action="store_true", help="wino43_16: the bf16x3 form (ss_wino43_gate16x: split operands on the bf16 matrix cores)")
     ap.add_argument("--pair", type=int, default=1, help="wino43_16: time the f0 launch with 2B items (both nets), as the loop launches it")
     ap.add_argument("--e-layout", default="row", help="conditioner addend: 'row' = [B][T][L*2C] (one row holds all layers), 'layer' = [L][B][T][2C]")
     a = ap.parse_args()
-    if a.prio >= 0:
-        L.check(L.load().ss_set_tuning(b"wave_prio", a.prio), "ss_set_tuning")
     if a.sweep:
         import subprocess
         for t in a.sweep.split(","):

@@ -13,11 +13,8 @@
 #   kbench-c4        the 16-bit many-round launches at the BASELINE config 4 shape: fp16x2 gate on gate256 / gate128, residual projection on
 #                    tile256 (tools/kbench_h.py)
 #   c4-streams       BASELINE config 4 with two batches in flight (measured in round 5: slower)
-#   fused            round 5: gate + residual projection of one layer as one dataflow launch vs two launches (DESIGN.md 7 lead 1)
 #   c4q / c3-emulated  the fp16q4 line of config 4 / configs[2]'s 8 shards emulated on one device
 #   pmc-gate128      PMC passes on gate128_kernel at the config-4 shape (profiles/r05_pmc_gate128.json)
-#   ablate-gate16    timing ablations of the 16x16-tile gate kernel (debug builds: tools/ablate_g16.sh build, in the container)
-#   ablate-res16     the same for the residual-projection kernel (tools/ablate_r16.sh build, in the container)
 #   kbench-layer512  round 6: ss_layer512 (one launch per residual layer of the fp16x2 mel stack) against the launch pair it replaces, C4 shape
 #   trace-layer512   per-phase shader-clock timing of layer512_kernel (builds the -DSS_L512_TRACE library first; hipcc works on the box)
 #   pmc-layer512 [--one --e16]  PMC passes on layer512_kernel (profiles/r06_pmc_layer512.json; with --one --e16 the fp16sd form: r06_pmc_layer512sd.json)
@@ -26,7 +23,6 @@
 #   phases-layer512  the layer launch with its half tiles first / last and as whole tiles (knob layer512_tail; profiles/r06_kbench_layer512_phase_shift.log)
 #   kbench-final     the mel output projection + DDPM update per tile choice, with / without the in-kernel noise (profiles/r06_kbench_final_projection.log)
 #   kbench-skip      the K = L C skip GEMM: pair layout, compact A, compact A + W (64-channel steps; SS_SKIP_DENSE=0: 32) (profiles/r06_kbench_skip_gemm_dense.log)
-#   groups-layer512  EXPERIMENT (own shared object): the fp16sd layer launch as two wave groups half a period apart (profiles/r06_kbench_layer512_groups.log)
 #   numerics-sd      CPU: the fp16sd numerics study (weight sets; --e-sets=N: the conditioner addend as N fp16 sets)
 #   power            rocm-smi power / sclk sampled under 12 s of back-to-back layer launches (1400 W = the cap)
 #   launch-floor     null-kernel hipGraph with the C2 mel loop's launch topology (tools/launch_floor.py)
@@ -68,12 +64,6 @@ case "$sec" in
     python tools/kbench_h.py --which gate --f16 --q4
     python tools/kbench_h.py --which res --f16 --pair-only
     python tools/kbench_h.py --which skip --f16 ;;
-  fused)
-    # round 5: one residual layer as ONE dataflow launch (gate + projection, per-row-tile counters; fences | write-through) vs the two launches, bit-identity
-    # checked. The experiment is not in the library: tools/kbench_fused.py builds tools/experiments/libfused_gate_res.so (hipcc) when it is missing / stale
-    python tools/kbench_fused.py
-    python tools/kbench_fused.py --B 32 --T 1500
-    python tools/kbench_fused.py --B 1 --T 750 ;;
   c4q)
     python bench.py --config c4q --streams 1 --steps 1 --warmup 1 --no-cpu-baseline --no-secondary | tail -1 | cut -c1-600 ;;
   c3-emulated)
@@ -81,10 +71,6 @@ case "$sec" in
   c4-streams)
     python bench.py --config c4 --streams 1 --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-roofline | tail -1 | cut -c1-400
     python bench.py --config c4 --streams 2 --steps 2 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline | tail -1 | cut -c1-400 ;;
-  ablate-gate16)
-    bash tools/ablate_g16.sh run ;;
-  ablate-res16)
-    bash tools/ablate_r16.sh run ;;
   kbench-layer512)
     python tools/kbench_layer512.py --iters 400
     python tools/kbench_layer512.py --iters 400 --one --which layer512
@@ -103,8 +89,6 @@ case "$sec" in
     python tools/kbench_h.py --f16 --which skip --compact 1 --iters 200
     python tools/kbench_h.py --f16 --which skip --compact 2 --iters 200
     SS_SKIP_DENSE=0 python tools/kbench_h.py --f16 --which skip --compact 2 --iters 200 ;;
-  groups-layer512)
-    python tools/kbench_layer512_groups.py "$@" ;;
   numerics-sd)
     python -m oracle.dither_numerics 1 2 4 8 16 32
     python -m oracle.dither_numerics 32 --e-sets=1 --e-sets=4 --e-sets=8 --e-sets=16 ;;

@@ -12,7 +12,7 @@
 // The MFMA count (12 288 + 4 096 per workgroup), the bytes each workgroup pulls (3.1 MB + 0.26 MB of weights, 64 KB of raw rows with halo x 6/4,
 // 128 KB of addend, 64 KB x in / out, 64 KB G out) and the LDS traffic are those of the real thing; what is missing can only make the real
 // kernel slower. Printed: time per launch for 188 workgroups (BASELINE configs[1]: 12 000 frames) and for 376 / 752 (many rounds), to be read
-// against the two-launch form's 65-68 us per layer at C2 (tools/kbench_fused.py prints it in the same session).
+// against the two-launch form's 65-68 us per layer at C2 (measured by the dataflow experiment's driver, since removed: DESIGN.md 7 lead 1).
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench/rowowner_skeleton.hip -o /tmp/rowowner && /tmp/rowowner
 #include <hip/hip_runtime.h>
 #include <cstdio>
