@@ -17,6 +17,135 @@
 
 namespace {
 
+inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+inline int round_up32(int x) { return (x + 31) / 32 * 32; }
+constexpr int MTR = 2;   // frames per workgroup of mel_tail_kernel
+
+// The form the residual stack takes for one (net, B, T) under the tuning knobs. resolve_form() fills it ONCE per sampler call and is the only
+// code that reads the mode fields, the optional weight pointers and the knobs; ws_layout() adds up the buffers of the form, the stack
+// functions launch it.
+enum StackKind {
+  STACK_FP32,     // fp32 activations in HBM on the fp32-MFMA kernels (direct / F(2,3) / F(4,3) gates; "bf16" without the 16-bit packs rounds in-kernel; "bf16x3")
+  STACK_PAIR16,   // 16-bit activations in HBM: a gate and a residual-projection launch per layer on ss_gemm_bf16
+  STACK_FUSED16,  // fp16 terms, ONE ss_layer512 launch per layer (gate + residual projection, G kept in LDS)
+};
+enum GateEntry { GATE_CONV, GATE_WINO23, GATE_WINO43, GATE_WINO43_16, GATE_WINO43_16W, GATE_WINO43_16X };
+enum ProjEntry { PROJ_CONV, PROJ_RES16, PROJ_RES16W };
+enum SkipEntry { SKIP_CONV, SKIP_STORE16, SKIP_SPLITK, SKIP_X3 };
+struct LayerForm {
+  int d;               // dilation
+  GateEntry gate;      // STACK_FP32: the gate's entry point ...
+  int mt;              // ... its row tiling (the 16x16x4 entry points; 0 = picked per launch) ...
+  int64_t e16_floats;  // ... and, > 0, GATE_WINO43_16W reads its conditioner addend from a slab of this many floats laid out for exactly that tiling
+  ProjEntry proj;      // STACK_FP32: the output projection's entry point
+  bool q4_gate;        // STACK_PAIR16, "fp16q4": the gate tries ss_gemm_bf16_gate128q first
+};
+struct StackForm {
+  StackKind kind;
+  int conv_bf16;     // ss_conv_gemm_args.mfma_bf16 of the STACK_FP32 launches
+  int outer_bf16;    // ... of the conditioner and skip projections: exact fp32 in the split modes (a fixed rounding error of E would enter every step)
+  bool cond16;       // the conditioner is rounded once to bf16 and E comes from ss_gemm_bf16
+  bool skip_folded;  // the K = L*C skip GEMM + ReLU is the stack's output (its weights carry skip_projection / sqrt(L)): no skip_projection launch
+  bool mel_tail;     // small launches: the mel sampler runs output projection + DDPM update + next input projection as one launch (mel_tail_kernel)
+  // STACK_FP32
+  bool defer;        // deferred skip: the output projections run their residual half only, the skip sum is one GEMM at the end of the stack
+  SkipEntry skip;    // that GEMM's entry point, row tile 16 * mt16 (0 = picked per launch) and K slices (1 = do not split)
+  int mt16, ksplit;
+  bool partials_ok;  // SKIP_SPLITK may leave its slices to the caller's tail kernel (ss_gemm16_store_partials) instead of reducing them
+  // 16-bit kinds. split (ss_gemm_bf16_args.split): 0 = bf16 operands; 1 = "bf16x2", every operand a (hi, mid) bf16 pair, pairs interleaved by 32
+  // channels (one 128-byte line = 32 channels of both planes; rows of Yh / GAh / the weights are twice as long), the matrix cores run
+  // hi*hi + hi*mid + mid*hi; 2 = "fp16x2", the same layouts with fp16 terms, weights-only split (two products), accumulators scaled by
+  // net->mfma_out_scale
+  int split, planes;   // planes per 16-bit row
+  int gplanes;         // ... per row of GAh: 1 when g_compact
+  bool g_compact;      // STACK_FUSED16 whose skip GEMM runs on the many-round kernel: GAh rows hold the L*C hi terms only (no dead second plane)
+  bool one_product;    // "fp16sd": one weight term
+  bool skip_w_compact; // ... and the skip GEMM reads the one-term sets without their zero plane (w_skipall_c: L2-resident)
+  bool q4_skip;        // "fp16q4": the skip GEMM tries ss_gemm_bf16_tile256q first
+  // "fp16sd": network evaluation j of a sampling loop (0 for its first one, in an order that does not depend on how a loop is cut into calls)
+  // reads weight set j % n_wsets (set * ws_* stride on every 16-bit weight pointer) and addend set j % n_esets (0 = one fp32 addend slab).
+  // Launch parameters only: a captured hipGraph replays the same sequence.
+  int n_wsets, n_esets;
+  LayerForm layer[SS_MAX_LAYERS];
+};
+
+StackForm resolve_form(const ss_wavenet* net, int B, int T) {
+  StackForm f;
+  memset(&f, 0, sizeof(f));
+  const SsTuning& knob = g_ss_tuning;
+  const int C = net->C, L = net->L, nl = L < SS_MAX_LAYERS ? L : SS_MAX_LAYERS;
+  f.split = net->mfma_split == 0 ? 0 : net->mfma_split == 2 ? 2 : 1;
+  f.planes = f.split ? 2 : 1;
+  const bool h16 = net->mfma_bf16 && net->w_dil_h[0] && net->w_skipall_h && (net->w_cond_h || f.split);
+  f.kind = h16 ? STACK_PAIR16 : STACK_FP32;
+  f.conv_bf16 = net->mfma_bf16;
+  f.outer_bf16 = f.split ? 0 : net->mfma_bf16;
+  f.cond16 = h16 && !f.split;
+  f.defer = !h16 && net->w_skipall;
+  f.skip_folded = net->skipall_folded && (h16 || f.defer);
+  f.mel_tail = knob.mel_tail != 0 && !net->mfma_bf16 && (int64_t)B * T <= 8L * ss_n_cu() && (C % 4) == 0 && (net->in_dim % 4) == 0 &&
+               (size_t)(MTR * C + MTR * round_up32(net->in_dim)) * 4 <= 48 * 1024;
+  f.one_product = net->mfma_products == 1;
+  f.n_wsets = net->n_wsets > 1 ? net->n_wsets : 1;
+  f.q4_skip = f.split == 2 && net->w_skipall_q && net->q_scale_z > 0.f;
+  // the fp16x2 stack as ONE ss_layer512 launch per layer (knob "layer512"): the net carries the fragment-order packs of every layer, one weight
+  // group, C = 256, dilations <= 8, and the launch fills the chip (ss_layer512_ok). Not "fp16q4": its gate runs the second product on the fp4
+  // instruction (gate128q), two launches per layer
+  if (h16 && knob.layer512 && f.split == 2 && net->n_groups <= 1 && C == 256 && !(net->w_dil_q[0] && net->q_scale_gate > 0.f)) {
+    bool packs = true;
+    for (int l = 0; l < nl; ++l) packs = packs && net->w_dil_f[l] && (l + 1 == L || net->w_out_f[l]);
+    const int dmax = 1 << ((L < net->dil_cycle ? L : net->dil_cycle) - 1);
+    if (packs && ss_layer512_ok(B, T, C, dmax, L * C * 2)) f.kind = STACK_FUSED16;
+  }
+  if (f.kind == STACK_FUSED16) {
+    // the skip GEMM's many-round kernel reads a compact operand (ss_gemm_bf16_args.a_compact). Its size rule, >= 2 rounds of 256-row tiles, belongs
+    // to gemm_bf16_tile256.hip; it is restated here because the layout of GAh is fixed before any launch
+    f.g_compact = knob.gate256 != 0 && (long)ss_cdiv(T, 256) * B >= 2L * ss_n_cu() && ((L * C) % 64) == 0 && C <= 256;
+    f.skip_w_compact = f.g_compact && f.one_product && net->w_skipall_c && net->n_groups <= 1;
+    if (f.one_product && net->n_esets > 0) f.n_esets = net->n_esets;   // the addend as fp16 sets (half the bytes per launch; ss_layer512_tile_addend_f16)
+  }
+  f.gplanes = f.g_compact ? 1 : f.planes;
+  f.ksplit = 1;
+  if (f.defer) {
+    const bool x3 = net->mfma_x3 && net->w_skipall_x3;   // opt-in bf16x3 mode: split operands on the bf16 matrix cores (gemm16x.hip)
+    if (!net->mfma_bf16 && (C & 3) == 0) f.ksplit = ss_gemm16_ksplit_pick(B, T, C, L * C);   // one short utterance: split K over the idle CUs
+    // long-K launch: when 64-row tiles also fit one round at three workgroups per CU they beat the 96-row pick (mel at C2: 240.7 vs 250.7 us)
+    f.mt16 = (long)((T + 63) / 64) * B * ((C + 63) / 64) <= 3L * ss_n_cu() && !x3 ? 4 : 0;
+    // fp32 operands: 16x16x4 tiles, both operands by LDS-DMA (gemm16.hip)
+    f.skip = net->mfma_bf16 ? SKIP_CONV : f.skip_folded && x3 ? SKIP_X3 : f.ksplit > 1 ? SKIP_SPLITK : SKIP_STORE16;
+    f.partials_ok = f.skip == SKIP_SPLITK && f.skip_folded;
+  }
+  const int g16 = knob.gate16;  // 0: 32x32x2 tiles; 1: per-launch pick; 2 / 3: 16x16x4 tiles of 16*MT quads
+  for (int l = 0; l < nl; ++l) {
+    LayerForm& y = f.layer[l];
+    y.d = 1 << (l % net->dil_cycle);
+    if (h16) {   // every other launch of "fp16q4" is fp16x2's
+      y.q4_gate = f.split == 2 && net->w_dil_q[l] && net->q_scale_gate > 0.f;
+      continue;
+    }
+    // deferred skip at C = 192 | 256: 16x16x4 tiles, balanced single round (gemm16.hip), weights in the kernel's fetch order when the net has them
+    if (f.defer && !net->mfma_bf16 && (C == 192 || C == 256)) y.proj = net->w_out16[l] ? PROJ_RES16W : PROJ_RES16;
+    if (!net->w_dil_wino[l] || net->mfma_bf16) continue;   // GATE_CONV
+    if (net->wino_m != 4) y.gate = GATE_WINO23;            // pairs of frames (t, t+d) from 4 products instead of 6
+    else if (net->mfma_x3 && net->w_dil_x3[l]) y.gate = GATE_WINO43_16X;   // opt-in "bf16x3" mode: split operands on the bf16 matrix cores
+    else if (g16 == 0) y.gate = GATE_WINO43;
+    else {
+      y.gate = net->w_dil_wino16[l] ? GATE_WINO43_16W : GATE_WINO43_16;
+      y.mt = g16 == 1 ? 0 : g16;
+      if (!net->w_dil_wino16[l] || net->mfma_x3) continue;
+      // the layer's slab of E is re-laid once per forward in the kernel's fetch order (ss_gate16_tile_addend), so that a wave's addend fetch is
+      // 1 KB contiguous per instruction instead of 8 lines x 32 B; for that the tiling is fixed here
+      int mt = g16 == 1 ? ss_wino43_gate16_pick(B, T, 2 * C, y.d) : g16;
+      if (mt == 1 && !(knob.gate16_ks != 0 && C >= 64)) mt = 2;   // wino43_gate16.hip's rule, as ss_wino43_gate16 resolves it: MT = 1 is K-staged only
+      const int64_t fl = mt > 0 ? ss_gate16_tiled_floats(B, T, 2 * C, y.d, mt) : -1;
+      if (fl <= 0 || fl * 4 >= (1ll << 31)) continue;
+      y.mt = mt;
+      y.e16_floats = fl;
+    }
+  }
+  return f;
+}
+
 struct WsLayout {
   float* E;   // [B*T][L*2C]
   float* X;   // [B*T][C]
@@ -25,54 +154,24 @@ struct WsLayout {
   float* O;   // [B*T][4]   (f0 net output)
   float* GA;  // [B*T][L*C] gate outputs of ALL layers (deferred-skip mode only, else null)
   float* E16[SS_MAX_LAYERS];  // per layer: the conditioner addend in the 16x16x4 gate kernel's fetch order (null: the layer reads E)
-  int mt16[SS_MAX_LAYERS];    // ... and the tiling it was laid out for (0 = none)
   float* KP;  // [ksplit][B*T][C] partial sums of the split-K skip GEMM (small launches only, else null)
-  int ksplit; // K slices of the skip GEMM for this (B, T): ss_gemm16_ksplit_pick
-  // bf16-in-HBM mode (net->w_dil_h set): the hidden activations travel as bf16
+  // 16-bit kinds: the hidden activations travel as 16-bit rows
   uint16_t* Yh;     // [B*T][C]        x + dstep of the next layer (the dilated conv's operand)
   uint16_t* GAh;    // [B*T][L*C]      gate outputs of all layers
   uint16_t* condh;  // [B*T][cond_dim] conditioner
-  // fused-layer form of the fp16x2 stack (ss_layer512, one launch per layer): the stream as hi rows (double buffered) + pairs in accumulator
-  // order, and every layer's addend slab in the kernel's accumulator order; null when the stack runs as gate + projection launches
+  // STACK_FUSED16: the stream as hi rows (double buffered) + pairs in accumulator order, and every layer's addend slab in the kernel's accumulator order
   uint16_t* H512[2];  // ss_layer512_h_elems: slot-major tiles
   void* P512;         // ss_layer512_stream_bytes
   float* E512;        // [L][ss_layer512_addend_floats]
   int64_t e512_layer; // floats per layer
-  uint16_t* E512h;    // fp16sd with ss_wavenet.n_esets > 0: [set][L][ss_layer512_addend_halfs] instead of E512
+  uint16_t* E512h;    // StackForm.n_esets > 0: [set][L][ss_layer512_addend_halfs] instead of E512
   int64_t e512h_layer, e512h_set;
-  bool g_compact;     // fused form whose skip GEMM runs on the many-round kernel: GAh rows hold the L*C hi terms only (no dead second plane)
   int64_t bytes;
 };
 
-// hmode: the hidden activations travel as bf16 in HBM. split (net->mfma_split, "bf16x2" precision): every bf16 operand is a (hi, mid) pair,
-// pairs interleaved by 32 channels (one 128-byte line = 32 channels of both planes; rows of Yh / GAh / the weights are twice as long) - and
-// the matrix cores run hi*hi + hi*mid + mid*hi (ss_gemm_bf16_args.split); the hoisted conditioner projection then runs in exact fp32 (it is
-// outside the step loop). mfma_split = 2 ("fp16x2"): the same layouts with fp16 terms, weights-only split (two products), accumulators scaled
-// by net->mfma_out_scale (ss_gemm_bf16_args.split = 2).
-inline bool smode(const ss_wavenet* net) { return net->mfma_split != 0; }
-inline bool hmode(const ss_wavenet* net) { return net->mfma_bf16 && net->w_dil_h[0] && net->w_skipall_h && (net->w_cond_h || smode(net)); }
-
-inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
-// "fp16sd": which of the net's noise-shaped weight sets the CURRENT network evaluation uses. The samplers set the evaluation index before every
-// evaluation (0 for the first one of a loop, in an order that does not depend on how a loop is cut into calls); the stack adds set * stride to
-// every 16-bit weight pointer. Launch parameters only: a captured hipGraph replays the same sequence.
-thread_local int g_wset_eval = 0;
-inline int64_t wset_off(const ss_wavenet* net, int64_t stride) { return net->n_wsets > 1 ? (int64_t)(g_wset_eval % net->n_wsets) * stride : 0; }
-
-// the fp16x2 mel stack as ONE ss_layer512 launch per layer: the net carries the fragment-order packs of every layer, one weight group, C = 256,
-// dilations <= 8, and the launch fills the chip (ss_layer512_ok); knob "layer512"
-inline bool fused512(const ss_wavenet* net, int B, int T) {
-  if (!g_ss_tuning.layer512 || net->mfma_split != 2 || !hmode(net) || net->n_groups > 1 || net->C != 256 || !net->w_skipall_h) return false;
-  if (net->w_dil_q[0] && net->q_scale_gate > 0.f) return false;   // "fp16q4": its gate runs the second product on the fp4 instruction (gate128q), two launches per layer
-  for (int l = 0; l < net->L; ++l)
-    if (!net->w_dil_f[l] || (l + 1 < net->L && !net->w_out_f[l])) return false;
-  const int dmax = 1 << ((net->L < net->dil_cycle ? net->L : net->dil_cycle) - 1);
-  return ss_layer512_ok(B, T, net->C, dmax, net->L * net->C * 2) != 0;
-}
-
-WsLayout ws_layout(const ss_wavenet* net, int B, int T, void* base) {
+WsLayout ws_layout(const ss_wavenet* net, const StackForm& f, int B, int T, void* base) {
   WsLayout w;
+  memset(&w, 0, sizeof(w));
   const int64_t rows = (int64_t)B * T;
   int64_t off = 0;
   char* p = (char*)base;
@@ -86,47 +185,23 @@ WsLayout ws_layout(const ss_wavenet* net, int B, int T, void* base) {
   w.G = take(rows * net->C);
   w.S = take(rows * net->C);
   w.O = take(rows * 4);
-  const bool h = hmode(net);
-  w.GA = (net->w_skipall && !h) ? take(rows * net->L * net->C) : nullptr;
-  // fp32 F(4,3) loops on the 16x16x4 gate kernel: every layer's slab of E is re-laid once per forward in that kernel's fetch order
-  // (ss_gate16_tile_addend), so that a wave's addend fetch is 1 KB contiguous per instruction instead of 8 lines x 32 B
-  for (int l = 0; l < SS_MAX_LAYERS; ++l) {
-    w.E16[l] = nullptr;
-    w.mt16[l] = 0;
+  if (f.defer) w.GA = take(rows * net->L * net->C);
+  for (int l = 0; l < net->L && l < SS_MAX_LAYERS; ++l)
+    if (f.layer[l].e16_floats) w.E16[l] = take(f.layer[l].e16_floats);
+  if (f.ksplit > 1) w.KP = take((int64_t)f.ksplit * rows * net->C);
+  if (f.kind != STACK_FP32) {
+    w.Yh = (uint16_t*)take((rows * net->C * f.planes + 1) / 2);
+    w.GAh = (uint16_t*)take((rows * net->L * net->C * f.gplanes + 1) / 2);
+    if (f.cond16) w.condh = (uint16_t*)take((rows * net->cond_dim + 1) / 2);
   }
-  if (!h && !net->mfma_bf16 && !net->mfma_x3 && net->wino_m == 4 && g_ss_tuning.gate16 != 0)
-    for (int l = 0; l < net->L && l < SS_MAX_LAYERS; ++l) {
-      if (!net->w_dil_wino[l] || !net->w_dil_wino16[l]) continue;
-      const int d = 1 << (l % net->dil_cycle);
-      int mt = g_ss_tuning.gate16 == 1 ? ss_wino43_gate16_pick(B, T, 2 * net->C, d) : g_ss_tuning.gate16;
-      if (mt == 1 && !(g_ss_tuning.gate16_ks != 0 && net->C >= 64)) mt = 2;   // as ss_wino43_gate16 resolves it (MT = 1 is K-staged only)
-      const int64_t fl = mt > 0 ? ss_gate16_tiled_floats(B, T, 2 * net->C, d, mt) : -1;
-      if (fl <= 0 || fl * 4 >= (1ll << 31)) continue;
-      w.E16[l] = take(fl);
-      w.mt16[l] = mt;
-    }
-  w.ksplit = (net->w_skipall && !h && !net->mfma_bf16 && (net->C & 3) == 0) ? ss_gemm16_ksplit_pick(B, T, net->C, net->L * net->C) : 1;
-  w.KP = w.ksplit > 1 ? take((int64_t)w.ksplit * rows * net->C) : nullptr;
-  const int planes = smode(net) ? 2 : 1;
-  w.Yh = h ? (uint16_t*)take((rows * net->C * planes + 1) / 2) : nullptr;
-  // the skip GEMM's many-round kernel reads a compact operand (ss_gemm_bf16_args.a_compact; its size rule: >= 2 rounds of 256-row tiles)
-  w.g_compact = fused512(net, B, T) && g_ss_tuning.gate256 != 0 && (long)ss_cdiv(T, 256) * B >= 2L * ss_n_cu() && ((net->L * net->C) % 64) == 0 && net->C <= 256;
-  w.GAh = h ? (uint16_t*)take((rows * net->L * net->C * (w.g_compact ? 1 : planes) + 1) / 2) : nullptr;
-  w.condh = (h && !smode(net)) ? (uint16_t*)take((rows * net->cond_dim + 1) / 2) : nullptr;
-  w.H512[0] = w.H512[1] = nullptr;
-  w.P512 = nullptr;
-  w.E512 = nullptr;
-  w.e512_layer = 0;
-  w.E512h = nullptr;
-  w.e512h_layer = w.e512h_set = 0;
-  if (fused512(net, B, T)) {
+  if (f.kind == STACK_FUSED16) {
     w.H512[0] = (uint16_t*)take((ss_layer512_h_elems(B, T) + 1) / 2);
     w.H512[1] = (uint16_t*)take((ss_layer512_h_elems(B, T) + 1) / 2);
     w.P512 = take(ss_layer512_stream_bytes(B, T) / 4);
-    if (net->mfma_products == 1 && net->n_esets > 0) {   // the addend as n_esets fp16 sets (half the bytes per launch; ss_layer512_tile_addend_f16)
+    if (f.n_esets) {
       w.e512h_layer = ss_layer512_addend_halfs(B, T);
       w.e512h_set = w.e512h_layer * net->L;
-      w.E512h = (uint16_t*)take((w.e512h_set * net->n_esets + 1) / 2);
+      w.E512h = (uint16_t*)take((w.e512h_set * f.n_esets + 1) / 2);
     } else {
       w.e512_layer = ss_layer512_addend_floats(B, T);
       w.E512 = take(w.e512_layer * net->L);
@@ -136,46 +211,64 @@ WsLayout ws_layout(const ss_wavenet* net, int B, int T, void* base) {
   return w;
 }
 
-inline ss_conv_gemm_args base_args(int B, int T, const int32_t* lens) {
-  ss_conv_gemm_args a;
+// what a launch of either argument struct starts from
+template <class Args> inline Args zeroed_args(int B, int T, const int32_t* lens) {
+  Args a;
   memset(&a, 0, sizeof(a));
   a.B = B;
   a.T = T;
   a.lens = lens;
   a.ntaps = 1;
+  a.post_scale = 1.0f;
+  a.mask_rows = 1;
+  return a;
+}
+inline ss_conv_gemm_args base_args(int B, int T, const int32_t* lens) {
+  ss_conv_gemm_args a = zeroed_args<ss_conv_gemm_args>(B, T, lens);
   a.a_scale = 1.0f;
   a.a_lrelu = 1.0f;
   a.pre_scale = 1.0f;
-  a.post_scale = 1.0f;
-  a.mask_rows = 1;
   return a;
 }
-
-inline int round_up32(int x) { return (x + 31) / 32 * 32; }
-
-// E = cond . Wc^T + (bc + b_dil)  for all layers at once
 inline ss_gemm_bf16_args base_args_h(const ss_wavenet* net, int B, int T, const int32_t* lens) {
-  ss_gemm_bf16_args a;
-  memset(&a, 0, sizeof(a));
-  a.B = B;
-  a.T = T;
-  a.lens = lens;
-  a.ntaps = 1;
-  a.post_scale = 1.0f;
-  a.mask_rows = 1;
+  ss_gemm_bf16_args a = zeroed_args<ss_gemm_bf16_args>(B, T, lens);
   if (net->n_groups > 1) a.group_size = B / net->n_groups;
   return a;
 }
+// the A operand / the output of a launch (either argument struct) as [B][T][ld] rows
+template <class Args, class P> inline void set_a(Args& a, P* p, int ld, int T) {
+  a.A = p;
+  a.lda = ld;
+  a.a_batch_stride = (int64_t)T * ld;
+}
+template <class Args, class P> inline void set_c(Args& a, P* p, int ld, int T) {
+  a.C = p;
+  a.ldc = ld;
+  a.c_batch_stride = (int64_t)T * ld;
+}
+// the three taps of a k = 3 conv of dilation d
+template <class Args> inline void set_taps3(Args& a, int d) {
+  a.ntaps = 3;
+  a.tap_off[0] = -d;
+  a.tap_off[1] = 0;
+  a.tap_off[2] = d;
+}
+// paired nets: item b runs net b / group_size, whose weights / bias / A-operand bias live gs_* floats further
+inline void set_groups(ss_conv_gemm_args& a, const ss_wavenet* net, int B, int64_t gs_w, int64_t gs_bias, int64_t gs_a_bias = 0) {
+  if (net->n_groups <= 1) return;
+  a.group_size = B / net->n_groups;
+  a.w_group_stride = gs_w;
+  a.bias_group_stride = gs_bias;
+  a.a_bias_group_stride = gs_a_bias;
+}
 
-int precompute_cond(const ss_wavenet* net, const float* cond, const int32_t* lens, int B, int T, const WsLayout& w,
-                    hipStream_t stream) {
+// E = cond . Wc^T + (bc + b_dil)  for all layers at once
+int precompute_cond(const ss_wavenet* net, const StackForm& sf, const float* cond, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
   const int NE = net->L * 2 * net->C;
-  if (hmode(net) && !smode(net)) {  // cond rounded once to bf16, then E = cond . Wc^T + (bc + b_dil) on the bf16 kernel (fp32 out)
+  if (sf.cond16) {  // cond rounded once to bf16, then E = cond . Wc^T + (bc + b_dil) on the bf16 kernel (fp32 out)
     SS_PROPAGATE(ss_to_bf16(cond, nullptr, w.condh, B, T, net->cond_dim, net->cond_dim, net->cond_dim, nullptr, 0, 0, stream));
     ss_gemm_bf16_args h = base_args_h(net, B, T, lens);
-    h.A = w.condh;
-    h.lda = net->cond_dim;
-    h.a_batch_stride = (int64_t)T * net->cond_dim;
+    set_a(h, w.condh, net->cond_dim, T);
     h.K = net->cond_dim;
     h.W = net->w_cond_h;
     h.w_group_stride = net->gs_w_cond_h;
@@ -184,16 +277,12 @@ int precompute_cond(const ss_wavenet* net, const float* cond, const int32_t* len
     h.epi = SS_HEPI_STORE;
     h.bias = net->b_cond;
     h.bias_group_stride = net->gs_b_cond;
-    h.C = w.E;
-    h.ldc = NE;
-    h.c_batch_stride = (int64_t)T * NE;
+    set_c(h, w.E, NE, T);
     h.mask_rows = 0;
     return ss_gemm_bf16(&h, stream);
   }
   ss_conv_gemm_args a = base_args(B, T, lens);
-  a.A = cond;
-  a.lda = net->cond_dim;
-  a.a_batch_stride = (int64_t)T * net->cond_dim;
+  set_a(a, cond, net->cond_dim, T);
   a.Cin = net->cond_dim;
   a.W = net->w_cond;
   a.N = NE;
@@ -201,125 +290,215 @@ int precompute_cond(const ss_wavenet* net, const float* cond, const int32_t* len
   a.Kp = round_up32(net->cond_dim);
   a.epi = SS_EPI_STORE;
   a.bias = net->b_cond;
-  a.C = w.E;
-  a.ldc = NE;
-  a.c_batch_stride = (int64_t)T * NE;
+  set_c(a, w.E, NE, T);
   a.mask_rows = 0;
-  a.mfma_bf16 = smode(net) ? 0 : net->mfma_bf16;   // split mode: exact fp32 (a fixed rounding error of E would enter every step)
-  if (net->n_groups > 1) {
-    a.group_size = B / net->n_groups;
-    a.w_group_stride = net->gs_w_cond;
-    a.bias_group_stride = net->gs_b_cond;
-  }
+  a.mfma_bf16 = sf.outer_bf16;
+  set_groups(a, net, B, net->gs_w_cond, net->gs_b_cond);
   SS_PROPAGATE(ss_conv_gemm(&a, stream));
-  if (w.E512)   // fused-layer form: every layer's 512 addend columns in ss_layer512's accumulator order
-    for (int l = 0; l < net->L; ++l)
-      SS_PROPAGATE(ss_layer512_tile_addend(w.E + (int64_t)l * 2 * net->C, NE, (int64_t)T * NE, w.E512 + (int64_t)l * w.e512_layer, B, T, stream));
-  if (w.E512h)  // ... as n_esets fp16 sigma-delta sets (fp16sd)
-    for (int l = 0; l < net->L; ++l)
-      SS_PROPAGATE(ss_layer512_tile_addend_f16(w.E + (int64_t)l * 2 * net->C, NE, (int64_t)T * NE, w.E512h + (int64_t)l * w.e512h_layer, net->n_esets, w.e512h_set, B, T,
-                                               stream));
-  for (int l = 0; l < net->L; ++l)
+  for (int l = 0; l < net->L; ++l) {   // the layer's addend columns again, in the order its kernel fetches them
+    const float* El = w.E + (int64_t)l * 2 * net->C;
+    if (w.E512)   // ss_layer512's accumulator order
+      SS_PROPAGATE(ss_layer512_tile_addend(El, NE, (int64_t)T * NE, w.E512 + (int64_t)l * w.e512_layer, B, T, stream));
+    if (w.E512h)  // ... as n_esets fp16 sigma-delta sets (fp16sd)
+      SS_PROPAGATE(ss_layer512_tile_addend_f16(El, NE, (int64_t)T * NE, w.E512h + (int64_t)l * w.e512h_layer, sf.n_esets, w.e512h_set, B, T, stream));
     if (w.E16[l])
-      SS_PROPAGATE(ss_gate16_tile_addend(w.E + (int64_t)l * 2 * net->C, NE, (int64_t)T * NE, w.E16[l], B, T, 2 * net->C, 1 << (l % net->dil_cycle),
-                                         w.mt16[l], stream));
+      SS_PROPAGATE(ss_gate16_tile_addend(El, NE, (int64_t)T * NE, w.E16[l], B, T, 2 * net->C, sf.layer[l].d, sf.layer[l].mt, stream));
+  }
   return SS_OK;
 }
 
-// the L residual layers + skip projection; X in/out, leaves relu(skip_projection) in G.
-// Deferred-skip mode (net->w_skipall set): the per-layer output projection only runs its residual half (N = C, no skip
+// The L residual layers + skip projection; X in/out, leaves relu(skip_projection) in G. `step` = network time, `eval` = index of this network
+// evaluation in its sampling loop (StackForm.n_wsets). One function per StackKind:
+//
+// STACK_FP32. Deferred-skip mode (net->w_skipall set): the per-layer output projection only runs its residual half (N = C, no skip
 // read-modify-write), every layer's gate output is kept ([rows][L*C]) and the skip sum of all layers is ONE GEMM with
 // K = L*C at the end of the stack - same products, summed in one accumulator chain instead of layer by layer.
-// bf16-in-HBM form of the stack: Yh = bf16(x + dstep_0) on entry; per layer gate (Yh -> GAh[l], bf16) and residual projection
-// (GAh[l] -> X fp32 in place, Yh = bf16(x + dstep_{l+1})); then the K = L*C skip GEMM -> S (fp32). Same operand roundings as
-// oracle/restatement.py with set_matmul_rounding("bf16") - each operand is rounded once, where it is produced.
-int run_residual_stack_h(const ss_wavenet* net, int step, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
+int skip_gemm_f32(const ss_wavenet* net, const StackForm& sf, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream, bool leave_partials) {
+  const int C = net->C, L = net->L;
+  // S = sum_l skip_l = [g_0 | g_1 | ... | g_{L-1}] . [W_skip_0 ; ... ; W_skip_{L-1}]^T + sum_l b_skip_l
+  ss_conv_gemm_args k = base_args(B, T, lens);
+  set_a(k, w.GA, L * C, T);
+  k.Cin = L * C;
+  k.W = net->w_skipall;
+  k.N = C;
+  k.Np = round_up32(C);
+  k.Kp = L * C;
+  k.epi = SS_EPI_STORE;
+  k.bias = net->b_skipall;
+  set_c(k, sf.skip_folded ? w.G : w.S, C, T);
+  if (sf.skip_folded) k.act = SS_ACT_RELU;
+  k.tile = SS_TILE_64x64;
+  k.mfma_bf16 = sf.conv_bf16;
+  set_groups(k, net, B, net->gs_w_skipall, net->gs_b_skipall);
+  switch (sf.skip) {
+    case SKIP_X3:
+      k.w_group_stride = net->gs_w_skipall_x3;
+      return ss_gemm16x_store(&k, net->w_skipall_x3, sf.mt16, stream);
+    case SKIP_SPLITK:
+      return leave_partials && sf.partials_ok ? ss_gemm16_store_partials(&k, 4, sf.ksplit, w.KP, stream) : ss_gemm16_store_splitk(&k, 4, sf.ksplit, w.KP, stream);
+    case SKIP_STORE16: return ss_gemm16_store(&k, sf.mt16, stream);
+    default: return ss_conv_gemm(&k, stream);
+  }
+}
+
+int run_stack_f32(const ss_wavenet* net, const StackForm& sf, int step, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream, bool leave_partials) {
   const int C = net->C, L = net->L;
   const int NE = L * 2 * C;
-  const int sp = smode(net) ? (net->mfma_split == 2 ? 2 : 1) : 0, pl = sp ? 2 : 1;   // split form; planes per 16-bit row
-  const bool fused = w.H512[0] != nullptr;
-  for (int l = 0; l < L && fused; ++l) {   // fused-layer form: gate + residual projection of layer l in one launch, G kept in LDS
-    ss_layer512_args f;
-    memset(&f, 0, sizeof(f));
-    f.Hin = w.H512[l & 1];
-    f.d = 1 << (l % net->dil_cycle);
-    f.lens = lens;
-    f.B = B;
-    f.T = T;
-    f.Wg = net->w_dil_f[l] + wset_off(net, net->ws_w_dil_f);
-    f.n_products = net->mfma_products == 1 ? 1 : 2;
-    if (w.E512h) {   // evaluation j reads addend set j % n_esets
-      f.E512 = reinterpret_cast<const float*>(w.E512h + (int64_t)(g_wset_eval % net->n_esets) * w.e512h_set + (int64_t)l * w.e512h_layer);
-      f.e_f16 = 1;
+  const int ldg = sf.defer ? L * C : C;
+  for (int l = 0; l < L; ++l) {
+    const LayerForm& y = sf.layer[l];
+    // y = dilated_conv(x + dstep) + cond_proj ; g = sigmoid(y[:C]) * tanh(y[C:])   (net.py:66-73)
+    ss_conv_gemm_args a = base_args(B, T, lens);
+    set_a(a, w.X, C, T);
+    a.Cin = C;
+    set_taps3(a, y.d);
+    a.a_bias = net->dstep + ((int64_t)step * L + l) * C;
+    a.W = net->w_dil[l];
+    a.N = C;
+    a.Np = 2 * C;
+    a.Kp = round_up32(C);
+    a.epi = SS_EPI_GATE;
+    a.E = w.E + (int64_t)l * 2 * C;
+    a.lde = NE;
+    a.e_batch_stride = (int64_t)T * NE;
+    float* Gl = sf.defer ? w.GA + (int64_t)l * C : w.G;
+    set_c(a, Gl, ldg, T);
+    a.mfma_bf16 = sf.conv_bf16;
+    set_groups(a, net, B, net->gs_w_dil, 0, net->gs_dstep);
+    if (y.gate != GATE_CONV) {
+      a.W = net->w_dil_wino[l];
+      a.w_group_stride = net->gs_w_dil_wino;
+    }
+    switch (y.gate) {
+      case GATE_CONV: SS_PROPAGATE(ss_conv_gemm(&a, stream)); break;
+      case GATE_WINO23: SS_PROPAGATE(ss_wino_gate(&a, y.d, stream)); break;
+      case GATE_WINO43: SS_PROPAGATE(ss_wino43_gate(&a, y.d, stream)); break;
+      case GATE_WINO43_16: SS_PROPAGATE(ss_wino43_gate16(&a, y.d, y.mt, stream)); break;
+      case GATE_WINO43_16W:
+        if (y.e16_floats) {   // addend in fetch order, laid out for exactly this tiling
+          a.E = w.E16[l];
+          a.e_tiled = 1;
+        }
+        SS_PROPAGATE(ss_wino43_gate16w(&a, net->w_dil_wino16[l], y.d, y.mt, stream));
+        break;
+      case GATE_WINO43_16X:
+        a.w_group_stride = net->gs_w_dil_x3;
+        SS_PROPAGATE(ss_wino43_gate16x(&a, net->w_dil_x3[l], y.d, 0, stream));
+        break;
+    }
+    // y = output_projection(g) ; x = (x + y[:C]) / sqrt(2) ; skip += y[C:]   (net.py:75-77)
+    // deferred-skip form: this launch only produces the residual stream, and the LAST layer's stream is never read (net.py:120-127)
+    if (sf.defer && l + 1 == L) break;
+    ss_conv_gemm_args o = base_args(B, T, lens);
+    set_a(o, Gl, ldg, T);
+    o.Cin = C;
+    o.W = net->w_out[l];
+    o.N = sf.defer ? C : 2 * C;  // deferred skip: only the residual half (the first C packed rows) runs per layer
+    if (sf.defer) o.tile = SS_TILE_64x64;
+    o.Np = 2 * C;
+    o.Kp = round_up32(C);
+    o.epi = SS_EPI_RESSKIP;
+    o.bias = net->b_out[l];
+    o.Nh = C;
+    o.R = w.X;
+    o.ldr = C;
+    o.r_batch_stride = (int64_t)T * C;
+    set_c(o, w.X, C, T);
+    o.post_scale = 0.70710678118654752440f;  // 1/sqrt(2.0)
+    o.C2 = w.S;
+    o.ldc2 = C;
+    o.c2_batch_stride = (int64_t)T * C;
+    o.accumulate = sf.defer ? 0 : l > 0;
+    o.mfma_bf16 = sf.conv_bf16;
+    set_groups(o, net, B, net->gs_w_out, net->gs_b_out);
+    if (y.proj == PROJ_RES16W) {
+      o.w_group_stride = net->gs_w_out16;
+      SS_PROPAGATE(ss_gemm16_resw(&o, net->w_out16[l], 0, stream));
     } else {
-      f.E512 = w.E512 + (int64_t)l * w.e512_layer;
+      SS_PROPAGATE(y.proj == PROJ_RES16 ? ss_gemm16_res(&o, 0, stream) : ss_conv_gemm(&o, stream));
     }
-    const int gpl = w.g_compact ? 1 : pl;   // planes per G row
-    f.G = w.GAh + (int64_t)l * C * gpl;
-    f.g_batch_stride = (int64_t)T * L * C * gpl;
-    f.ldg = L * C * gpl;
-    f.g_compact = w.g_compact ? 1 : 0;
-    f.mask_rows = 1;
-    f.out_scale = net->mfma_out_scale;
-    f.post_scale = 0.70710678118654752440f;
-    if (l + 1 < L) {   // the residual stream of the last layer is never read (net.py:120-127)
-      f.Hout = w.H512[(l & 1) ^ 1];
-      f.P = w.P512;
-      f.Wr = net->w_out_f[l] + wset_off(net, net->ws_w_out_f);
-      f.bias_r = net->b_out[l];
-      f.next_bias = net->dstep + ((int64_t)step * L + l + 1) * C;
-      f.cur_bias = net->dstep + ((int64_t)step * L + l) * C;
-    }
-    SS_PROPAGATE(ss_layer512(&f, stream));
   }
-  for (int l = 0; l < L && !fused; ++l) {
-    const int d = 1 << (l % net->dil_cycle);
+  return sf.defer ? skip_gemm_f32(net, sf, lens, B, T, w, stream, leave_partials) : SS_OK;
+}
+
+// The 16-bit kinds: per layer gate (stream -> GAh[l]) and residual projection (GAh[l] -> stream + dstep_{l+1}), then the K = L*C skip GEMM -> S (fp32).
+// Same operand roundings as oracle/restatement.py with set_matmul_rounding("bf16") - each operand is rounded once, where it is produced.
+inline int64_t wset_off(const StackForm& sf, int eval, int64_t stride) { return (int64_t)(eval % sf.n_wsets) * stride; }
+// "fp16q4" (try_q4): the launch with its second product on the fp4 instruction (weight pack Wq, A-operand scale q_scale) when that kernel's own
+// _ok rule takes it. The rule reads the filled argument struct, so it is asked here, per launch, and not in resolve_form()
+int launch_h(const ss_gemm_bf16_args& a, bool try_q4, const uint16_t* Wq, int64_t gs_wq, float q_scale, int (*q_ok)(const ss_gemm_bf16_args*),
+             int (*q_run)(const ss_gemm_bf16_args*, void*), hipStream_t stream) {
+  if (try_q4) {
+    ss_gemm_bf16_args q = a;
+    q.split = 3;
+    q.W = Wq;
+    q.w_group_stride = gs_wq;
+    q.q_scale = q_scale;
+    if (q_ok(&q)) return q_run(&q, stream);
+  }
+  return ss_gemm_bf16(&a, stream);
+}
+
+int skip_gemm_h(const ss_wavenet* net, const StackForm& sf, int eval, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
+  const int C = net->C, L = net->L;
+  ss_gemm_bf16_args k = base_args_h(net, B, T, lens);
+  set_a(k, w.GAh, L * C * sf.gplanes, T);
+  k.a_compact = sf.g_compact ? 1 : 0;
+  k.split = sf.split;
+  k.out_scale = net->mfma_out_scale;
+  k.K = L * C;
+  if (sf.skip_w_compact) {
+    k.W = net->w_skipall_c + wset_off(sf, eval, net->ws_w_skipall_c);
+    k.one_product = 2;
+  } else {
+    k.W = net->w_skipall_h + wset_off(sf, eval, net->ws_w_skipall_h);
+    k.one_product = sf.one_product ? 1 : 0;
+  }
+  k.w_group_stride = net->gs_w_skipall_h;
+  k.N = C;
+  k.Np = round_up32(C);
+  k.epi = SS_HEPI_STORE;
+  k.bias = net->b_skipall;
+  k.bias_group_stride = net->gs_b_skipall;
+  set_c(k, sf.skip_folded ? w.G : w.S, C, T);
+  if (sf.skip_folded) k.act = SS_ACT_RELU;
+  return launch_h(k, sf.q4_skip, net->w_skipall_q, net->gs_w_skipall_q, net->q_scale_z, ss_gemm_bf16_tile256q_ok, ss_gemm_bf16_tile256q, stream);
+}
+
+// STACK_PAIR16: Yh = 16-bit (x + dstep_0) on entry; the residual projection updates X (fp32, bf16 mode only) and writes Yh for the next layer
+int run_stack_pair16(const ss_wavenet* net, const StackForm& sf, int step, int eval, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
+  const int C = net->C, L = net->L, pl = sf.planes;
+  const int NE = L * 2 * C;
+  const float* dstep0 = net->dstep + (int64_t)step * L * C;
+  const int gsz = net->n_groups > 1 ? B / net->n_groups : 0;
+  if (sf.split == 2) SS_PROPAGATE(ss_split_f16(w.X, dstep0, 1.0f, w.Yh, B, T, C, C, 2 * C, lens, gsz, net->gs_dstep, stream));
+  else if (sf.split) SS_PROPAGATE(ss_split_bf16(w.X, dstep0, w.Yh, B, T, C, C, 2 * C, lens, gsz, net->gs_dstep, stream));
+  else SS_PROPAGATE(ss_to_bf16(w.X, dstep0, w.Yh, B, T, C, C, C, lens, gsz, net->gs_dstep, stream));
+  for (int l = 0; l < L; ++l) {
     ss_gemm_bf16_args g = base_args_h(net, B, T, lens);
-    g.A = w.Yh;
-    g.lda = C * pl;
-    g.a_batch_stride = (int64_t)T * C * pl;
-    g.split = sp;
+    set_a(g, w.Yh, C * pl, T);
+    g.split = sf.split;
     g.out_scale = net->mfma_out_scale;
     g.K = C;
-    g.ntaps = 3;
-    g.tap_off[0] = -d;
-    g.tap_off[1] = 0;
-    g.tap_off[2] = d;
-    g.W = net->w_dil_h[l] + wset_off(net, net->ws_w_dil_h);
+    set_taps3(g, sf.layer[l].d);
+    g.W = net->w_dil_h[l] + wset_off(sf, eval, net->ws_w_dil_h);
     g.w_group_stride = net->gs_w_dil_h;
     g.N = C;
     g.Np = 2 * C;
     g.epi = SS_HEPI_GATE;
-    g.gate_mode = 0;
     g.E = w.E + (int64_t)l * 2 * C;
     g.lde = NE;
     g.e_batch_stride = (int64_t)T * NE;
-    g.C = w.GAh + (int64_t)l * C * pl;
-    g.ldc = L * C * pl;
-    g.c_batch_stride = (int64_t)T * L * C * pl;
-    bool gate_done = false;
-    if (sp == 2 && net->w_dil_q[l] && net->q_scale_gate > 0.f) {   // "fp16q4": this layer's gate with its second product on the fp4 instruction, when the launch qualifies
-      ss_gemm_bf16_args q = g;
-      q.split = 3;
-      q.W = net->w_dil_q[l];
-      q.w_group_stride = net->gs_w_dil_q;
-      q.q_scale = net->q_scale_gate;
-      if (ss_gemm_bf16_gate128q_ok(&q)) {
-        SS_PROPAGATE(ss_gemm_bf16_gate128q(&q, stream));
-        gate_done = true;
-      }
-    }
-    if (!gate_done) SS_PROPAGATE(ss_gemm_bf16(&g, stream));
+    set_c(g, w.GAh + (int64_t)l * C * pl, L * C * pl, T);
+    SS_PROPAGATE(launch_h(g, sf.layer[l].q4_gate, net->w_dil_q[l], net->gs_w_dil_q, net->q_scale_gate, ss_gemm_bf16_gate128q_ok, ss_gemm_bf16_gate128q, stream));
     // the residual stream of the LAST layer is never read (only the skip sum leaves the stack, net.py:120-127): no projection for it
     if (l + 1 == L) break;
     ss_gemm_bf16_args o = base_args_h(net, B, T, lens);
-    o.A = w.GAh + (int64_t)l * C * pl;
-    o.lda = L * C * pl;
-    o.a_batch_stride = (int64_t)T * L * C * pl;
-    o.split = sp;
+    set_a(o, w.GAh + (int64_t)l * C * pl, L * C * pl, T);
+    o.split = sf.split;
     o.out_scale = net->mfma_out_scale;
     o.K = C;
-    o.W = net->w_out_h[l] + wset_off(net, net->ws_w_out_h);
+    o.W = net->w_out_h[l] + wset_off(sf, eval, net->ws_w_out_h);
     o.w_group_stride = net->gs_w_out_h;
     o.N = C;
     o.Np = C;  // the residual half = the first C packed rows
@@ -332,7 +511,7 @@ int run_residual_stack_h(const ss_wavenet* net, int step, const int32_t* lens, i
     o.Y = w.Yh;
     o.ldy = C * pl;
     o.y_batch_stride = (int64_t)T * C * pl;
-    if (sp) {   // split mode: the stream lives only as the pair Yh = x + dstep_l (16 significant bits; measured harmless, oracle/bf16x2_numerics.py)
+    if (sf.split) {   // split mode: the stream lives only as the pair Yh = x + dstep_l (16 significant bits; measured harmless, oracle/bf16x2_numerics.py)
       o.cur_bias = net->dstep + ((int64_t)step * L + l) * C;
       o.cur_bias_group_stride = net->gs_dstep;
     } else {
@@ -342,216 +521,65 @@ int run_residual_stack_h(const ss_wavenet* net, int step, const int32_t* lens, i
     }
     SS_PROPAGATE(ss_gemm_bf16(&o, stream));
   }
-  ss_gemm_bf16_args k = base_args_h(net, B, T, lens);
-  k.A = w.GAh;
-  k.lda = L * C * (w.g_compact ? 1 : pl);
-  k.a_batch_stride = (int64_t)T * L * C * (w.g_compact ? 1 : pl);
-  k.a_compact = w.g_compact ? 1 : 0;
-  k.split = sp;
-  k.out_scale = net->mfma_out_scale;
-  k.K = L * C;
-  k.W = net->w_skipall_h + wset_off(net, net->ws_w_skipall_h);
-  k.one_product = net->mfma_products == 1 ? 1 : 0;
-  if (w.g_compact && net->mfma_products == 1 && net->w_skipall_c && net->n_groups <= 1) {   // the one-term sets without their zero plane (L2-resident)
-    k.W = net->w_skipall_c + wset_off(net, net->ws_w_skipall_c);
-    k.one_product = 2;
-  }
-  k.w_group_stride = net->gs_w_skipall_h;
-  k.N = C;
-  k.Np = round_up32(C);
-  k.epi = SS_HEPI_STORE;
-  k.bias = net->b_skipall;
-  k.bias_group_stride = net->gs_b_skipall;
-  k.C = w.S;
-  k.ldc = C;
-  k.c_batch_stride = (int64_t)T * C;
-  if (net->skipall_folded) {   // w_skipall_h already carries skip_projection / sqrt(L): this GEMM + ReLU is the stack's output
-    k.act = SS_ACT_RELU;
-    k.C = w.G;
-  }
-  if (sp == 2 && net->w_skipall_q && net->q_scale_z > 0.f) {   // "fp16q4": the second product on the fp4 instruction, when the launch qualifies
-    ss_gemm_bf16_args q = k;
-    q.split = 3;
-    q.W = net->w_skipall_q;
-    q.w_group_stride = net->gs_w_skipall_q;
-    q.q_scale = net->q_scale_z;
-    if (ss_gemm_bf16_tile256q_ok(&q)) return ss_gemm_bf16_tile256q(&q, stream);
-  }
-  return ss_gemm_bf16(&k, stream);
+  return skip_gemm_h(net, sf, eval, lens, B, T, w, stream);
 }
 
-// Yh = bf16(X + dstep[step][0]) : the first layer's conv operand (bf16-in-HBM mode)
-int stack_entry_h(const ss_wavenet* net, int step, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
-  if (w.H512[0])
-    return ss_layer512_entry(w.X, net->C, (int64_t)T * net->C, net->dstep + (int64_t)step * net->L * net->C, lens, w.H512[0], w.P512, B, T, stream);
-  if (net->mfma_split == 2)
-    return ss_split_f16(w.X, net->dstep + (int64_t)step * net->L * net->C, 1.0f, w.Yh, B, T, net->C, net->C, 2 * net->C, lens,
-                        net->n_groups > 1 ? B / net->n_groups : 0, net->gs_dstep, stream);
-  if (smode(net))
-    return ss_split_bf16(w.X, net->dstep + (int64_t)step * net->L * net->C, w.Yh, B, T, net->C, net->C, 2 * net->C, lens,
-                         net->n_groups > 1 ? B / net->n_groups : 0, net->gs_dstep, stream);
-  return ss_to_bf16(w.X, net->dstep + (int64_t)step * net->L * net->C, w.Yh, B, T, net->C, net->C, net->C, lens,
-                    net->n_groups > 1 ? B / net->n_groups : 0, net->gs_dstep, stream);
-}
-
-// partials_ok: the caller's next kernel (f0_tail_kernel / mel_tail_kernel) can add the split-K slices of the skip GEMM itself (skip_partials()
-// tells it whether it has to): the reduction launch is then left out
-inline bool skip_partials(const ss_wavenet* net, const WsLayout& w) {
-  return w.ksplit > 1 && net->skipall_folded && !hmode(net) && !net->mfma_bf16 && !(net->mfma_x3 && net->w_skipall_x3);
-}
-int run_residual_stack(const ss_wavenet* net, int step, const int32_t* lens, int B, int T, const WsLayout& w,
-                       hipStream_t stream, bool partials_ok = false) {
+// STACK_FUSED16: gate + residual projection of layer l in one launch, G kept in LDS; the stream alternates between the two H512 buffers
+int run_stack_fused16(const ss_wavenet* net, const StackForm& sf, int step, int eval, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
   const int C = net->C, L = net->L;
-  const int NE = L * 2 * C;
-  if (hmode(net)) {
-    SS_PROPAGATE(stack_entry_h(net, step, lens, B, T, w, stream));
-    SS_PROPAGATE(run_residual_stack_h(net, step, lens, B, T, w, stream));
-    if (net->skipall_folded) return SS_OK;
-  } else
+  SS_PROPAGATE(ss_layer512_entry(w.X, C, (int64_t)T * C, net->dstep + (int64_t)step * L * C, lens, w.H512[0], w.P512, B, T, stream));
   for (int l = 0; l < L; ++l) {
-    const int d = 1 << (l % net->dil_cycle);
-    // y = dilated_conv(x + dstep) + cond_proj ; g = sigmoid(y[:C]) * tanh(y[C:])   (net.py:66-73)
-    ss_conv_gemm_args a = base_args(B, T, lens);
-    a.A = w.X;
-    a.lda = C;
-    a.a_batch_stride = (int64_t)T * C;
-    a.Cin = C;
-    a.ntaps = 3;
-    a.tap_off[0] = -d;
-    a.tap_off[1] = 0;
-    a.tap_off[2] = d;
-    a.a_bias = net->dstep + ((int64_t)step * L + l) * C;
-    a.W = net->w_dil[l];
-    a.N = C;
-    a.Np = 2 * C;
-    a.Kp = round_up32(C);
-    a.epi = SS_EPI_GATE;
-    a.gate_mode = 0;
-    a.E = w.E + (int64_t)l * 2 * C;
-    a.lde = NE;
-    a.e_batch_stride = (int64_t)T * NE;
-    const bool defer = net->w_skipall != nullptr;  // see the note above run_residual_stack
-    const int ldg = defer ? L * C : C;
-    float* Gl = defer ? w.GA + (int64_t)l * C : w.G;
-    a.C = Gl;
-    a.ldc = ldg;
-    a.c_batch_stride = (int64_t)T * ldg;
-    a.mfma_bf16 = net->mfma_bf16;
-    if (net->n_groups > 1) {
-      a.group_size = B / net->n_groups;
-      a.w_group_stride = net->gs_w_dil;
-      a.a_bias_group_stride = net->gs_dstep;
-    }
-    if (net->w_dil_wino[l] && !net->mfma_bf16) {  // Winograd F(2,3): pairs of frames (t, t+d) from 4 products instead of 6
-      a.W = net->w_dil_wino[l];
-      a.w_group_stride = net->gs_w_dil_wino;
-      if (net->wino_m == 4 && net->mfma_x3 && net->w_dil_x3[l]) {   // opt-in "bf16x3" mode: split operands on the bf16 matrix cores
-        a.w_group_stride = net->gs_w_dil_x3;
-        SS_PROPAGATE(ss_wino43_gate16x(&a, net->w_dil_x3[l], d, 0, stream));
-      } else if (net->wino_m == 4) {
-        const int g16 = g_ss_tuning.gate16;  // 0: 32x32x2 tiles; 1: per-launch pick; 2 / 3: 16x16x4 tiles of 16*MT quads
-        if (g16 == 0) SS_PROPAGATE(ss_wino43_gate(&a, d, stream));
-        else if (net->w_dil_wino16[l] && w.E16[l]) {   // addend in fetch order, laid out for exactly this tiling
-          a.E = w.E16[l];
-          a.e_tiled = 1;
-          SS_PROPAGATE(ss_wino43_gate16w(&a, net->w_dil_wino16[l], d, w.mt16[l], stream));
-        } else if (net->w_dil_wino16[l]) SS_PROPAGATE(ss_wino43_gate16w(&a, net->w_dil_wino16[l], d, g16 == 1 ? 0 : g16, stream));
-        else SS_PROPAGATE(ss_wino43_gate16(&a, d, g16 == 1 ? 0 : g16, stream));
-      } else {
-        SS_PROPAGATE(ss_wino_gate(&a, d, stream));
-      }
+    ss_layer512_args f;
+    memset(&f, 0, sizeof(f));
+    f.Hin = w.H512[l & 1];
+    f.d = sf.layer[l].d;
+    f.lens = lens;
+    f.B = B;
+    f.T = T;
+    f.Wg = net->w_dil_f[l] + wset_off(sf, eval, net->ws_w_dil_f);
+    f.n_products = sf.one_product ? 1 : 2;
+    if (sf.n_esets) {   // evaluation j reads addend set j % n_esets
+      f.E512 = reinterpret_cast<const float*>(w.E512h + (int64_t)(eval % sf.n_esets) * w.e512h_set + (int64_t)l * w.e512h_layer);
+      f.e_f16 = 1;
     } else {
-      SS_PROPAGATE(ss_conv_gemm(&a, stream));
+      f.E512 = w.E512 + (int64_t)l * w.e512_layer;
     }
-    // y = output_projection(g) ; x = (x + y[:C]) / sqrt(2) ; skip += y[C:]   (net.py:75-77)
-    // deferred-skip form: this launch only produces the residual stream, and the LAST layer's stream is never read (net.py:120-127)
-    if (defer && l + 1 == L) break;
-    ss_conv_gemm_args o = base_args(B, T, lens);
-    o.A = Gl;
-    o.lda = ldg;
-    o.a_batch_stride = (int64_t)T * ldg;
-    o.Cin = C;
-    o.W = net->w_out[l];
-    o.N = defer ? C : 2 * C;  // deferred skip: only the residual half (the first C packed rows) runs per layer
-    if (defer) o.tile = SS_TILE_64x64;
-    o.Np = 2 * C;
-    o.Kp = round_up32(C);
-    o.epi = SS_EPI_RESSKIP;
-    o.bias = net->b_out[l];
-    o.Nh = C;
-    o.R = w.X;
-    o.ldr = C;
-    o.r_batch_stride = (int64_t)T * C;
-    o.C = w.X;
-    o.ldc = C;
-    o.c_batch_stride = (int64_t)T * C;
-    o.post_scale = 0.70710678118654752440f;  // 1/sqrt(2.0)
-    o.C2 = w.S;
-    o.ldc2 = C;
-    o.c2_batch_stride = (int64_t)T * C;
-    o.accumulate = defer ? 0 : l > 0;
-    o.mfma_bf16 = net->mfma_bf16;
-    if (net->n_groups > 1) {
-      o.group_size = B / net->n_groups;
-      o.w_group_stride = net->gs_w_out;
-      o.bias_group_stride = net->gs_b_out;
+    f.G = w.GAh + (int64_t)l * C * sf.gplanes;
+    f.g_batch_stride = (int64_t)T * L * C * sf.gplanes;
+    f.ldg = L * C * sf.gplanes;
+    f.g_compact = sf.g_compact ? 1 : 0;
+    f.mask_rows = 1;
+    f.out_scale = net->mfma_out_scale;
+    f.post_scale = 0.70710678118654752440f;
+    if (l + 1 < L) {   // the residual stream of the last layer is never read (net.py:120-127)
+      f.Hout = w.H512[(l & 1) ^ 1];
+      f.P = w.P512;
+      f.Wr = net->w_out_f[l] + wset_off(sf, eval, net->ws_w_out_f);
+      f.bias_r = net->b_out[l];
+      f.next_bias = net->dstep + ((int64_t)step * L + l + 1) * C;
+      f.cur_bias = net->dstep + ((int64_t)step * L + l) * C;
     }
-    if (defer && !net->mfma_bf16 && (C == 192 || C == 256) && net->w_out16[l]) {   // weights in the kernel's fetch order
-      o.w_group_stride = net->gs_w_out16;
-      SS_PROPAGATE(ss_gemm16_resw(&o, net->w_out16[l], 0, stream));
-    } else if (defer && !net->mfma_bf16 && (C == 192 || C == 256)) {
-      SS_PROPAGATE(ss_gemm16_res(&o, 0, stream));   // 16x16x4 tiles, balanced single round (gemm16.hip)
-    } else {
-      SS_PROPAGATE(ss_conv_gemm(&o, stream));
-    }
+    SS_PROPAGATE(ss_layer512(&f, stream));
   }
-  if (net->w_skipall && !hmode(net)) {  // S = sum_l skip_l = [g_0 | g_1 | ... | g_{L-1}] . [W_skip_0 ; ... ; W_skip_{L-1}]^T + sum_l b_skip_l
-    ss_conv_gemm_args k = base_args(B, T, lens);
-    k.A = w.GA;
-    k.lda = L * C;
-    k.a_batch_stride = (int64_t)T * L * C;
-    k.Cin = L * C;
-    k.W = net->w_skipall;
-    k.N = C;
-    k.Np = round_up32(C);
-    k.Kp = L * C;
-    k.epi = SS_EPI_STORE;
-    k.bias = net->b_skipall;
-    k.C = w.S;
-    k.ldc = C;
-    k.c_batch_stride = (int64_t)T * C;
-    k.tile = SS_TILE_64x64;
-    k.mfma_bf16 = net->mfma_bf16;
-    if (net->n_groups > 1) {
-      k.group_size = B / net->n_groups;
-      k.w_group_stride = net->gs_w_skipall;
-      k.bias_group_stride = net->gs_b_skipall;
-    }
-    const bool use16 = !net->mfma_bf16 && k.Kp == k.Cin;   // 16x16x4 tiles, both operands by LDS-DMA (gemm16.hip)
-    // row tile 16 * mt16 (0 = picked per launch). Long-K launch: when 64-row tiles also fit one round at three workgroups per CU they beat
-    // the 96-row pick (mel at C2: 240.7 vs 250.7 us)
-    const int mt16 = (long)((T + 63) / 64) * B * ((C + 63) / 64) <= 3L * ss_n_cu() && !(net->mfma_x3 && net->w_skipall_x3) ? 4 : 0;
-    if (net->skipall_folded) {  // w_skipall already carries skip_projection / sqrt(L): this GEMM + ReLU is the stack's output
-      k.act = SS_ACT_RELU;
-      k.C = w.G;
-      if (use16 && net->mfma_x3 && net->w_skipall_x3) {   // opt-in bf16x3 mode: split operands on the bf16 matrix cores (gemm16x.hip)
-        k.w_group_stride = net->gs_w_skipall_x3;
-        return ss_gemm16x_store(&k, net->w_skipall_x3, mt16, stream);
-      }
-      if (use16 && w.ksplit > 1)   // one short utterance: split K over the idle CUs
-        return partials_ok && skip_partials(net, w) ? ss_gemm16_store_partials(&k, 4, w.ksplit, w.KP, stream) : ss_gemm16_store_splitk(&k, 4, w.ksplit, w.KP, stream);
-      return use16 ? ss_gemm16_store(&k, mt16, stream) : ss_conv_gemm(&k, stream);
-    }
-    if (use16 && w.ksplit > 1) SS_PROPAGATE(ss_gemm16_store_splitk(&k, 4, w.ksplit, w.KP, stream));
-    else SS_PROPAGATE(use16 ? ss_gemm16_store(&k, mt16, stream) : ss_conv_gemm(&k, stream));
+  return skip_gemm_h(net, sf, eval, lens, B, T, w, stream);
+}
+
+// leave_partials: the caller's next kernel (f0_tail_kernel / mel_tail_kernel) adds the split-K slices of the skip GEMM itself whenever
+// sf.partials_ok: the reduction launch is then left out
+int run_residual_stack(const ss_wavenet* net, const StackForm& sf, int step, int eval, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream,
+                       bool leave_partials = false) {
+  switch (sf.kind) {
+    case STACK_FP32: SS_PROPAGATE(run_stack_f32(net, sf, step, lens, B, T, w, stream, leave_partials)); break;
+    case STACK_PAIR16: SS_PROPAGATE(run_stack_pair16(net, sf, step, eval, lens, B, T, w, stream)); break;
+    case STACK_FUSED16: SS_PROPAGATE(run_stack_fused16(net, sf, step, eval, lens, B, T, w, stream)); break;
   }
+  if (sf.skip_folded) return SS_OK;
   // x = relu(skip_projection(sum(skip) / sqrt(L)))   (net.py:124-127)
+  const int C = net->C;
   ss_conv_gemm_args s = base_args(B, T, lens);
-  s.A = w.S;
-  s.lda = C;
-  s.a_batch_stride = (int64_t)T * C;
+  set_a(s, w.S, C, T);
   s.Cin = C;
-  s.a_scale = 1.0f / sqrtf((float)L);
+  s.a_scale = 1.0f / sqrtf((float)net->L);
   s.W = net->w_skip;
   s.N = C;
   s.Np = round_up32(C);
@@ -559,15 +587,9 @@ int run_residual_stack(const ss_wavenet* net, int step, const int32_t* lens, int
   s.epi = SS_EPI_STORE;
   s.bias = net->b_skip;
   s.act = SS_ACT_RELU;
-  s.C = w.G;
-  s.ldc = C;
-  s.c_batch_stride = (int64_t)T * C;
-  s.mfma_bf16 = smode(net) ? 0 : net->mfma_bf16;
-  if (net->n_groups > 1) {
-    s.group_size = B / net->n_groups;
-    s.w_group_stride = net->gs_w_skip;
-    s.bias_group_stride = net->gs_b_skip;
-  }
+  set_c(s, w.G, C, T);
+  s.mfma_bf16 = sf.outer_bf16;
+  set_groups(s, net, B, net->gs_w_skip, net->gs_b_skip);
   return ss_conv_gemm(&s, stream);
 }
 
@@ -836,24 +858,14 @@ inline int grid_for(int64_t n) {
 
 extern "C" int64_t ss_wavenet_workspace_bytes(const ss_wavenet* net, int B, int T) {
   if (!net || B <= 0 || T <= 0) return -1;
-  return ws_layout(net, B, T, nullptr).bytes;
-}
-
-// x_in -> relu(input_projection) -> residual stack; leaves relu(skip_projection(.)) in w.G  (net.py:114-127)
-static int mel_input_proj(const ss_wavenet* net, const float* x_in, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream);
-static int mel_net_body(const ss_wavenet* net, const float* x_in, const int32_t* lens, int B, int T, const WsLayout& w, int t,
-                        hipStream_t stream) {
-  SS_PROPAGATE(mel_input_proj(net, x_in, lens, B, T, w, stream));
-  return run_residual_stack(net, t, lens, B, T, w, stream);
+  return ws_layout(net, resolve_form(net, B, T), B, T, nullptr).bytes;
 }
 
 // x_in -> w.X = relu(input_projection(x_in))  (net.py:114-116)
 static int mel_input_proj(const ss_wavenet* net, const float* x_in, const int32_t* lens, int B, int T, const WsLayout& w, hipStream_t stream) {
   const int C = net->C, M = net->in_dim;
   ss_conv_gemm_args a = base_args(B, T, lens);
-  a.A = x_in;
-  a.lda = M;
-  a.a_batch_stride = (int64_t)T * M;
+  set_a(a, x_in, M, T);
   a.Cin = M;
   a.W = net->w_in;
   a.N = C;
@@ -862,9 +874,7 @@ static int mel_input_proj(const ss_wavenet* net, const float* x_in, const int32_
   a.epi = SS_EPI_STORE;
   a.bias = net->b_in;
   a.act = SS_ACT_RELU;
-  a.C = w.X;
-  a.ldc = C;
-  a.c_batch_stride = (int64_t)T * C;
+  set_c(a, w.X, C, T);
   return ss_conv_gemm(&a, stream);
 }
 
@@ -872,7 +882,6 @@ static int mel_input_proj(const ss_wavenet* net, const float* x_in, const int32_
 // (C -> M), the DDPM posterior step on x (shallow_diffusion_tts.py:130-162; same tape / Philox counters as the SS_EPI_DDPM epilogue) and the
 // NEXT evaluation's input projection relu(W_in x + b) - two 16-20 us MFMA launches of 24-48 workgroups become one ~8 us VALU launch. Exact
 // fp32 FMAs; only the summation order over K differs from the matrix-core form. MTR = 2 frames per workgroup.
-constexpr int MTR = 2;
 __global__ __launch_bounds__(256) void mel_tail_kernel(const SkipSrc src, const float* __restrict__ Wf, const float* __restrict__ bf,
                                                        float* __restrict__ x, const float* __restrict__ noise, uint64_t seed,
                                                        const uint64_t* __restrict__ seed_dev, uint32_t step, float recip, float recipm1, float c1,
@@ -957,51 +966,43 @@ __global__ __launch_bounds__(256) void mel_tail_kernel(const SkipSrc src, const 
   }
 }
 
-// eps_out [B][T][M] = DiffNet(x_in, t, cond)  (plain output projection, for samplers that keep a history of eps)
-static int mel_eps(const ss_wavenet* net, const float* x_in, float* eps_out, const int32_t* lens, int B, int T, const WsLayout& w,
-                   int t, hipStream_t stream) {
+// One network evaluation DiffNet(x_in, t, cond) up to its output projection: x_in -> relu(input_projection) -> residual stack -> the arguments of
+// eps = output_projection(.) into out [B][T][M], whose epilogue the caller chooses  (net.py:114-130). eval: see run_residual_stack
+static int mel_net_body(const ss_wavenet* net, const StackForm& sf, const float* x_in, float* out, const int32_t* lens, int B, int T, const WsLayout& w,
+                        int t, int eval, hipStream_t stream, ss_conv_gemm_args& f) {
   const int C = net->C, M = net->in_dim;
-  SS_PROPAGATE(mel_net_body(net, x_in, lens, B, T, w, t, stream));
-  ss_conv_gemm_args f = base_args(B, T, lens);
-  f.A = w.G;
-  f.lda = C;
-  f.a_batch_stride = (int64_t)T * C;
+  SS_PROPAGATE(mel_input_proj(net, x_in, lens, B, T, w, stream));
+  SS_PROPAGATE(run_residual_stack(net, sf, t, eval, lens, B, T, w, stream));
+  f = base_args(B, T, lens);
+  set_a(f, w.G, C, T);
   f.Cin = C;
   f.W = net->w_final;
   f.N = M;
   f.Np = round_up32(M);
   f.Kp = round_up32(C);
-  f.epi = SS_EPI_STORE;
   f.bias = net->b_final;
-  f.C = eps_out;
-  f.ldc = M;
-  f.c_batch_stride = (int64_t)T * M;
+  set_c(f, out, M, T);
+  return SS_OK;
+}
+
+// eps_out [B][T][M] = DiffNet(x_in, t, cond)  (plain output projection, for samplers that keep a history of eps)
+static int mel_eps(const ss_wavenet* net, const StackForm& sf, const float* x_in, float* eps_out, const int32_t* lens, int B, int T, const WsLayout& w,
+                   int t, int eval, hipStream_t stream) {
+  ss_conv_gemm_args f;
+  SS_PROPAGATE(mel_net_body(net, sf, x_in, eps_out, lens, B, T, w, t, eval, stream, f));
+  f.epi = SS_EPI_STORE;
   f.mask_rows = 0;
   return ss_conv_gemm(&f, stream);
 }
 
 // One reverse step of the mel net at network time `t` with explicit update coefficients
 //   x0 = clamp(recip*x - recipm1*eps, -1, 1) ; x <- c1*x0 + c2*x + sigma*z
-static int mel_step(const ss_wavenet* net, float* x, const int32_t* lens, int B, int T, const WsLayout& w, int t, float recip,
-                    float recipm1, float c1, float c2, float sigma, const float* noise_t, uint64_t seed,
+static int mel_step(const ss_wavenet* net, const StackForm& sf, float* x, const int32_t* lens, int B, int T, const WsLayout& w, int t, int eval,
+                    float recip, float recipm1, float c1, float c2, float sigma, const float* noise_t, uint64_t seed,
                     const uint64_t* seed_dev, uint32_t step_id, hipStream_t stream, int x0_pred = 0) {
-  const int C = net->C, M = net->in_dim;
-  SS_PROPAGATE(mel_net_body(net, x, lens, B, T, w, t, stream));
-  // eps = output_projection(.) fused with the posterior step (shallow_diffusion_tts.py:130-162)
-  ss_conv_gemm_args f = base_args(B, T, lens);
-  f.A = w.G;
-  f.lda = C;
-  f.a_batch_stride = (int64_t)T * C;
-  f.Cin = C;
-  f.W = net->w_final;
-  f.N = M;
-  f.Np = round_up32(M);
-  f.Kp = round_up32(C);
-  f.epi = SS_EPI_DDPM;
-  f.bias = net->b_final;
-  f.C = x;
-  f.ldc = M;
-  f.c_batch_stride = (int64_t)T * M;
+  ss_conv_gemm_args f;
+  SS_PROPAGATE(mel_net_body(net, sf, x, x, lens, B, T, w, t, eval, stream, f));
+  f.epi = SS_EPI_DDPM;   // eps = output_projection(.) fused with the posterior step (shallow_diffusion_tts.py:130-162)
   f.ddpm_recip = recip;
   f.ddpm_recipm1 = recipm1;
   f.ddpm_c1 = c1;
@@ -1023,27 +1024,25 @@ extern "C" int ss_meldiff_sample(const ss_wavenet* net, float* x, const float* c
   SS_CHECK_ARG(net->L > 0 && net->L <= SS_MAX_LAYERS && (net->C % 32) == 0, "ss_meldiff_sample: bad net C=%d L=%d", net->C, net->L);
   SS_CHECK_ARG(0 <= step_lo && step_lo <= step_hi && step_hi <= net->steps, "ss_meldiff_sample: bad step range");
   SS_CHECK_ARG(net->n_groups <= 1, "ss_meldiff_sample: grouped nets are only supported by the f0 sampler");
-  const WsLayout w = ws_layout(net, B, T, ws);
+  const StackForm sf = resolve_form(net, B, T);
+  const WsLayout w = ws_layout(net, sf, B, T, ws);
   SS_CHECK_ARG(ws_bytes >= w.bytes, "ss_meldiff_sample: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)w.bytes);
   const int M = net->in_dim, C = net->C;
-  if (do_precompute) SS_PROPAGATE(precompute_cond(net, cond, lens, B, T, w, stream));
-  // launches that leave most CUs idle (one short utterance): the two small projections around the sampler update run as ONE VALU launch
+  if (do_precompute) SS_PROPAGATE(precompute_cond(net, sf, cond, lens, B, T, w, stream));
   const int Kp_in = round_up32(M);
-  const bool tail = g_ss_tuning.mel_tail != 0 && !net->mfma_bf16 && (int64_t)B * T <= 8L * ss_n_cu() && (C % 4) == 0 && (M % 4) == 0 &&
-                    (size_t)(MTR * C + MTR * Kp_in) * 4 <= 48 * 1024;
   for (int t = step_hi - 1; t >= step_lo; --t) {
-    g_wset_eval = net->steps - 1 - t;   // evaluation index of the whole loop, whatever [step_lo, step_hi) this call covers
+    const int eval = net->steps - 1 - t;   // evaluation index of the whole loop, whatever [step_lo, step_hi) this call covers
     const float sigma = t > 0 ? expf(0.5f * net->post_logvar[t]) : 0.0f;
     const float* noise_t = noise ? noise + (int64_t)t * B * T * M : nullptr;
-    if (!tail) {
-      SS_PROPAGATE(mel_step(net, x, lens, B, T, w, t, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], net->post_c1[t], net->post_c2[t], sigma, noise_t,
+    if (!sf.mel_tail) {
+      SS_PROPAGATE(mel_step(net, sf, x, lens, B, T, w, t, eval, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], net->post_c1[t], net->post_c2[t], sigma, noise_t,
                             seed, seed_dev, (uint32_t)t, stream));
       continue;
     }
+    // launches that leave most CUs idle (one short utterance): the two small projections around the sampler update run as ONE VALU launch
     if (t == step_hi - 1) SS_PROPAGATE(mel_input_proj(net, x, lens, B, T, w, stream));   // later evaluations get their input from the tail kernel
-    SS_PROPAGATE(run_residual_stack(net, t, lens, B, T, w, stream, true));
-    const bool parts = skip_partials(net, w);
-    const SkipSrc src = {w.G, w.KP, parts ? net->b_skipall : nullptr, parts ? w.ksplit : 1, (int64_t)B * T * C};
+    SS_PROPAGATE(run_residual_stack(net, sf, t, eval, lens, B, T, w, stream, true));
+    const SkipSrc src = {w.G, w.KP, sf.partials_ok ? net->b_skipall : nullptr, sf.partials_ok ? sf.ksplit : 1, (int64_t)B * T * C};
     hipLaunchKernelGGL(mel_tail_kernel, dim3((unsigned)(((int64_t)B * T + MTR - 1) / MTR)), dim3(256), (size_t)(MTR * C + MTR * Kp_in) * 4, stream, src, net->w_final,
                        net->b_final, x, noise_t, seed, seed_dev, (uint32_t)t, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], net->post_c1[t],
                        net->post_c2[t], sigma, net->w_in, net->b_in, t > step_lo ? w.X : nullptr, lens, B, T, C, M, Kp_in);
@@ -1060,13 +1059,13 @@ extern "C" int ss_prodiff_sample(const ss_wavenet* net, float* x, const float* c
   SS_CHECK_ARG(net && x && cond && ws && c1 && c2 && sigma, "ss_prodiff_sample: null pointer");
   SS_CHECK_ARG(net->n_groups <= 1 && net->L > 0 && net->L <= SS_MAX_LAYERS && (net->C % 32) == 0, "ss_prodiff_sample: bad net");
   SS_CHECK_ARG(n_steps >= 1 && n_steps <= net->steps, "ss_prodiff_sample: n_steps=%d outside [1, %d]", n_steps, net->steps);
-  const WsLayout w = ws_layout(net, B, T, ws);
+  const StackForm sf = resolve_form(net, B, T);
+  const WsLayout w = ws_layout(net, sf, B, T, ws);
   SS_CHECK_ARG(ws_bytes >= w.bytes, "ss_prodiff_sample: workspace too small");
   const int M = net->in_dim;
-  if (do_precompute) SS_PROPAGATE(precompute_cond(net, cond, lens, B, T, w, stream));
+  if (do_precompute) SS_PROPAGATE(precompute_cond(net, sf, cond, lens, B, T, w, stream));
   for (int t = n_steps - 1; t >= 0; --t) {
-    g_wset_eval = n_steps - 1 - t;
-    SS_PROPAGATE(mel_step(net, x, lens, B, T, w, t, 0.0f, 0.0f, c1[t], c2[t], t > 0 ? sigma[t] : 0.0f,
+    SS_PROPAGATE(mel_step(net, sf, x, lens, B, T, w, t, n_steps - 1 - t, 0.0f, 0.0f, c1[t], c2[t], t > 0 ? sigma[t] : 0.0f,
                           noise ? noise + (int64_t)t * B * T * M : nullptr, seed, seed_dev, (uint32_t)t, stream, 1));
   }
   return SS_OK;
@@ -1089,14 +1088,14 @@ extern "C" int ss_meldiff_sample_ddim(const ss_wavenet* net, float* x, const flo
   SS_CHECK_ARG(net && x && cond && ws && ts && alphas_cumprod && n_ts > 0, "ss_meldiff_sample_ddim: null pointer");
   SS_CHECK_ARG(net->n_groups <= 1 && net->L > 0 && net->L <= SS_MAX_LAYERS, "ss_meldiff_sample_ddim: bad net");
   SS_CHECK_ARG(eta >= 0.0f && eta <= 1.0f, "ss_meldiff_sample_ddim: eta=%g outside [0, 1]", (double)eta);
-  const WsLayout w = ws_layout(net, B, T, ws);
+  const StackForm sf = resolve_form(net, B, T);
+  const WsLayout w = ws_layout(net, sf, B, T, ws);
   SS_CHECK_ARG(ws_bytes >= w.bytes, "ss_meldiff_sample_ddim: workspace too small");
   for (int i = 0; i < n_ts; ++i)
     SS_CHECK_ARG(ts[i] >= 0 && ts[i] < net->steps && (i == 0 || ts[i] < ts[i - 1]), "ss_meldiff_sample_ddim: ts must be strictly decreasing in [0,steps)");
   const int M = net->in_dim;
-  if (do_precompute) SS_PROPAGATE(precompute_cond(net, cond, lens, B, T, w, stream));
+  if (do_precompute) SS_PROPAGATE(precompute_cond(net, sf, cond, lens, B, T, w, stream));
   for (int i = 0; i < n_ts; ++i) {
-    g_wset_eval = i;
     const int t = ts[i];
     const double ac_t = alphas_cumprod[t];
     const double ac_p = (i + 1 < n_ts) ? alphas_cumprod[ts[i + 1]] : 1.0;
@@ -1104,7 +1103,7 @@ extern "C" int ss_meldiff_sample_ddim(const ss_wavenet* net, float* x, const flo
     const double c2 = sqrt(fmax(0.0, 1.0 - ac_p - sig * sig) / (1.0 - ac_t));
     const double c1 = sqrt(ac_p) - c2 * sqrt(ac_t);
     const bool draw = eta > 0.0f;  // like p_sample, a stochastic run draws at every step (sigma = 0 on the last)
-    SS_PROPAGATE(mel_step(net, x, lens, B, T, w, t, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], (float)c1, (float)c2, (float)sig,
+    SS_PROPAGATE(mel_step(net, sf, x, lens, B, T, w, t, i, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], (float)c1, (float)c2, (float)sig,
                           (draw && noise) ? noise + (int64_t)t * B * T * M : nullptr, seed, draw ? seed_dev : nullptr, (uint32_t)t, stream));
   }
   return SS_OK;
@@ -1143,16 +1142,16 @@ extern "C" int ss_meldiff_sample_plms(const ss_wavenet* net, float* x, const flo
   SS_CHECK_ARG(net->n_groups <= 1 && net->L > 0 && net->L <= SS_MAX_LAYERS, "ss_meldiff_sample_plms: bad net");
   SS_CHECK_ARG(step_hi >= 1 && step_hi <= net->steps, "ss_meldiff_sample_plms: step_hi=%d must be in [1, steps]", step_hi);
   SS_CHECK_ARG(interval >= 1 && interval < step_hi, "ss_meldiff_sample_plms: interval=%d must be in [1, step_hi)", interval);
-  const WsLayout w = ws_layout(net, B, T, ws);
+  const StackForm sf = resolve_form(net, B, T);
+  const WsLayout w = ws_layout(net, sf, B, T, ws);
   SS_CHECK_ARG(ws_bytes >= w.bytes, "ss_meldiff_sample_plms: workspace too small");
   const int64_t n = (int64_t)B * T * net->in_dim;
   float* slot[5];
   for (int i = 0; i < 5; ++i) slot[i] = hist + i * n;  // ring of eps(x_t, t): the current one + the last 4
   float* x_pred = hist + 5 * n;
-  if (do_precompute) SS_PROPAGATE(precompute_cond(net, cond, lens, B, T, w, stream));
+  if (do_precompute) SS_PROPAGATE(precompute_cond(net, sf, cond, lens, B, T, w, stream));
   const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  int n_hist = 0, cur = 0;
-  g_wset_eval = 0;   // PLMS: evaluations counted as they come (the first step evaluates twice)
+  int n_hist = 0, cur = 0, eval = 0;   // evaluations counted as they come (the first step evaluates twice)
   const int t_first = (step_hi - 1) / interval * interval;  // reversed(range(0, K_step, interval)), shallow_diffusion_tts.py:254-260
   for (int t = t_first; t >= 0; t -= interval) {
     const int tp = t - interval > 0 ? t - interval : 0;
@@ -1162,14 +1161,12 @@ extern "C" int ss_meldiff_sample_plms(const ss_wavenet* net, float* x, const flo
     const float kx = 1.0f / (a_t_sq * (a_t_sq + a_p_sq));
     const float ke = 1.0f / (a_t_sq * (sqrtf((1.0f - a_p) * a_t) + sqrtf((1.0f - a_t) * a_p)));
     float* e0 = slot[cur];
-    SS_PROPAGATE(mel_eps(net, x, e0, lens, B, T, w, t, stream));
-    ++g_wset_eval;
+    SS_PROPAGATE(mel_eps(net, sf, x, e0, lens, B, T, w, t, eval++, stream));
     auto h = [&](int back) { return slot[(cur + 5 - back) % 5]; };
     if (n_hist == 0) {
       hipLaunchKernelGGL(plms_update_kernel, dim3(blocks), dim3(256), 0, stream, x, x_pred, e0, e0, e0, e0, 0, d, kx, ke, n);
       float* e_prev = slot[(cur + 1) % 5];  // scratch: overwritten by the next step's eps
-      SS_PROPAGATE(mel_eps(net, x_pred, e_prev, lens, B, T, w, tp, stream));
-      ++g_wset_eval;
+      SS_PROPAGATE(mel_eps(net, sf, x_pred, e_prev, lens, B, T, w, tp, eval++, stream));
       hipLaunchKernelGGL(plms_update_kernel, dim3(blocks), dim3(256), 0, stream, x, x, e0, e_prev, e0, e0, 1, d, kx, ke, n);
     } else {
       const int order = n_hist == 1 ? 2 : n_hist == 2 ? 3 : 4;
@@ -1192,11 +1189,12 @@ extern "C" int ss_f0diff_sample(const ss_wavenet* net, float* f0, int32_t* uv, c
   SS_CHECK_ARG(0 <= step_lo && step_lo <= step_hi && step_hi <= net->steps, "ss_f0diff_sample: bad step range");
   SS_CHECK_ARG(net->out_dim == 3 && net->in_dim == 1, "ss_f0diff_sample: net must be the 1->3 DDiffNet");
   SS_CHECK_ARG(net->n_groups <= 1 || (net->n_groups == 2 && B % 2 == 0), "ss_f0diff_sample: paired nets need an even item count");
-  const WsLayout w = ws_layout(net, B, T, ws);
+  const StackForm sf = resolve_form(net, B, T);
+  const WsLayout w = ws_layout(net, sf, B, T, ws);
   SS_CHECK_ARG(ws_bytes >= w.bytes, "ss_f0diff_sample: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)w.bytes);
   const int C = net->C;
   const int64_t n = (int64_t)B * T;
-  if (do_precompute) SS_PROPAGATE(precompute_cond(net, cond, lens, B, T, w, stream));
+  if (do_precompute) SS_PROPAGATE(precompute_cond(net, sf, cond, lens, B, T, w, stream));
   const int gsz = net->n_groups > 1 ? B / net->n_groups : 0;
   for (int t = step_hi - 1; t >= step_lo; --t) {
     if (t == step_hi - 1) {   // the first evaluation's input; every later one is written by the previous step's tail kernel
@@ -1204,9 +1202,9 @@ extern "C" int ss_f0diff_sample(const ss_wavenet* net, float* f0, int32_t* uv, c
                          lens, gsz, net->gs_w_in, net->gs_b_in, net->gs_uv_embed);
       SS_CHECK_LAUNCH("f0_input_kernel");
     }
-    SS_PROPAGATE(run_residual_stack(net, t, lens, B, T, w, stream, true));
-    const bool parts = skip_partials(net, w);   // the skip GEMM left its split-K slices in w.KP: the tail kernel adds them
-    const SkipSrc src = {w.G, w.KP, parts ? net->b_skipall : nullptr, parts ? w.ksplit : 1, n * C};
+    SS_PROPAGATE(run_residual_stack(net, sf, t, net->steps - 1 - t, lens, B, T, w, stream, true));
+    // partials_ok: the skip GEMM left its split-K slices in w.KP and the tail kernel adds them
+    const SkipSrc src = {w.G, w.KP, sf.partials_ok ? net->b_skipall : nullptr, sf.partials_ok ? sf.ksplit : 1, n * C};
     const int tm1 = t > 0 ? t - 1 : 0;
     const F0StepCoef k = {net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], net->post_c1[t], net->post_c2[t],
                           t > 0 ? expf(0.5f * net->post_logvar[t]) : 0.0f, net->log_alpha[t], net->log_1m_alpha[t],

@@ -403,6 +403,68 @@ def test_launch_planners_of_the_library_run_without_a_gpu():
     assert l.ss_layer512_h_elems(32, 5625) == 1408 * 128 * 256 and l.ss_layer512_h_elems(1, 1) == 128 * 256
 
 
+def _ws_net(mode, C_=256, L_=20, groups=1):
+    """An ss_wavenet descriptor of one precision mode for the size query: placeholder non-null pointers (never dereferenced there)."""
+    D = 0x1000
+    n = lib.WaveNet()
+    n.C, n.L, n.cond_dim, n.dil_cycle, n.in_dim, n.out_dim, n.steps, n.n_groups = C_, L_, 256, 4, 80, 80, 100, groups
+    n.w_skipall, n.skipall_folded = D, 1
+    if mode in ("fp32", "bf16x3"):
+        n.wino_m, n.mfma_x3 = 4, int(mode == "bf16x3")
+        for i in range(L_):
+            n.w_dil_wino[i] = n.w_dil_wino16[i] = D
+        return n
+    n.mfma_bf16, n.w_skipall_h, n.w_cond_h = 1, D, D
+    for i in range(L_):
+        n.w_dil_h[i] = n.w_out_h[i] = D
+    if mode != "bf16":
+        n.mfma_split, n.mfma_products = 1 if mode == "bf16x2" else 2, 1 if mode == "fp16sd" else 2
+    if mode in ("fp16x2", "fp16sd"):
+        for i in range(L_):
+            n.w_dil_f[i] = n.w_out_f[i] = D
+    if mode == "fp16sd":
+        n.n_wsets, n.n_esets, n.w_skipall_c = 32, 8, D
+    if mode == "fp16q4":
+        n.q_scale_gate = 1.0
+        for i in range(L_):
+            n.w_dil_q[i] = D
+    return n
+
+
+def test_workspace_bytes_of_every_stack_form_are_pinned():
+    """ss_wavenet_workspace_bytes without a device (256 CUs) for every precision mode at a launch-bound, a mid and the fused-form shape, the f0
+    pair, and every knob that changes the stack's form: the resolved form and the workspace layout stay what they were (integers recorded from
+    the library before the form was resolved in one place)."""
+    import ctypes
+    l = lib.load()
+
+    def ws(n, B, T):
+        return l.ss_wavenet_workspace_bytes(ctypes.byref(n), B, T)
+    want = {"fp32": (84946944, 1296236544, 11629494272), "bf16x3": (53489664, 792920064, 11629494272), "bf16": (42479616, 679673856, 9968549888),
+            "bf16x2": (50343936, 805502976, 11814043648), "fp16x2": (50343936, 805502976, 17627348992), "fp16q4": (50343936, 805502976, 11814043648),
+            "fp16sd": (50343936, 805502976, 39773274112)}
+    for mode, sizes in want.items():
+        assert tuple(ws(_ws_net(mode), B, T) for B, T in ((1, 768), (8, 1536), (32, 5632))) == sizes, mode
+    assert ws(_ws_net("fp32", 192, 10, 2), 16, 1536) == 1000734720
+    assert ws(_ws_net("fp32"), 0, 768) == -1
+
+    def with_knob(key, val, n, B, T):
+        before = l.ss_get_tuning(key)
+        assert l.ss_set_tuning(key, val) == 0
+        try:
+            return ws(n, B, T)
+        finally:
+            assert l.ss_set_tuning(key, before) == 0
+    assert with_knob(b"gate16", 0, _ws_net("fp32"), 8, 1536) == 792920064 and with_knob(b"gate16", 3, _ws_net("fp32"), 8, 1536) == 1296236544
+    assert with_knob(b"gate16_ks", 0, _ws_net("fp32"), 1, 768) == 84946944
+    assert with_knob(b"layer512", 0, _ws_net("fp16x2"), 32, 5632) == 11814043648 and with_knob(b"layer512", 0, _ws_net("fp16sd"), 32, 5632) == 11814043648
+    assert with_knob(b"gate256", 0, _ws_net("fp16sd"), 32, 5632) == 41618767872
+    no_esets = _ws_net("fp16sd")
+    no_esets.n_esets = 0
+    assert ws(no_esets, 32, 5632) == 17627348992
+    assert with_knob(b"layer512", 2, _ws_net("fp16x2"), 1, 768) == 82980864 and with_knob(b"layer512", 2, _ws_net("fp16sd"), 1, 768) == 177352704
+
+
 def test_gate128_index_math_against_a_tagged_lds_image(tmp_path):
     """gate128_kernel (the fp16x2 gate on 256 x 128 tiles, two workgroups per CU) takes all of its DMA / fragment / epilogue addresses from
     stylesinger_amd/csrc/gate128_layout.h; tools/layout_check_gate128.cpp compiles the SAME header on the host, replays every LDS-DMA piece
