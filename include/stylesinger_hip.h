@@ -135,7 +135,7 @@ typedef struct ss_conv_gemm_args {
   int32_t Nh; /* RESSKIP split point */
   /* DDPM epilogue (C is x_t in/out, [B][T][N]) */
   float ddpm_recip, ddpm_recipm1, ddpm_c1, ddpm_c2, ddpm_sigma;
-  const float* noise; /* [B][T][N] or NULL -> Philox(seed, step) */
+  const float* noise; /* [B][T][N] or NULL -> Philox(seed, step). The counter layout of every draw site is restated in oracle/philox.py. */
   uint64_t seed;
   const uint64_t* seed_dev; /* optional device word added to `seed` at run time (keeps hipGraph replays fresh) */
   uint32_t step;

@@ -125,7 +125,8 @@ __device__ __forceinline__ float ss_apply_act(float v, int act, float slope) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// Philox4x32-10 counter RNG (production noise; parity tests inject a tape instead).
+// Philox4x32-10 counter RNG (production noise; parity tests inject a tape instead). Pinned by tests/test_noise_cpu.py (Random123 known
+// answers, through the host restatement oracle/philox.py) and tests/test_gpu_noise.py (every draw site against that restatement).
 // ----------------------------------------------------------------------------------------------
 struct SsPhilox {
   uint32_t k0, k1;
@@ -171,6 +172,20 @@ __device__ __forceinline__ void ss_mel_draw4(const SsPhilox& rng, uint32_t t4, u
   rng.gen(t4 * N + n, b, step, 0x4d454c44u, o);
   ss_boxmuller(o[0], o[1], z[0], z[1]);
   ss_boxmuller(o[2], o[3], z[2], z[3]);
+}
+
+// One posterior update of the mel sampler, shared by its two launch forms (SS_EPI_DDPM epilogue, mel_tail_kernel) so that both round alike:
+//   x0 = clamp(fl(recip x) - fl(recipm1 eps), -1, 1)  (or eps itself: x0-prediction) ; mean = fma(c1, x0, fl(c2 x)) ; x <- fl(mean + fl(sigma z)).
+// Left to the compiler's multiply-add contraction the two translation units chose different fusions (the tail kernel differed from the epilogue
+// by up to 4 ulp after 16 steps at eps = 0); the roundings are spelled out here as the epilogue has always had them, so its results are unchanged.
+__device__ __forceinline__ float ss_ddpm_update(float x, float eps, float recip, float recipm1, float c1, float c2, float sigma, float z, int x0_pred) {
+#pragma clang fp contract(off)
+  const float a = recip * x, b = recipm1 * eps;
+  float x0 = fminf(fmaxf(a - b, -1.0f), 1.0f);
+  if (x0_pred) x0 = eps;  // the network output IS x0 (ProDiffusion.p_sample, prodiff.py:150-153), no clamp
+  const float c2x = c2 * x, sz = sigma * z;
+  const float mean = __builtin_fmaf(c1, x0, c2x);
+  return mean + sz;
 }
 
 // SS_TRACE (debug builds only, tools/wave_trace.py): phase stamps on the shader clock. SS_CLK waits for the LDS/scalar queue (lgkmcnt 0),

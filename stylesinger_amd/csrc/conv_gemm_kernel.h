@@ -590,12 +590,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_gemm_kernel(const
           const int row = row_of(m, r);
           if (!col_ok || row >= a.T) continue;
           const float eps = acc[m][n][r] + bs;
-          const float x = xv[r];
-          float x0 = a.ddpm_recip * x - a.ddpm_recipm1 * eps;
-          x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-          if (a.ddpm_x0_pred) x0 = eps;  // the network output IS x0 (ProDiffusion.p_sample, prodiff.py:150-153), no clamp
-          const float mean = a.ddpm_c1 * x0 + a.ddpm_c2 * x;
-          float xn = mean + a.ddpm_sigma * zv[r];
+          float xn = ss_ddpm_update(xv[r], eps, a.ddpm_recip, a.ddpm_recipm1, a.ddpm_c1, a.ddpm_c2, a.ddpm_sigma, zv[r], a.ddpm_x0_pred);
           if (a.mask_rows && row >= len) xn = 0.f;
           Cb[(int64_t)row * a.ldc + col] = xn;
         }

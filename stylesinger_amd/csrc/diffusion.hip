@@ -919,9 +919,6 @@ __global__ __launch_bounds__(256) void mel_tail_kernel(const SkipSrc src, const 
     const float eps = acc + bf[n];
     const int b = (int)(i / T), t = (int)(i % T);
     const float xv = x[i * M + n];
-    float x0 = recip * xv - recipm1 * eps;
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float mean = c1 * x0 + c2 * xv;
     float z = 0.f;
     if (sigma != 0.f) {
       if (noise) z = noise[i * M + n];
@@ -931,7 +928,7 @@ __global__ __launch_bounds__(256) void mel_tail_kernel(const SkipSrc src, const 
         z = z4[t & 3];
       }
     }
-    float xn = mean + sigma * z;
+    float xn = ss_ddpm_update(xv, eps, recip, recipm1, c1, c2, sigma, z, 0);   // the epilogue's update, rounding for rounding
     if (lens && t >= lens[b]) xn = 0.f;
     x[i * M + n] = xn;
     xs[row * Kp_in + n] = xn;
