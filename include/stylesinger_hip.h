@@ -818,6 +818,16 @@ int ss_round_f16_rows(const float* x, int64_t ldx, int Lx, const int32_t* n_in, 
  * out [B][out_stride] <- the kept windows back to back, zeros behind; out_lens[b] = kept samples; win_dst [B][max_windows] int32 scratch. */
 int ss_vad_trim(const float* wav, int64_t wav_stride, const int32_t* n_samples, const uint8_t* flags, int flags_stride, int B, int max_windows,
                 int samples_per_window, int avg_width, int max_silence, float* out, int64_t out_stride, int32_t* out_lens, int32_t* win_dst, void* stream);
+/* Polyphase sample-rate conversion by up / down (reduced sr_out / sr_in): what `librosa.core.load(path, sr=audio_sample_rate)` does to a file of
+ * another rate (utils/audios/__init__.py:52; resampy's `kaiser_best` windowed sinc - un-vendored: parity UNPINNED, `stylesinger_amd/resample.py`
+ * holds the definition and builds the bank). Output t of item b sits at input position t * down / up = n + p / up (64-bit integers):
+ *   y[b][t] = sum_{j < taps} bank[p][j] * xz[b][n - left + j]   for t < min(n_out_computed[b], n_out[b]),   0 for the other columns up to Ly,
+ * xz = x[b] inside [0, n_in[b]) and zero outside (what the buffer holds past n_in[b] is padding and never read into a sum). bank [up][taps] fp32,
+ * row p = the filter of phase p. n_out[b] (>= n_out_computed[b]: librosa's fix_length may append one zero sample) may be NULL. fp32 FMA over j in
+ * ascending order, no atomics: an item's samples do not depend on B, Lx, Ly or the other items. up <= 4096, down + taps <= 16000 (the staged input
+ * span of a workgroup is kept within 64 KiB of LDS). No allocation: graph-capturable. */
+int ss_resample_poly(const float* x, int64_t ldx, int Lx, const int32_t* n_in, float* y, int64_t ldy, int Ly, const int32_t* n_out_computed,
+                     const int32_t* n_out, int B, const float* bank, int up, int down, int taps, int left, void* stream);
 
 /* Emotion encoder (input producer; data_gen/tts/emotion/model.py:11-78 = nn.LSTM(40, 256, 3) + Linear, inference.py:39-53,
  * 139-151). One LSTM layer's recurrence as a persistent launch (one workgroup per sequence):

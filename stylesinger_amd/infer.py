@@ -249,6 +249,31 @@ class StyleSingerInfer:
         frames, counts = self._partials_batch(wavs, lens, lambda n: spk_slices(n, rate, min_coverage))
         return self._mean_l2norm_per_item(self.speaker_encoder.forward(frames), counts)
 
+    def _resample_refs(self, ref_wavs, ref_lens, ref_srs):
+        """`librosa.core.load(..., sr=audio_sample_rate)`'s resampling for a batch with per-item rates: the items are grouped by rate, each group
+        of another rate goes through `resample_batch` (one launch), and the results are scattered back in order. -> ([B, max new length] fp32,
+        zero beyond each item's length; the new lengths as host ints)."""
+        from .resample import out_len, resample_batch
+        sr = int(self.hparams["audio_sample_rate"])
+        srs = [int(r) for r in ref_srs]
+        if len(srs) != ref_wavs.shape[0]:
+            raise ValueError(f"preprocess_batch: {len(srs)} ref_srs for {ref_wavs.shape[0]} items")
+        new_lens = [out_len(n, r, sr) for n, r in zip(ref_lens, srs)]
+        out = torch.zeros(ref_wavs.shape[0], max(new_lens), device=ref_wavs.device, dtype=torch.float32)
+        for rate in sorted(set(srs)):
+            idx = [b for b, r in enumerate(srs) if r == rate]
+            lens = [ref_lens[b] for b in idx]
+            if rate == sr:
+                sub, width = ref_wavs[idx], max(lens)
+            else:
+                sub, _ = resample_batch(ref_wavs[idx][:, :max(1, max(lens))], lens, rate, sr)
+                width = sub.shape[1]
+            out[idx, :width] = sub[:, :width]
+        for b, n in enumerate(new_lens):   # an item at the model's rate keeps its samples; what the buffer held past them is padding
+            if srs[b] == sr:
+                out[b, n:] = 0
+        return out, new_lens
+
     def process_audio_wav(self, ref_wavs, frames, valid_lens=None):
         """The waveform `process_audio` returns next to the mel (inference/StyleSinger.py:86-88): the audio zero-padded to
         n_mel * hop samples (utils/audios/__init__.py:76-78) and rounded to float16. -> ([B, max n_mel * hop] fp32 holding
@@ -269,10 +294,13 @@ class StyleSingerInfer:
 
     @torch.no_grad()
     def preprocess_batch(self, ref_wavs, ref_lens, spk_embed, f0_hz, txt_tokens, note, note_dur, note_type, mel2ph=None,
-                         emo_embed=None, emo_wavs=None, emo_lens=None, emo_vad_flags=None):
+                         emo_embed=None, emo_wavs=None, emo_lens=None, emo_vad_flags=None, ref_srs=None):
         """Batched device form of `preprocess_input` + `input_to_batch` (inference/StyleSinger.py:94-172): from reference audio to
         the dict `infer_batch` takes, with no host round trip of the data.
-          ref_wavs [B, L] fp32 48 kHz reference audio (zero beyond ref_lens[b]; ref_lens host ints)   -> ref_mels  (process_audio, :106-118)
+          ref_wavs [B, L] fp32 reference audio (zero beyond ref_lens[b]; ref_lens host ints)          -> ref_mels  (process_audio, :106-118)
+                   at the model's sample rate, or at the per-item rates `ref_srs` (host ints): items of another rate are resampled on the
+                   device first, as `librosa.core.load(path, sr=audio_sample_rate)` does (utils/audios/__init__.py:52; `resample.py`, parity
+                   UNPINNED), one launch per distinct rate; None or all equal to the model's rate = no resampling
           f0_hz    [B, Tr] tracker contour in Hz aligned to the mel frames (align_f0_to_mel), 0 = unvoiced -> ref_f0 (norm_interp_f0, :152);
                    None -> tracked on the device from `process_audio`'s waveform as :112-135 does with parselmouth (`f0track.py`: Praat's
                    published autocorrelation method, 80-800 Hz, voicing threshold 0.6; parity UNPINNED - parselmouth is un-vendored)
@@ -294,6 +322,8 @@ class StyleSingerInfer:
             self._mel_frontend = MelFrontendHIP(self._front_hparams, device=d)
         ref_lens_h = [int(v) for v in ref_lens]
         ref_wavs = ref_wavs.to(d).float()
+        if ref_srs is not None and any(int(r) != int(self.hparams["audio_sample_rate"]) for r in ref_srs):
+            ref_wavs, ref_lens_h = self._resample_refs(ref_wavs, ref_lens_h, ref_srs)
         ref_mels, frames = self._mel_frontend.wav2mel(ref_wavs, torch.tensor(ref_lens_h, dtype=torch.int64))
         Tr = ref_mels.shape[1]
         hop = int(self.hparams["hop_size"])
@@ -362,8 +392,8 @@ class StyleSingerInfer:
 
     @staticmethod
     def _load_wav(path, want_sr):
-        """A reference-audio FILE: 16-bit PCM WAV at the model's sample rate (the reference resamples through librosa, un-vendored: other rates
-        are refused, not approximated). -> float32 mono in [-1, 1)."""
+        """The strict static loader: a 16-bit PCM WAV at exactly `want_sr` Hz -> float32 mono in [-1, 1); anything else is a ValueError.
+        (`preprocess_input` reads files through `audiofile.load_audio` + `resample.resample_batch`, which take other formats and rates.)"""
         import wave
         with wave.open(os.fsdecode(path), "rb") as wf:
             if wf.getsampwidth() != 2 or wf.getframerate() != want_sr:
@@ -397,25 +427,37 @@ class StyleSingerInfer:
         """`preprocess_input` + `input_to_batch` (inference/StyleSinger.py:94-172) for ONE item with every producer on the device: the dict
         `infer_batch` takes, device tensors only (+ `ref_f0_hz`, `n_mel`). ONE pass of the f0 tracker."""
         sr, hop = int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])
-        audio = inp["ref_audio"]
-        wav = self._load_wav(audio, sr) if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__") else np.asarray(audio, dtype=np.float32)
+        audio, in_sr = inp["ref_audio"], int(inp.get("ref_sr") or sr)
+        if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__"):
+            from .audiofile import load_audio
+            wav, in_sr = load_audio(audio)
+        elif isinstance(audio, (tuple, list)) and len(audio) == 2 and np.ndim(audio[1]) == 0 and np.ndim(audio[0]) == 1:
+            wav, in_sr = np.asarray(audio[0], dtype=np.float32), int(audio[1])       # (waveform, sample_rate)
+        else:
+            wav = np.asarray(audio, dtype=np.float32)
+        ref, n = torch.from_numpy(np.ascontiguousarray(wav))[None], len(wav)
+        if in_sr != sr:   # librosa.core.load(wav_path, sr=audio_sample_rate) (utils/audios/__init__.py:52): the samples go to the device once
+            from .resample import resample_batch
+            ref, (n,) = resample_batch(ref.to(self.device), [n], in_sr, sr)
         if "ph_token" not in inp:
             if self.ph_encoder is None:
                 raise ValueError("preprocess_input: give inp['ph_token'], construct StyleSingerInfer(..., phone_set=<phone_set.json>) or set "
                                  "self.ph_encoder (the reference's build_token_encoder(f'{processed_data_dir}/phone_set.json'))")
             inp["ph_token"] = self.ph_encoder.encode(" ".join(inp["ph"]))
         t = lambda x, dt: torch.as_tensor(np.asarray(x), dtype=dt)[None]
-        batch = self.preprocess_batch(torch.from_numpy(wav)[None], [len(wav)], None, None, t(inp["ph_token"], torch.long), t(inp["note"], torch.long),
+        batch = self.preprocess_batch(ref, [n], None, None, t(inp["ph_token"], torch.long), t(inp["note"], torch.long),
                                       t(inp["note_dur"], torch.float32), t(inp["note_type"], torch.long),
                                       mel2ph=t(inp["mel2ph"], torch.long) if "mel2ph" in inp else None, emo_vad_flags=self._resolve_vad(vad_flags))
-        batch["n_mel"] = len(wav) // hop + 1
+        batch["n_mel"] = n // hop + 1
         return batch
 
     @torch.no_grad()
     def preprocess_input(self, inp, vad_flags=None):
         """Mirror of `StyleSingerInfer.preprocess_input` (inference/StyleSinger.py:94-137) with every producer on the device: fills `mel`,
         `spk_embed`, `emo_embed`, `f0` (the tracker's contour in Hz on the mel grid) as numpy arrays, `ph_token`, and `item_name` / `wav_fn` from
-        `inp['ref_audio']` (a float waveform at the model's sample rate, or the path of a 16-bit PCM WAV at that rate). Needs `emotion_state` and
+        `inp['ref_audio']`: the path of a WAV file (`audiofile.load_audio`: PCM or float, any channel count, any sample rate), a float waveform at
+        `inp['ref_sr']` Hz (default: the model's sample rate) or a `(waveform, sample_rate)` pair; audio of another rate is resampled on the device as
+        `librosa.core.load(wav_path, sr=audio_sample_rate)` does (`resample.py`; parity with librosa UNPINNED). Needs `emotion_state` and
         `speaker_state` (the two encoders' checkpoints). `vad_flags`: see `_resolve_vad` (None = webrtcvad on the host, False = opt out)."""
         batch = self._device_batch(inp, vad_flags)
         n_mel, audio = batch["n_mel"], inp["ref_audio"]
