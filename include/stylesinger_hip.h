@@ -712,6 +712,13 @@ int ss_f0_bounds(const int64_t* midi, float* lo, float* hi, int n, void* stream)
 int ss_pitch_post(const float* f0_a, const int32_t* uv_a, const float* f0_b, const int32_t* uv_b, const int64_t* midi,
                   const int64_t* mel2ph, float* pitch_pred /*[n][2]*/, float* f0_denorm, int64_t* pitch_coarse, int n,
                   void* stream);
+/* The same post-processing for a GIVEN contour (forward(f0=, uv=): the reference's `use_gt_f0` test step, tasks/StyleSinger/stylesinger.py:176-188;
+ * the f0 is not None branch of modules/StyleSinger/stylesinger.py:230-241 with :301-311, utils/pitch_utils.py denorm_f0 / f0_to_coarse). Per frame:
+ *   pitch_pred = (f0/2 + f0/2, uv/2 + uv/2) ; hz = exp2f(f0), 0 where uv > 0 or mel2ph == 0 ; coarse = f0_to_coarse(hz), the code ss_pitch_post runs.
+ * f0_log2 [n] = log2 Hz interpolated through unvoiced frames (norm_interp_f0), uv [n] fp32 (> 0 = unvoiced). The note-rest rule of the predicted
+ * branch (uv[midi == 0] = 1, :288,296) is NOT applied: the reference does not apply it to a given contour. */
+int ss_pitch_given(const float* f0_log2, const float* uv, const int64_t* mel2ph, float* pitch_pred /*[n][2]*/, float* f0_denorm,
+                   int64_t* pitch_coarse, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * HiFi-GAN-NSF vocoder (modules/hifigan/hifigan_nsf.py:105-169, modules/parallel_wavegan/models/source.py:311-531)
@@ -828,6 +835,16 @@ int ss_vad_trim(const float* wav, int64_t wav_stride, const int32_t* n_samples, 
  * span of a workgroup is kept within 64 KiB of LDS). No allocation: graph-capturable. */
 int ss_resample_poly(const float* x, int64_t ldx, int Lx, const int32_t* n_in, float* y, int64_t ldy, int Ly, const int32_t* n_out_computed,
                      const int32_t* n_out, int B, const float* bank, int up, int down, int taps, int left, void* stream);
+
+/* A pitch contour in Hz fitted to a score's frame count (input producer of forward(pitch_hz=...); definition: `contour_fit` in
+ * stylesinger_amd/pitch.py). f0_hz [B][ldc], lens_c[b] <= Lc valid source frames (0 = unvoiced); out [B][ldo], T columns written; lens_t[b] <= T
+ * target frames per item - a DEVICE array, e.g. what ss_length_regulate wrote, so the fit needs no host sync. Output frame t < lens_t[b] sits at
+ * source position s = (t + 0.5) * lens_c / lens_t - 0.5 clamped to [0, lens_c - 1]: voiced iff the NEAREST source frame is voiced (a tie goes to the
+ * later one); value = log2-linear interpolation of the two neighbours when both are voiced, else the nearest frame's value; times
+ * 2^(shift_semitones / 12), |shift| <= 48. An integer s takes the source sample itself: with shift 0, lens_c == lens_t is a bit-exact copy.
+ * Unvoiced frames and frames >= lens_t[b] are written as 0. One thread per output frame, no atomics, independent of the batch. Graph-capturable. */
+int ss_contour_fit(const float* f0_hz, int64_t ldc, int Lc, const int32_t* lens_c, const int32_t* lens_t, float shift_semitones, float* out,
+                   int64_t ldo, int T, int B, void* stream);
 
 /* Emotion encoder (input producer; data_gen/tts/emotion/model.py:11-78 = nn.LSTM(40, 256, 3) + Linear, inference.py:39-53,
  * 139-151). One LSTM layer's recurrence as a persistent launch (one workgroup per sequence):

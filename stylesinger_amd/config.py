@@ -51,6 +51,8 @@ DEFAULT_HPARAMS = dict(
     fp16sd_e_sets=8,   # fp16sd: the conditioner addend slab of the fused layer launch as this many fp16 sigma-delta sets (0 = fp32 slab)
     # ProDiff decoder (hparams['decoder'] == 'prodiff', egs/stylesinger.yaml:145-155): timesteps = 8 teacher steps there
     timescale=1, pndm_speedup=None,
+    # the test step hands sample['f0'] / sample['uv'] to the model (tasks/StyleSinger/stylesinger.py:180-182): infer_batch_to_files
+    use_gt_f0=False,
     # not a reference key: frame bucket of the hipGraph / plan cache (StyleSingerHIP.t_bucket)
     t_bucket=64,
 )

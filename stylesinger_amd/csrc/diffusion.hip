@@ -818,6 +818,18 @@ __global__ void f0_bounds_kernel(const int64_t* __restrict__ midi, float* __rest
   hi[i] = nb(m + 3.0f);
 }
 
+// f0_to_coarse (utils/pitch_utils.py:22-31): Hz -> pitch embedding row; shared by the predicted and the given-contour kernels
+__device__ __forceinline__ int64_t f0_to_coarse(float hz) {
+  // utils/pitch_utils.py:17-18: numpy float64 constants, cast to fp32 when they meet the tensor
+  const float f0_mel_min = (float)77.75496616579426;          // 1127*ln(1+50/700)
+  const float f0_mel_span = (float)986.6532669978451;         // 1127*ln(1+1100/700) - f0_mel_min
+  float mel = 1127.0f * logf(1.0f + hz / 700.0f);
+  if (mel > 0.0f) mel = (mel - f0_mel_min) * 254.0f / f0_mel_span + 1.0f;
+  if (mel <= 1.0f) mel = 1.0f;
+  if (mel > 255.0f) mel = 255.0f;
+  return (int64_t)(mel + 0.5f);
+}
+
 // merge of the two predictors + denorm + coarse (stylesinger.py:230-246,286-311; pitch_utils.py:22-31,65-78)
 __global__ void pitch_post_kernel(const float* __restrict__ f0_a, const int32_t* __restrict__ uv_a,
                                   const float* __restrict__ f0_b, const int32_t* __restrict__ uv_b,
@@ -838,15 +850,25 @@ __global__ void pitch_post_kernel(const float* __restrict__ f0_a, const int32_t*
   if (u > 0.0f) hz = 0.0f;
   if (mel2ph[i] == 0) hz = 0.0f;
   f0_denorm[i] = hz;
-  // f0_to_coarse
-  // utils/pitch_utils.py:17-18: numpy float64 constants, cast to fp32 when they meet the tensor
-  const float f0_mel_min = (float)77.75496616579426;          // 1127*ln(1+50/700)
-  const float f0_mel_span = (float)986.6532669978451;         // 1127*ln(1+1100/700) - f0_mel_min
-  float mel = 1127.0f * logf(1.0f + hz / 700.0f);
-  if (mel > 0.0f) mel = (mel - f0_mel_min) * 254.0f / f0_mel_span + 1.0f;
-  if (mel <= 1.0f) mel = 1.0f;
-  if (mel > 255.0f) mel = 255.0f;
-  coarse[i] = (int64_t)(mel + 0.5f);
+  coarse[i] = f0_to_coarse(hz);
+}
+
+// A GIVEN contour instead of the two predictors (the f0 is not None branch of stylesinger.py:230-241 with add_gmdiff_pitch's :301-311: both
+// "predictors" return cat(f0, uv) unchanged, so pitch_pred = (f0/2 + f0/2, uv/2 + uv/2)); then denorm_f0 + f0_to_coarse as above. The note-rest rule
+// (uv[midi == 0] = 1, :288,296) sits in the predicted branch only: the reference does not apply it to a given contour, and neither does this kernel.
+__global__ void pitch_given_kernel(const float* __restrict__ f0_log2, const float* __restrict__ uv, const int64_t* __restrict__ mel2ph,
+                                   float* __restrict__ pitch_pred, float* __restrict__ f0_denorm, int64_t* __restrict__ coarse, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float f = f0_log2[i] / 2.0f + f0_log2[i] / 2.0f;
+  const float u = uv[i] / 2.0f + uv[i] / 2.0f;
+  pitch_pred[(int64_t)i * 2 + 0] = f;
+  pitch_pred[(int64_t)i * 2 + 1] = u;
+  float hz = exp2f(f);
+  if (u > 0.0f) hz = 0.0f;
+  if (mel2ph[i] == 0) hz = 0.0f;
+  f0_denorm[i] = hz;
+  coarse[i] = f0_to_coarse(hz);
 }
 
 inline int grid_for(int64_t n) {
@@ -1250,5 +1272,15 @@ extern "C" int ss_pitch_post(const float* f0_a, const int32_t* uv_a, const float
   hipLaunchKernelGGL(pitch_post_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, f0_a, uv_a, f0_b, uv_b,
                      midi, mel2ph, pitch_pred, f0_denorm, pitch_coarse, n);
   SS_CHECK_LAUNCH("ss_pitch_post");
+  return SS_OK;
+}
+
+extern "C" int ss_pitch_given(const float* f0_log2, const float* uv, const int64_t* mel2ph, float* pitch_pred, float* f0_denorm,
+                              int64_t* pitch_coarse, int n, void* stream) {
+  SS_CHECK_ARG(f0_log2 && uv && mel2ph && pitch_pred && f0_denorm && pitch_coarse, "ss_pitch_given: null pointer");
+  SS_CHECK_ARG(n > 0, "ss_pitch_given: n=%d must be positive", n);
+  hipLaunchKernelGGL(pitch_given_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, f0_log2, uv, mel2ph, pitch_pred,
+                     f0_denorm, pitch_coarse, n);
+  SS_CHECK_LAUNCH("ss_pitch_given");
   return SS_OK;
 }

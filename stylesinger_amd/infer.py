@@ -95,12 +95,16 @@ class StyleSingerInfer:
     @torch.no_grad()
     def infer_batch(self, batch, noise=None, vocoder_noise=None, seed=None, vocode=True, plan_slot=0):
         """batch: dict of device tensors (txt_tokens, note, note_dur, note_type, spk_embed, emo_embed, ref_mels,
-        ref_f0, optional mel2ph).  Returns dict(mel [B,T,80], f0 [B,T], lens int32 [B], wav [B,T*hop])."""
+        ref_f0, optional mel2ph).  Returns dict(mel [B,T,80], f0 [B,T], lens int32 [B], wav [B,T*hop]).
+        Pitch control (StyleSingerHIP.forward): optional `f0` + `uv` [B, T] (the normalised contour, the reference's use_gt_f0 form), or
+        `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
+        pitch = {k: batch[k] for k in ("pitch_hz", "pitch_shift") if batch.get(k) is not None}
         out = self.model(batch["txt_tokens"], mel2ph=batch.get("mel2ph"), spk_embed=batch["spk_embed"], emo_embed=batch["emo_embed"],
-                         ref_mels=batch["ref_mels"], ref_f0=batch["ref_f0"], global_steps=320000, infer=True, note=batch["note"],
-                         note_dur=batch["note_dur"], note_type=batch["note_type"], noise=noise, seed=seed, plan_slot=plan_slot)
+                         ref_mels=batch["ref_mels"], ref_f0=batch["ref_f0"], f0=batch.get("f0"), uv=batch.get("uv"), global_steps=320000,
+                         infer=True, note=batch["note"], note_dur=batch["note_dur"], note_type=batch["note_type"], noise=noise, seed=seed,
+                         plan_slot=plan_slot, **pitch)
         res = dict(mel=out["mel_out"], f0=out["f0_denorm"], lens=out["lens"], model_out=out)
         if vocode:
             res["wav"] = self.vocode(out["mel_out"], out["f0_denorm"], out["lens"], noise=vocoder_noise, seed=seed + 101)
@@ -165,8 +169,11 @@ class StyleSingerInfer:
     def infer_batch_to_files(self, batch, names, writer, seed=None):
         """Batched form of the reference's test step + after_infer (tasks/StyleSinger/stylesinger.py:186-275), which
         is limited to batch size 1: run the batch, vocode it, quantise to PCM16 on the device, crop each item to its own
-        frame count and queue the files on `writer` (a writer.WavWriter)."""
+        frame count and queue the files on `writer` (a writer.WavWriter). As there (:180-182), the batch's ground-truth `f0` / `uv` are handed
+        to the model only with hparams['use_gt_f0']; otherwise the f0 is predicted, whatever the dataset batch carries."""
         from .writer import wav_to_pcm16
+        if not (self.hparams.get("use_gt_f0") and batch.get("f0") is not None and batch.get("uv") is not None):
+            batch = {k: v for k, v in batch.items() if k not in ("f0", "uv")}
         res = self.infer_batch(batch, seed=seed)
         self.model.check_finite(res["model_out"])
         hop = self.vocoder.model.hop
@@ -374,7 +381,7 @@ class StyleSingerInfer:
                     spk_embed=t(item["spk_embed"], torch.float32), emo_embed=t(item["emo_embed"], torch.float32),
                     note=t(item["note"], torch.long), note_dur=t(item["note_dur"], torch.float32),
                     note_type=t(item["note_type"], torch.long), ref_f0=f0[None].to(d),
-                    **({"mel2ph": t(item["mel2ph"], torch.long)} if "mel2ph" in item else {}))
+                    **({"mel2ph": t(item["mel2ph"], torch.long)} if "mel2ph" in item else {}), **self._pitch_inputs(item))
 
     def _wav_from_result(self, res, vocoder_noise=None):
         """inference/StyleSinger.py:53-63: drop all-zero frames, clip the mel, vocode with the predicted f0 (one item)."""
@@ -449,7 +456,44 @@ class StyleSingerInfer:
                                       t(inp["note_dur"], torch.float32), t(inp["note_type"], torch.long),
                                       mel2ph=t(inp["mel2ph"], torch.long) if "mel2ph" in inp else None, emo_vad_flags=self._resolve_vad(vad_flags))
         batch["n_mel"] = n // hop + 1
+        batch.update(self._pitch_inputs(inp))
         return batch
+
+    def _pitch_inputs(self, inp):
+        """The pitch-control entries of `inp` as `infer_batch` takes them: inp['pitch_hz'] (a 1-D contour in Hz at the mel hop, 0 = unvoiced) or
+        inp['pitch_audio'] (a WAV path or a (waveform, sample_rate) pair: a guide vocal, resampled like `ref_audio` and tracked on the device as
+        `preprocess_batch` tracks the reference audio, 80-800 Hz), and inp['pitch_shift'] (semitones). -> {} when `inp` has none of them."""
+        if inp.get("pitch_hz") is not None and inp.get("pitch_audio") is not None:
+            raise ValueError("preprocess_input: give inp['pitch_hz'] or inp['pitch_audio'], not both")
+        out = {}
+        if inp.get("pitch_hz") is not None:
+            hz = torch.as_tensor(np.asarray(inp["pitch_hz"], dtype=np.float32))
+            if hz.dim() != 1 or hz.numel() == 0:
+                raise ValueError(f"preprocess_input: inp['pitch_hz'] must be a non-empty 1-D contour in Hz (got shape {tuple(hz.shape)})")
+            out["pitch_hz"] = (hz[None].to(self.device), [hz.numel()])
+        elif inp.get("pitch_audio") is not None:
+            from .f0track import track_f0_device
+            sr, hop = int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])
+            audio = inp["pitch_audio"]
+            if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__"):
+                from .audiofile import load_audio
+                wav, in_sr = load_audio(audio)
+            elif isinstance(audio, (tuple, list)) and len(audio) == 2 and np.ndim(audio[1]) == 0 and np.ndim(audio[0]) == 1:
+                wav, in_sr = np.asarray(audio[0], dtype=np.float32), int(audio[1])
+            else:
+                raise ValueError("preprocess_input: inp['pitch_audio'] must be a WAV path or a (waveform, sample_rate) pair")
+            gv, n = torch.from_numpy(np.ascontiguousarray(wav))[None].to(self.device), len(wav)
+            if in_sr != sr:
+                from .resample import resample_batch
+                gv, (n,) = resample_batch(gv, [n], in_sr, sr)
+            n_mel = n // hop + 1
+            wav16, wav16_lens = self.process_audio_wav(gv, [n_mel], [n])
+            out["pitch_hz"] = (track_f0_device(wav16, wav16_lens, n_mel, sr=sr, hop_size=hop), [n_mel])
+        if inp.get("pitch_shift") is not None:
+            if "pitch_hz" not in out:
+                raise ValueError("preprocess_input: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
+            out["pitch_shift"] = float(inp["pitch_shift"])
+        return out
 
     @torch.no_grad()
     def preprocess_input(self, inp, vad_flags=None):
@@ -458,12 +502,17 @@ class StyleSingerInfer:
         `inp['ref_audio']`: the path of a WAV file (`audiofile.load_audio`: PCM or float, any channel count, any sample rate), a float waveform at
         `inp['ref_sr']` Hz (default: the model's sample rate) or a `(waveform, sample_rate)` pair; audio of another rate is resampled on the device as
         `librosa.core.load(wav_path, sr=audio_sample_rate)` does (`resample.py`; parity with librosa UNPINNED). Needs `emotion_state` and
-        `speaker_state` (the two encoders' checkpoints). `vad_flags`: see `_resolve_vad` (None = webrtcvad on the host, False = opt out)."""
+        `speaker_state` (the two encoders' checkpoints). `vad_flags`: see `_resolve_vad` (None = webrtcvad on the host, False = opt out).
+        Pitch control (`_pitch_inputs`): `inp['pitch_hz']` / `inp['pitch_shift']` pass through; `inp['pitch_audio']` (a guide vocal) is tracked
+        on the device and replaced by its contour in `inp['pitch_hz']`."""
         batch = self._device_batch(inp, vad_flags)
         n_mel, audio = batch["n_mel"], inp["ref_audio"]
         inp.update(item_name=inp.get("name"), wav_fn=os.fsdecode(audio) if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__") else None,
                    mel=batch["ref_mels"][0, :n_mel].cpu().numpy(), spk_embed=batch["spk_embed"][0].cpu().numpy(),
                    emo_embed=batch["emo_embed"][0].cpu().numpy(), f0=batch["ref_f0_hz"][0, :n_mel].double().cpu().numpy())
+        if inp.get("pitch_audio") is not None:   # tracked once, here: the contour replaces the audio entry
+            inp["pitch_hz"] = batch["pitch_hz"][0][0].cpu().numpy()
+            del inp["pitch_audio"]
         return inp
 
     def postprocess_output(self, output):
@@ -480,7 +529,7 @@ class StyleSingerInfer:
         return self.postprocess_output(self._wav_from_result(res, vocoder_noise))
 
     @classmethod
-    def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, **ctor):
+    def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, pitch=None, **ctor):
         """inference/StyleSinger.py:181-331: the example score (stylesinger_amd/example_input.json = that method's input dict, extracted by
         `python -m oracle.gen_golden --round6`) sung in the style of `ref_audio`, written to `out_path` as 16-bit PCM (utils/audio.py:12-17).
         `ctor`: how to build the instance - `exp_dir` + `vocoder_dir` (the reference's checkpoints, `from_checkpoints`) or explicit
@@ -489,6 +538,7 @@ class StyleSingerInfer:
         with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "example_input.json")) as fh:
             inp = {k: v for k, v in json.load(fh).items() if k != "source"}
         inp["ref_audio"] = ref_audio
+        inp.update(pitch or {})   # pitch control: pitch_hz | pitch_audio, pitch_shift (`_pitch_inputs`)
         if "exp_dir" in ctor:
             ins = cls.from_checkpoints(hparams, ctor.pop("exp_dir"), ctor.pop("vocoder_dir"), **ctor)
         else:
@@ -503,7 +553,8 @@ class StyleSingerInfer:
 def main(argv=None):
     """`python -m stylesinger_amd.infer --exp-dir checkpoints/<exp> --vocoder-dir <hifigan dir> --emotion-ckpt <pt> --speaker-ckpt <pt>
     --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim]` = the reference's
-    `python inference/StyleSinger.py` (StyleSingerInfer.example_run)."""
+    `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
+    sing the score on a given pitch contour instead of the predicted one."""
     import argparse
     ap = argparse.ArgumentParser(description="StyleSinger example_run on the HIP path")
     ap.add_argument("--exp-dir", required=True)
@@ -514,7 +565,21 @@ def main(argv=None):
     ap.add_argument("--ref-audio", default="test/test.wav")
     ap.add_argument("--out", default="infer_out/test.wav")
     ap.add_argument("--no-vad-trim", action="store_true", help="explicit opt-out of trim_long_silences (webrtcvad missing)")
+    ap.add_argument("--pitch-audio", help="sing on the pitch of this guide vocal (a WAV file, tracked on the device, 80-800 Hz) instead of the predicted f0")
+    ap.add_argument("--pitch-npy", help="sing on this contour: a .npy file holding a 1-D array of Hz at the mel hop, 0 = unvoiced")
+    ap.add_argument("--pitch-shift", type=float, help="transpose the given contour by this many semitones")
     a = ap.parse_args(argv)
+    if a.pitch_audio and a.pitch_npy:
+        ap.error("--pitch-audio and --pitch-npy exclude each other")
+    if a.pitch_shift is not None and not (a.pitch_audio or a.pitch_npy):
+        ap.error("--pitch-shift needs --pitch-audio or --pitch-npy")
+    pitch = {}
+    if a.pitch_audio:
+        pitch["pitch_audio"] = a.pitch_audio
+    if a.pitch_npy:
+        pitch["pitch_hz"] = np.load(a.pitch_npy)
+    if a.pitch_shift is not None:
+        pitch["pitch_shift"] = a.pitch_shift
     emo = torch.load(a.emotion_ckpt, map_location="cpu", weights_only=False)
     spk = torch.load(a.speaker_ckpt, map_location="cpu", weights_only=False)
     from . import ckpt
@@ -522,7 +587,7 @@ def main(argv=None):
     if state is None:
         raise FileNotFoundError(f"| ckpt not found in {a.exp_dir}.")
     vstate, vcfg = ckpt.load_vocoder_ckpt(a.vocoder_dir)
-    StyleSingerInfer.example_run(None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, model_state=state, vocoder_state=vstate,
+    StyleSingerInfer.example_run(None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, pitch=pitch, model_state=state, vocoder_state=vstate,
                                  vocoder_config=vcfg, emotion_state=emo.get("model_state", emo), speaker_state=spk.get("model_state", spk),
                                  phone_set=a.phone_set)
 

@@ -862,9 +862,34 @@ class StyleSingerHIP(torch.nn.Module):
         `sampler="plms", plms_interval=n` (the reference's PLMS sampler, hparams['pndm_speedup'],
         shallow_diffusion_tts.py:165-197), `plan_slot` (workspace/graph set to use: give concurrent forwards on different streams
         different slots), `style_cache` (the dict encode_style() returned for these references: skips
-        the style encoder)."""
-        if not infer or f0 is not None or uv is not None:
-            raise NotImplementedError("StyleSingerHIP implements the inference path only (infer=True, f0/uv predicted)")
+        the style encoder).
+
+        Pitch control (infer=True only): sing on a GIVEN f0 contour instead of the two f0 diffusions' output. Two forms:
+          * `f0=, uv=` [B, T_out] - the reference's own form (hparams['use_gt_f0'], tasks/StyleSinger/stylesinger.py:176-188): what
+            sample['f0'] / sample['uv'] hold, i.e. `norm_interp_f0` output (log2 Hz interpolated through unvoiced frames; uv > 0 = unvoiced,
+            any dtype). T_out = mel2ph.shape[1] when mel2ph is given, else the predicted frame count; another length is a ValueError.
+          * `pitch_hz=(contour_hz [B, Lc], lens_c)` (+ `pitch_shift=<semitones>`): a contour in Hz (0 = unvoiced) on a frame grid of its own,
+            fitted on the device to each item's frame count once that is known (`ss_contour_fit`, pitch.contour_fit), normalised with
+            `norm_interp_f0_device`, then used as above. An item whose fitted contour has no voiced frame is sung unvoiced, as
+            `norm_interp_f0` treats an all-unvoiced contour (f0 = 0, uv = 1 on every frame).
+        Both skip `ss_f0_bounds` and the f0 pair loop (and its hipGraph) and run `ss_pitch_given` in place of `ss_pitch_post`; everything from
+        `pitch_embed` on is unchanged, and the mel loop draws the same noise as a predicted-f0 forward with the same `seed`. `ret` carries
+        `pitch_pred`, `f0_denorm`, `f0_denorm_pred` (= `f0_denorm`, as stylesinger.py:241 yields for a given contour) and `pitch_coarse`, and
+        no `f0_a` / `uv_a` / `f0_b` / `uv_b`. The note-rest rule (uv[midi == 0] = 1) belongs to the predicted branch and is not applied. The
+        reference's `mdiff*` / `gdiff*` / `nll*` on this branch are training losses of the f0 nets (:305-307): they are not produced. A
+        recorded `noise` dict needs no `f0_a` / `f0_b` entries in these forms."""
+        if not infer:
+            raise NotImplementedError("StyleSingerHIP implements the inference path only (infer=True)")
+        pitch_hz, pitch_shift = kwargs.get("pitch_hz"), kwargs.get("pitch_shift")
+        if (f0 is None) != (uv is None):
+            raise ValueError(f"forward: f0 and uv go together (got {'f0' if uv is None else 'uv'} without {'uv' if uv is None else 'f0'})")
+        if pitch_hz is not None and f0 is not None:
+            raise ValueError("forward: give either pitch_hz (a contour in Hz to fit) or f0 / uv (the normalised contour), not both")
+        if pitch_shift is not None and pitch_hz is None:
+            raise ValueError("forward: pitch_shift transposes the pitch_hz contour; it needs pitch_hz")
+        if pitch_hz is not None and not (isinstance(pitch_hz, (tuple, list)) and len(pitch_hz) == 2):
+            raise ValueError("forward: pitch_hz = (contour_hz [B, Lc], lens_c)")
+        given = f0 is not None or pitch_hz is not None
         self._ensure_packed()
         lib, hp, pk = _lib(), self.hp, self._pk
         st = L.stream_ptr
@@ -934,6 +959,9 @@ class StyleSingerHIP(torch.nn.Module):
         # hipGraph bucket: run the frame axis padded to a multiple of t_bucket (padding = mel2ph 0 -> masked like any
         # batch padding); the plan/graph cache is then keyed by the bucket and every frame-level output is cropped back.
         T_out = T
+        if f0 is not None and (tuple(f0.shape) != (B, T_out) or tuple(uv.shape) != (B, T_out)):
+            raise ValueError(f"forward: f0 {tuple(f0.shape)} / uv {tuple(uv.shape)} given for {T_out} frames "
+                             f"({'mel2ph' if 'dur_choice' not in ret else 'predicted durations'}): expected [{B}, {T_out}]")
         T = self.bucket_frames(T_out)
         if T != T_out:
             mel2ph = _pad_frames(mel2ph, T).contiguous()
@@ -969,48 +997,64 @@ class StyleSingerHIP(torch.nn.Module):
         ret["gloss"] = 0.0
 
         # ---- pitch: two joint Gaussian/multinomial diffusions (a8) + post-processing (a9) ----
-        midi = torch.empty(B, T, device=dev, dtype=torch.int64)
-        L.check(lib.ss_gather_expand_i64(L.ptr(note), L.ptr(mel2ph), L.ptr(midi), B, Tp, T, st()), "midi")
         pl = self._plan(B, T, dev, int(kwargs.get("plan_slot", 0)))
         pl.uses += 1
         pl.lens2[:B].copy_(lens_t)
-        pl.lens2[B:].copy_(lens_t)
         pl.seed.fill_(seed)
-        L.check(lib.ss_f0_bounds(L.ptr(midi), L.ptr(pl.lo2), L.ptr(pl.hi2), B * T, st()), "bounds")
-        pl.lo2[B:].copy_(pl.lo2[:B])
-        pl.hi2[B:].copy_(pl.hi2[:B])
-        pl.cond_a.copy_(dec)  # = decoder_inp * tgt_nonpadding (the gather already wrote 0 on padding)
-        L.check(lib.ss_add_bcast_mask(L.ptr(dec), L.ptr(spk), None, L.ptr(emo), L.ptr(style), L.ptr(pl.cond_b), B, T, H, L.ptr(lens_t), st()), "cond_b")
-        pl.uv2.zero_()
         graphs = noise is None and self._want_graphs(pl)
-
-        def tape_t(x):  # recorded noise [..., T_out] (reference layout) -> device fp32, frame axis padded to the bucket
-            return _pad_frames(x.to(dev).float(), T)
-        if noise is not None:
-            S = pk["f0_pair"]["net"].steps
-            na, nb_ = noise["f0_a"], noise["f0_b"]
-            pl.f0[0].copy_(tape_t(na["z0"]).reshape(B, T))
-            pl.f0[1].copy_(tape_t(nb_["z0"]).reshape(B, T))
-            zs = torch.cat([tape_t(na["z_steps"]).reshape(S, B, T), tape_t(nb_["z_steps"]).reshape(S, B, T)], 1).contiguous()
-            us = torch.cat([tape_t(na["u_steps"]).reshape(S, B, 2, T), tape_t(nb_["u_steps"]).reshape(S, B, 2, T)], 1).contiguous()
-            self._run_f0_pair(pl, (zs, us))
-        elif graphs:
-            if pl.g_f0 is None:
-                pl.g_f0 = self._capture(lambda: self._run_f0_pair(pl))
-                pl.uv2.zero_()
-            pl.g_f0.replay()
-        else:
-            self._run_f0_pair(pl)
-        res = {"f0_a": (pl.f0[0].clone(), pl.uv[0].clone()), "f0_b": (pl.f0[1].clone(), pl.uv[1].clone())}
-        ret["gdiff1"] = ret["mdiff1"] = ret["gdiff2"] = ret["mdiff2"] = 0.0
         pitch_pred = torch.empty(B, T, 2, **f32)
         f0_denorm = torch.empty(B, T, **f32)
         coarse = torch.empty(B, T, device=dev, dtype=torch.int64)
-        L.check(lib.ss_pitch_post(L.ptr(res["f0_a"][0]), L.ptr(res["f0_a"][1]), L.ptr(res["f0_b"][0]), L.ptr(res["f0_b"][1]),
-                                  L.ptr(midi), L.ptr(mel2ph), L.ptr(pitch_pred), L.ptr(f0_denorm), L.ptr(coarse), B * T, st()), "pitch_post")
+
+        def tape_t(x):  # recorded noise [..., T_out] (reference layout) -> device fp32, frame axis padded to the bucket
+            return _pad_frames(x.to(dev).float(), T)
+        if given:
+            # ---- a given contour: no clamp bounds, no f0 pair loop (pl.g_f0 stays untouched); the mel loop's Philox keys are per call site
+            # (constant + pl.seed) and its counters per (step, element), so it draws what a predicted-f0 forward with this seed draws
+            if pitch_hz is not None:
+                from .pitch import contour_fit_device, norm_interp_f0_device
+                if pitch_hz[0].dim() != 2 or pitch_hz[0].shape[0] != B:
+                    raise ValueError(f"forward: pitch_hz contour {tuple(pitch_hz[0].shape)} for a batch of {B}: expected [{B}, Lc]")
+                hz = contour_fit_device(pitch_hz[0].to(dev), pitch_hz[1], lens_t, T, 0.0 if pitch_shift is None else float(pitch_shift))
+                f0_g, uv_g = norm_interp_f0_device(hz, lens_t, hp)   # frames >= lens_t[b]: f0 = 0, uv = 0 - masked by mel2ph == 0 below
+            else:  # bucket padding: f0 = 0, uv = 1 (mel2ph is 0 there anyway)
+                f0_g = _pad_frames(f0.to(dev).float(), T).contiguous()
+                uv_g = uv.to(dev).float()
+                uv_g = uv_g.contiguous() if T == T_out else torch.nn.functional.pad(uv_g, (0, T - T_out), value=1.0)
+            L.check(lib.ss_pitch_given(L.ptr(f0_g), L.ptr(uv_g), L.ptr(mel2ph), L.ptr(pitch_pred), L.ptr(f0_denorm), L.ptr(coarse), B * T, st()),
+                    "pitch_given")
+        else:
+            midi = torch.empty(B, T, device=dev, dtype=torch.int64)
+            L.check(lib.ss_gather_expand_i64(L.ptr(note), L.ptr(mel2ph), L.ptr(midi), B, Tp, T, st()), "midi")
+            pl.lens2[B:].copy_(lens_t)
+            L.check(lib.ss_f0_bounds(L.ptr(midi), L.ptr(pl.lo2), L.ptr(pl.hi2), B * T, st()), "bounds")
+            pl.lo2[B:].copy_(pl.lo2[:B])
+            pl.hi2[B:].copy_(pl.hi2[:B])
+            pl.cond_a.copy_(dec)  # = decoder_inp * tgt_nonpadding (the gather already wrote 0 on padding)
+            L.check(lib.ss_add_bcast_mask(L.ptr(dec), L.ptr(spk), None, L.ptr(emo), L.ptr(style), L.ptr(pl.cond_b), B, T, H, L.ptr(lens_t), st()), "cond_b")
+            pl.uv2.zero_()
+            if noise is not None:
+                S = pk["f0_pair"]["net"].steps
+                na, nb_ = noise["f0_a"], noise["f0_b"]
+                pl.f0[0].copy_(tape_t(na["z0"]).reshape(B, T))
+                pl.f0[1].copy_(tape_t(nb_["z0"]).reshape(B, T))
+                zs = torch.cat([tape_t(na["z_steps"]).reshape(S, B, T), tape_t(nb_["z_steps"]).reshape(S, B, T)], 1).contiguous()
+                us = torch.cat([tape_t(na["u_steps"]).reshape(S, B, 2, T), tape_t(nb_["u_steps"]).reshape(S, B, 2, T)], 1).contiguous()
+                self._run_f0_pair(pl, (zs, us))
+            elif graphs:
+                if pl.g_f0 is None:
+                    pl.g_f0 = self._capture(lambda: self._run_f0_pair(pl))
+                    pl.uv2.zero_()
+                pl.g_f0.replay()
+            else:
+                self._run_f0_pair(pl)
+            res = {"f0_a": (pl.f0[0].clone(), pl.uv[0].clone()), "f0_b": (pl.f0[1].clone(), pl.uv[1].clone())}
+            ret["gdiff1"] = ret["mdiff1"] = ret["gdiff2"] = ret["mdiff2"] = 0.0
+            L.check(lib.ss_pitch_post(L.ptr(res["f0_a"][0]), L.ptr(res["f0_a"][1]), L.ptr(res["f0_b"][0]), L.ptr(res["f0_b"][1]),
+                                      L.ptr(midi), L.ptr(mel2ph), L.ptr(pitch_pred), L.ptr(f0_denorm), L.ptr(coarse), B * T, st()), "pitch_post")
+            ret["f0_a"], ret["uv_a"], ret["f0_b"], ret["uv_b"] = res["f0_a"][0], res["f0_a"][1], res["f0_b"][0], res["f0_b"][1]
         ret["pitch_pred"], ret["f0_denorm"], ret["f0_denorm_pred"] = pitch_pred, f0_denorm, f0_denorm
         ret["pitch_coarse"] = coarse
-        ret["f0_a"], ret["uv_a"], ret["f0_b"], ret["uv_b"] = res["f0_a"][0], res["f0_a"][1], res["f0_b"][0], res["f0_b"][1]
         pitch_emb = torch.empty(B, T, H, **f32)
         L.check(lib.ss_embedding(L.ptr(coarse), L.ptr(self.p("pitch_embed.weight")), L.ptr(pitch_emb), B * T, H, 300, 1.0, 0, st()), "pitch emb")
         dec_inp = torch.empty(B, T, H, **f32)

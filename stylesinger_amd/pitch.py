@@ -8,6 +8,10 @@ Two forms with the same contract:
   * `norm_interp_f0(f0, hparams)`      host numpy, what `StyleSingerInfer.input_to_batch` calls for one utterance;
   * `norm_interp_f0_device(f0, lens)`  `[B, T]` on the GPU (`ss_norm_interp_f0`), what `preprocess_batch` uses so a batch
                                        goes from tracker output to `infer_batch` without a host round trip.
+
+Pitch control (`StyleSingerHIP.forward(pitch_hz=...)`): a caller's contour in Hz lives on a frame grid of its own, the score's frame count is only
+known inside forward. `contour_fit` is the float64 definition of the fit between the two grids, `contour_fit_device` the kernel (`ss_contour_fit`,
+csrc/pitch_fit.hip) that runs it from device lengths.
 """
 import numpy as np
 import torch
@@ -66,3 +70,53 @@ def norm_interp_f0_device(f0_hz, lens=None, hparams=None):
     lp = None if lens is None else lens.to(device=x.device, dtype=torch.int32).contiguous()
     L.check(L.load().ss_norm_interp_f0(L.ptr(x), L.ptr(lp), L.ptr(out), L.ptr(uv), B, T, L.stream_ptr()), "ss_norm_interp_f0")
     return out, uv
+
+
+def contour_fit(f0_hz, n_t, shift=0.0):
+    """The definition of the contour fit (float64): f0_hz [n_c] in Hz (0 = unvoiced) -> [n_t] in Hz on a grid of n_t frames over the same time span.
+    Output frame t sits at source position s = (t + 0.5) * n_c / n_t - 0.5, clamped to [0, n_c - 1] (the frame centres of both grids on one time
+    axis); s is held as the exact fraction num / (2 n_t). With i0 = floor(s), fr = s - i0, i1 = min(i0 + 1, n_c - 1):
+      * the frame is voiced iff the NEAREST source frame is voiced (fr >= 1/2 -> i1: a tie goes to the later frame), else 0;
+      * its value is exp2((1 - fr) log2 f[i0] + fr log2 f[i1]) when both neighbours are voiced, otherwise the nearest frame's value (then the only
+        voiced neighbour), times 2^(shift / 12) (shift in semitones);
+      * fr == 0 takes f[i0] itself, so with shift == 0 equal lengths return the contour unchanged, bit for bit."""
+    f = np.asarray(f0_hz, dtype=np.float64)
+    n_c, n_t = len(f), int(n_t)
+    out = np.zeros(n_t, dtype=np.float64)
+    if n_c == 0 or n_t == 0:
+        return out
+    t = np.arange(n_t, dtype=np.int64)
+    den = 2 * n_t
+    num = np.clip((2 * t + 1) * n_c - n_t, 0, (n_c - 1) * den)
+    i0, rem = num // den, num % den
+    i1 = np.minimum(i0 + 1, n_c - 1)
+    a, c = f[i0], f[i1]
+    near = np.where(2 * rem >= den, c, a)
+    fr = rem / den
+    both = (a > 0) & (c > 0) & (rem != 0)
+    with np.errstate(divide="ignore"):
+        la, lc = np.log2(np.where(both, a, 1.0)), np.log2(np.where(both, c, 1.0))
+    val = np.where(both, np.exp2(la + fr * (lc - la)), near)
+    voiced = near > 0
+    out[voiced] = val[voiced] * (2.0 ** (float(shift) / 12.0) if shift else 1.0)
+    return out
+
+
+@torch.no_grad()
+def contour_fit_device(f0_hz, lens_c, lens_t, T, shift=0.0):
+    """f0_hz fp32 [B, Lc] on the device (Hz, 0 = unvoiced), lens_c [B] valid source frames (host ints or a device tensor; None = Lc), lens_t int32 [B] ON THE
+    DEVICE (target frames per item: no host sync) -> [B, T] fp32: `contour_fit` of each item's first lens_c[b] frames to lens_t[b] frames, 0 beyond."""
+    if not torch.is_tensor(f0_hz) or f0_hz.device.type != "cuda":
+        raise L.StyleSingerHipError("contour_fit_device needs device tensors: there is no CPU path")
+    x = f0_hz if f0_hz.dtype == torch.float32 and f0_hz.stride(1) == 1 and f0_hz.stride(0) >= f0_hz.shape[1] else f0_hz.float().contiguous()
+    B, Lc = x.shape
+    dev = x.device
+    lc = torch.full((B,), Lc, dtype=torch.int32) if lens_c is None else torch.as_tensor(lens_c)
+    lc = lc.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    lt = lens_t.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if lc.numel() != B or lt.numel() != B:
+        raise ValueError(f"contour_fit_device: {lc.numel()} source lengths and {lt.numel()} target lengths for {B} contours")
+    out = torch.empty(B, int(T), device=dev, dtype=torch.float32)
+    L.check(L.load().ss_contour_fit(L.ptr(x), x.stride(0), Lc, L.ptr(lc), L.ptr(lt), float(shift), L.ptr(out), out.stride(0), int(T), B,
+                                    L.stream_ptr()), "ss_contour_fit")
+    return out
