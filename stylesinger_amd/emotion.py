@@ -39,6 +39,11 @@ def compute_partial_slices(n_samples, partial_utterance_n_frames=PARTIALS_N_FRAM
     return wav, mel
 
 
+def pack_whh(w_hh, H):
+    """torch's weight_hh [4H, H] (gate-major rows: i, f, g, o) -> [k][j][gate] = weight_hh[gate * H + j][k], the order ss_lstm_layer streams."""
+    return w_hh.view(4, H, H).permute(2, 1, 0).contiguous()
+
+
 class EmotionEncoderHIP:
     def __init__(self, state_dict=None, device="cuda", hidden=256, n_mel=40, layers=3, embed=256):
         if not torch.cuda.is_available():
@@ -69,7 +74,7 @@ class EmotionEncoderHIP:
             b_p = b.view(4, H).t().reshape(4 * H).contiguous()
             W = L.pack_conv_weight(w_ih_p)
             pk.append(dict(W=W, bias=L.pack_bias(b_p), Np=W.shape[0], Kp=W.shape[1], cin=cin,
-                           whh=w_hh.view(4, H, H).permute(2, 1, 0).contiguous()))   # [k][j][gate]
+                           whh=pack_whh(w_hh, H)))
         lw = sd["linear.weight"].to(dev).float()
         Wl = L.pack_conv_weight(lw)
         self._lin = dict(W=Wl, bias=L.pack_bias(sd["linear.bias"].to(dev).float()), Np=Wl.shape[0], Kp=Wl.shape[1])
