@@ -17,24 +17,18 @@
 //   * epilogues are fused: bias / activation / residual / gate / residual+skip / DDPM posterior step.
 #pragma once
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 #include <type_traits>
 #include "../../include/stylesinger_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
-constexpr int BK = 32;
-constexpr int LDS_LD = BK;  // floats; no padding: the 16-B slots of a row are XOR-swizzled instead (see lds_slot)
+using namespace ss_dev;
 
-// LDS image of a staged operand tile: row r holds 32 consecutive K values = 8 slots of 16 B. Slot s of row r lives
-// at physical slot s ^ ((r >> 1) & 7). With 128-B rows the 64 banks (256 B) hold two rows, so a ds_read_b128 lane
-// group (rows {0-3,12-15,20-27} of one 16-B column, MI355X_MICROARCH.md §LDS) conflicts iff two rows agree in
-// parity and in (r>>1)&7, i.e. are congruent mod 16 - none are. ds_write_b128 (8 contiguous lanes = the 8 slots of
-// one row) is conflict-free too. Dropping the +4 padding cuts a 64x128 tile to 48 KiB -> 3 blocks per CU.
-__device__ __forceinline__ int lds_slot(int row, int slot) { return row * LDS_LD + ((slot ^ ((row >> 1) & 7)) << 2); }
+constexpr int BK = 32;
+static_assert(BK == 32, "lds_slot lays out 32-float rows");
+constexpr int LDS_LD = BK;  // floats; no padding: the 16-B slots of a row are XOR-swizzled instead (lds_slot, device_prims.h)
 
 // BF16 = true: same staging and epilogues, but both operands are rounded to bf16 (RNE, v_cvt_pk_bf16_f32) on their way
 // from LDS to the matrix core and the products run on v_mfma_f32_32x32x16_bf16 (fp32 accumulate) - BASELINE config 4.
@@ -93,12 +87,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_gemm_kernel(const
   // W: records = Np*ldw*4 -> packed rows beyond Np read 0.
   // (descriptor inputs go through readfirstlane so that hipcc can PROVE them wave-uniform; otherwise every
   //  buffer op is wrapped in a waterfall loop - cdna_hip_programming.md T20)
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w =

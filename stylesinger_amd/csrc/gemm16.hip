@@ -18,34 +18,18 @@
 // Arithmetic: exact fp32 products, fp32 accumulation; the K order inside an accumulator differs from the 32x32x2 kernel
 // (tests/test_gpu_round3.py compares with torch fp32 and with ss_conv_gemm).
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BK = 32;
 constexpr int LD = BK;
 constexpr int BN = 64;
 constexpr int NBUF = 3;
-
-// same 16-byte slot swizzle as the 16x16 gate kernel (conflict-free ds_read_b128 for lanes (row = l & 15, slots 2(l>>4), 2(l>>4)+1))
-__device__ __forceinline__ int swz16(int row) { return ((row >> 1) & 7) ^ ((((row >> 2) ^ (row >> 3)) & 1) << 1); }
-
-// s_waitcnt vmcnt(N), other counters untouched (gfx9 encoding: vmcnt = imm[3:0] | imm[15:14] << 4, expcnt imm[6:4], lgkmcnt imm[11:8])
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
-// LDS-DMA of 64 x 16 bytes: lane i's 16 bytes land at lds_dst + 16 i (wave-uniform destination, per-lane source offset).
-// (A __device__ helper on purpose: with the builtin written directly inside the templated __global__ body, the host pass of hipcc
-//  (ROCm 7.2) silently drops the kernel's launch stub and the library no longer links.)
-template <int AUX = 0>   // cache-policy bits (0 in the product; 16 = sc1: reads past this CU's L1, for operands another workgroup published write-through)
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, float* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, AUX);
-}
 
 // WL = weight layout: false = packed rows [Np][Kp]; true = the lane-contiguous repack of ss_pack_gemm16_weights
 // ([n tile][wave][K chunk][half][lane][4 floats]): one fetch instruction of a wave = 1 KB contiguous instead of 16 columns x 64 B
@@ -77,12 +61,6 @@ __device__ __forceinline__ void gemm16_res_body(const ss_conv_gemm_args& a, cons
   const int len = ss_uniform_len(a.lens, b, a.T);
   const int grp_w = a.group_size > 0 ? b / a.group_size : 0;
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(
@@ -277,12 +255,6 @@ __global__ __launch_bounds__(256, 3) void gemm16_store_kernel(const ss_conv_gemm
   const int kch_all = a.Kp / BK;
   const int kbeg = (int)((long)ksi * kch_all / ksplit), kchunks = (int)((long)(ksi + 1) * kch_all / ksplit);   // this slice: chunks [kbeg, kchunks)
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(

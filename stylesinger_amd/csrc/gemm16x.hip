@@ -7,34 +7,17 @@
 //   * A (the gate outputs of all layers, fp32 in HBM) is fetched two K chunks ahead into registers, split when it is staged:
 //     LDS image [2 buffers][3 planes][16 MT rows][32 bf16] with the 64-byte-row slot swizzle of wino43_gate16x.hip; one barrier per chunk.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BK = 32;
 constexpr int BN = 64;
 constexpr int ROWB = BK * 2;
-
-__device__ __forceinline__ int swz64(int row) { return (row & 8) ? 3 : 0; }
-
-__device__ __forceinline__ void split3(float x, float y, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
-  auto pk = [](float p, float q) {
-    const f32x2 v = {p, q};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-  };
-  hi = pk(x, y);
-  const float rx = x - __builtin_bit_cast(float, hi << 16), ry = y - __builtin_bit_cast(float, hi & 0xffff0000u);
-  mid = pk(rx, ry);
-  lo = pk(rx - __builtin_bit_cast(float, mid << 16), ry - __builtin_bit_cast(float, mid & 0xffff0000u));
-}
 
 template <int MT>
 __global__ __launch_bounds__(256, 3) void gemm16x_store_kernel(const ss_conv_gemm_args a, const uint16_t* __restrict__ Wx, int m_tiles_per_item,
@@ -60,12 +43,6 @@ __global__ __launch_bounds__(256, 3) void gemm16x_store_kernel(const ss_conv_gem
   const int grp_w = a.group_size > 0 ? b / a.group_size : 0;
   const int kchunks = a.Kp / BK;
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const int np64 = (a.Np + BN - 1) / BN;   // 64-column tiles in the split weights

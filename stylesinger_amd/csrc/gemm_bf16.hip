@@ -17,16 +17,15 @@
 // Arithmetic contract = oracle/restatement.py with set_matmul_rounding("bf16"): RNE rounding of both matmul operands, exact
 // products, fp32 accumulation; everything outside the matmuls fp32.
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 #include "../../include/stylesinger_hip.h"
 #include "pair16.h"
 #include <type_traits>
 
-typedef ss_f32x16 f32x16;
-typedef ss_bf16x8 bf16x8;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BKH = 64;  // bf16 per K chunk
 constexpr int LDH = 64;  // bf16 per LDS row (128 bytes)
@@ -34,12 +33,6 @@ constexpr int LDH = 64;  // bf16 per LDS row (128 bytes)
 // byte offset of 16-byte slot `slot` of row `row` (slot ^ ((row >> 1) & 7): conflict-free ds_read_b128 / ds_write_b128, see
 // conv_gemm_kernel.h)
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * (LDH * 2) + ((slot ^ ((row >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ uint16_t f2bf(float x) {  // RNE, like torch's .bfloat16()
-  return __builtin_bit_cast(uint16_t, (__bf16)x);
-}
-
-__device__ __forceinline__ float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 
 // SPLIT = 1 ("bf16x2"): operands are (hi, mid) bf16 pairs interleaved by 32 channels - a 128-byte K chunk holds 32 channels of BOTH planes
 // (slots 0-3 hi, 4-7 mid), the fetch / staging code is the same, and a chunk feeds 2 k-steps x 3 products (mid*hi, hi*mid, hi*hi) instead of 4 x 1.
@@ -77,12 +70,6 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
   const int nchunks = a.ntaps * nchunks_tap;
   const int ldw = a.ntaps * a.K * (SPLIT ? 2 : 1);  // bf16 per packed weight row
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   // range-checked fetches: rows outside [0, len) of the item read 0 (= the conv's zero padding), packed rows beyond Np read 0
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 2), 0x00020000);

@@ -14,31 +14,19 @@
 // All index math lives in gate128_layout.h and is checked on the host against a tagged LDS image (tools/layout_check_gate128.cpp).
 // Arithmetic contract = gate256_kernel<8, 2>: results equal up to the K summation order (the same order, in fact: same steps, same tiles).
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include "pair16.h"
 #include "gate128_layout.h"
 #include <type_traits>
 #include <utility>
 
-typedef ss_f32x16 f32x16;
-typedef ss_bf16x8 bf16x8;
-
 namespace {
+
+using namespace ss_dev;
 
 using namespace g128;
 constexpr int CCS = 8;   // K = 256 channels per tap = 8 chunks of 32
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-template <class F, int... I>
-__device__ __forceinline__ void unrolled_steps(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
 
 __global__ __launch_bounds__(256, 2) void gate128_kernel(const ss_gemm_bf16_args a, int m_tiles_per_item, int m_tiles, int n_tiles, int d,
                                                           unsigned long long* clock_probe) {
@@ -78,12 +66,6 @@ __global__ __launch_bounds__(256, 2) void gate128_kernel(const ss_gemm_bf16_args
   const int grp_w = a.group_size > 0 ? b / a.group_size : 0;
   const int ldw = 3 * a.K * 2;   // 16-bit terms per packed weight row: 3 taps, both planes
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(

@@ -13,31 +13,20 @@
 // Arithmetic contract unchanged: bf16 operands (rounded once where they are produced), exact products, fp32 accumulation, fp32 addend,
 // hardware exp/rcp activations, bf16 gate output - the same values as gemm_bf16_kernel<GATE> up to the K summation order.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include "pair16.h"
 #include <type_traits>
 #include <utility>
 
-typedef ss_f32x16 f32x16;
-typedef ss_bf16x8 bf16x8;
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BM = 256, BN = 256, BKH = 64;
 constexpr int HALO = 8;                       // rows staged before the tile (dilations up to 8)
 constexpr int AROWS = 320;                    // 5 DMA instructions per wave (8 rows each); rows >= BM + 2 HALO are zero fill
 constexpr int ROWB = BKH * 2;                 // bytes per LDS row (64 bf16)
-
-__device__ __forceinline__ uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-// LDS-DMA of 64 x 16 bytes (lane i lands at lds_dst + 16 i); a __device__ helper so that the host pass keeps the kernel's launch stub
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
 
 // SPLIT ("bf16x2" precision, ss_gemm_bf16_args.split): operands are (hi, mid) bf16 pairs interleaved by 32 channels, so a 128-byte LDS row is
 // 32 channels of BOTH planes (slots 0-3 hi, 4-7 mid) and every line of the DMA / LDS plan below is unchanged; a step then covers 32 channels
@@ -46,11 +35,6 @@ __device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_ds
 // SPLIT = 2 ("fp16x2"): the same image with fp16 terms; the A operand's second plane is staged but never read, a step runs 2 k-steps x 2
 // products (hi*hi, hi*lo) = 32 MFMAs from 8 + 8 fragment reads (step_w2), the accumulators are scaled by args.out_scale in the epilogue and the
 // output is fp16(g) in the hi slots only (the second plane of the output rows is left untouched).
-template <class F, int... I>
-__device__ __forceinline__ void unrolled_steps(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-
 template <int CCS, int SPLIT>
 __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args a, int m_tiles_per_item, int m_tiles, int n_tiles, int d) {
   extern __shared__ __attribute__((aligned(16))) char smem_g256[];   // 144 KB (split: 160 KB, the epilogue's staging tile is twice as wide): one workgroup per CU
@@ -84,12 +68,6 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
   constexpr bool W2 = SPLIT == 2;
   const int ldw = 3 * a.K * (SPLIT ? 2 : 1);            // bf16 per packed weight row (3 taps; both planes when split)
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(

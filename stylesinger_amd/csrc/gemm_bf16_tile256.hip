@@ -15,29 +15,17 @@
 // W2 (ss_gemm_bf16_args.split = 2, "fp16x2"): fp16 terms, the A operand's second plane is neither fetched (dead DMA lanes write zeros) nor read, two products hi*hi + hi*lo per
 // k-step (32 MFMAs per step, the 16 of the second k-step deferred), accumulators scaled by args.out_scale where the epilogue first touches them.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include "pair16.h"
 #include <type_traits>
 
-typedef ss_f32x16 f32x16;
-typedef ss_bf16x8 bf16x8;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BM = 256, BN = 256;
 constexpr int ROWB = 128;                     // bytes per LDS row: 32 channels x (hi | mid)
-
-__device__ __forceinline__ uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ __forceinline__ float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
 
 // ONE (with W2; "fp16sd", ss_gemm_bf16_args.one_product): a single fp16 weight term - the lo plane of the weights is neither fetched (dead DMA lanes, as the
 // A operand's second plane) nor read, 16 MFMAs per step instead of 32 (the 8 of the second k-step deferred past the barrier with the DMA pieces between them)
@@ -65,12 +53,6 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
   const int ldw = w_compact ? a.K : 2 * a.K;              // 16-bit elements per packed weight row (both planes, one tap)
   const int b_chunk = (w_compact && !DENSE) ? ROWB / 2 : ROWB;
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(

@@ -8,29 +8,21 @@
 // The launch sits at the chip's power-limited matrix rate, so fewer matrix instructions are what makes it faster.
 // NOT YET RUN ON HARDWARE (written after the round's GPU budget was spent): reached only through ss_gemm_bf16_tile256q, not dispatched to.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include "pair16.h"
 #include "gate128_layout.h"
 #include <type_traits>
 
-typedef ss_f32x16 f32x16;
-typedef ss_bf16x8 bf16x8;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
+using namespace ss_dev;
+
 constexpr int BM = 256, BN = 256;
 constexpr int ROWB = 128;   // bytes per LDS row: A = 32 channels x (hi | unused plane), B = 32 channels hi | the pair's fp4 lo terms + scales
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
 
 __global__ __launch_bounds__(512, 2) void tile256q_store_kernel(const ss_gemm_bf16_args a, int m_tiles_per_item, int m_tiles, int kchunks) {
   extern __shared__ __attribute__((aligned(16))) char smem_t256q[];   // 128 KB: [A0 32 K][B0 32 K][A1 32 K][B1 32 K]; epilogue: 2 x 64 KB staging
@@ -50,12 +42,6 @@ __global__ __launch_bounds__(512, 2) void tile256q_store_kernel(const ss_gemm_bf
   const int grp_w = a.group_size > 0 ? b / a.group_size : 0;
   const int ldw = 2 * a.K;            // 16-bit terms per packed weight row (one 64-element line per 32-channel chunk)
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(

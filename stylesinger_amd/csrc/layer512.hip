@@ -32,19 +32,16 @@
 // keeps it as an fp16 pair = 22 bits). Results equal those of the two-launch form up to the
 // fp32 summation order (tests/test_gpu_layer512.py: both against float64 of the same terms).
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 #include "../../include/stylesinger_hip.h"
 #include "pair16.h"
 #include <type_traits>
 #include <utility>
 
-typedef ss_f32x16 f32x16;
-typedef ss_bf16x8 bf16x8;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BM = 128;                    // rows per tile
 constexpr int HALO = 8;                    // dilations up to 8
@@ -84,23 +81,6 @@ constexpr int nring_r(int NP) { return NP == 2 ? 5 : 8; }   // ... of the residu
 #define L512_STAMP(k) do { } while (0)
 #endif
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, int voffset, int soffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-template <class F, int... I>
-__device__ __forceinline__ void unrolled_steps(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-__device__ __forceinline__ void* uniform_ptr(const void* p) {
-  const uint64_t v = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-}
 __device__ __forceinline__ bf16x8 ldw(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
   return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
 }

@@ -19,28 +19,19 @@
 // The leaky-relu of the input is applied ONCE per fetched row register (max(x, slope x) == x >= 0 ? x : slope x for 0 < slope < 1): one
 // packed multiply per two elements + one bare v_max_f32 per element (ss_lrelu_max).
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BK = 32;
 constexpr int LD = BK;
 constexpr int BQ = 64;  // quads per tile (= 256 output frames)
 constexpr int BN = 64;
 constexpr int NC = 6;
-
-__device__ __forceinline__ int lds_slot(int row, int slot) { return row * LD + ((slot ^ ((row >> 1) & 7)) << 2); }
-
-__device__ __forceinline__ float4 vfma(float c, const float4& r, const float4& v) {
-  return make_float4(fmaf(c, r.x, v.x), fmaf(c, r.y, v.y), fmaf(c, r.z, v.z), fmaf(c, r.w, v.w));
-}
-__device__ __forceinline__ float4 vadd(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 vsub(const float4& a, const float4& b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 
 template <int D>
 __device__ __forceinline__ int frame_of_quad(int q) {
@@ -74,12 +65,6 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
   const int kchunks = a.Kp / BK;
   const int ldw = groups * NC * a.Kp;
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w =

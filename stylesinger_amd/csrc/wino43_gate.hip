@@ -23,12 +23,10 @@
 // Chunk g = 6k + j uses LDS buffer j & 1 (compile time) and accumulator j. Skeleton (LDS swizzle, buffer-resource fetch with SGPR
 // chunk offsets, stores-then-fetch scheduling) as wino_gate_kernel_v2.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // SS_TRACE (debug builds only, tools/wave_trace.py --kernel wino43): every wave sums, over its chunks, the shader-clock time of the
 // phases of a chunk and writes the sums + its entry/exit stamps at exit (same record layout as wino_gate_kernel_v2).
@@ -41,13 +39,13 @@ extern "C" int ss_debug_set_wino43_trace(void* p) {
 
 namespace {
 
+using namespace ss_dev;
+
 constexpr int BK = 32;
 constexpr int LD = BK;
 constexpr int BQ = 64;  // quads per tile (= 256 output frames)
 constexpr int BN = 64;
 constexpr int NC = 6;   // components
-
-__device__ __forceinline__ int lds_slot(int row, int slot) { return row * LD + ((slot ^ ((row >> 1) & 7)) << 2); }
 
 // input-transform coefficients of raw row q for component J (0 = row not used)
 template <int J, int Q>
@@ -100,12 +98,6 @@ __global__ __launch_bounds__(256, 2) void wino43_gate_kernel(const ss_conv_gemm_
   const int kchunks = a.Kp / BK;
   const int ldw = NC * a.Kp;
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w =
@@ -124,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void wino43_gate_kernel(const ss_conv_gemm_
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int q = q0 + st_row + i * 32;
-    const int t = q + 3 * (q & ~(d - 1));
+    const int t = wino43_frame(q, d);
     float v[6];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
@@ -318,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void wino43_gate_kernel(const ss_conv_gemm_
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int q = qbase + (r & 3) + 8 * (r >> 2);
-    tfr[r] = q + 3 * (q & ~(d - 1));
+    tfr[r] = wino43_frame(q, d);
   }
   const int lde4 = a.lde * 4;
   float* Cb = a.C + (int64_t)b * a.c_batch_stride;

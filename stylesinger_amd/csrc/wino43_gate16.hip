@@ -17,35 +17,20 @@
 // enter an accumulator differs (a 16x16x4 MFMA consumes K = {4h+e, 8+4h+e, 16+4h+e, 24+4h+e} of a chunk), so the two forms agree to
 // fp32 rounding, not bit for bit (tests/test_gpu_round3.py).
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BK = 32;
 constexpr int LD = BK;
 constexpr int BN = 64;
 constexpr int NC = 6;
 
-// 16-byte slot swizzle of a [rows][32] fp32 tile. Reads: lane (r = l & 15, kg = l >> 4) takes slots 2kg, 2kg+1 of row r; with the
-// ds_read_b128 lane groups of gfx950 ({0-3,12-15,20-27}, ...) this map is conflict-free (simulated; SQ_LDS_BANK_CONFLICT = 0).
-__device__ __forceinline__ int swz16(int row) { return ((row >> 1) & 7) ^ ((((row >> 2) ^ (row >> 3)) & 1) << 1); }
 __device__ __forceinline__ int lds_slot16(int row, int slot) { return row * LD + ((slot ^ swz16(row)) << 2); }
-
-
-// elementwise helpers on float4 / float2 (the two staging slot widths)
-__device__ __forceinline__ float4 vfma(float c, const float4& r, const float4& v) {
-  return make_float4(fmaf(c, r.x, v.x), fmaf(c, r.y, v.y), fmaf(c, r.z, v.z), fmaf(c, r.w, v.w));
-}
-__device__ __forceinline__ float2 vfma(float c, const float2& r, const float2& v) { return make_float2(fmaf(c, r.x, v.x), fmaf(c, r.y, v.y)); }
-__device__ __forceinline__ float4 vadd(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float2 vadd(const float2& a, const float2& b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float4 vsub(const float4& a, const float4& b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float2 vsub(const float2& a, const float2& b) { return make_float2(a.x - b.x, a.y - b.y); }
 
 // WL = weight layout: false = the packed rows of ss_pack_conv_weight ([Np][6][Kp], shared with the 32x32x2 kernel); true = the
 // lane-contiguous repack of ss_pack_gate16_weights ([n tile][wave][K chunk][component][half][lane][4 floats]): one fetch instruction of
@@ -91,12 +76,6 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
   const int kchunks = a.Kp / BK;
   const int ldw = NC * a.Kp;
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w =
@@ -114,7 +93,7 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
   int roffh[6];
   float mch[NC];
   auto row_setup = [&](int q, int col_floats, int (&ro)[6], auto&& set_mc) {
-    const int t = q + 3 * (q & ~(d - 1));
+    const int t = wino43_frame(q, d);
     float v[6];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
@@ -388,11 +367,11 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int qm = q0 + 16 * m + 4 * kg;          // multiple of 4
-      const int tm = qm + 3 * (qm & ~(d - 1));      // frame of quad qm
+      const int tm = wino43_frame(qm, d);      // frame of quad qm
       const int e_base = tm * lde4 + (pc * 4 + oob);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int dr = r + 3 * (r & ~(d - 1));      // wave-uniform: frame of quad qm + r = tm + dr
+        const int dr = wino43_frame(r, d);      // wave-uniform: frame of quad qm + r = tm + dr
 #pragma unroll
         for (int o = 0; o < 4; ++o)
           pe[m][r][o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_e, e_base, (dr + o * d) * lde4, 0));
@@ -438,11 +417,11 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int qm = q0 + 16 * m + 4 * kg;          // multiple of 4
-      const int tm = qm + 3 * (qm & ~(d - 1));      // frame of quad qm
+      const int tm = wino43_frame(qm, d);      // frame of quad qm
       const int c_base = (tm + my_first) * ldc4 + (oc * 4 + oob);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int dr = r + 3 * (r & ~(d - 1));
+        const int dr = wino43_frame(r, d);
         const float a0 = acc[0][m][r], a5 = acc[5][m][r];
         float s12 = acc[1][m][r] + acc[2][m][r], d12 = acc[1][m][r] - acc[2][m][r];
         const float s34 = acc[3][m][r] + acc[4][m][r], d34 = acc[3][m][r] - acc[4][m][r];
@@ -473,7 +452,7 @@ __device__ __forceinline__ bool wino43_gate16_body(const ss_conv_gemm_args& a, c
   };
   // last frame this tile can touch: quad q0 + BQ - 1, frame + 3d
   const int q_last = q0 + BQ - 1;
-  const bool fast = a.bias == nullptr && (q_last + 3 * (q_last & ~(d - 1)) + 3 * d) < row_lim;  // block-uniform
+  const bool fast = a.bias == nullptr && (wino43_frame(q_last, d) + 3 * d) < row_lim;  // block-uniform
   if (fast) epilogue(std::true_type{});
   else epilogue(std::false_type{});
   }
@@ -576,8 +555,8 @@ __global__ void gate16_tile_addend_kernel(const float* __restrict__ E, int lde, 
     const int lc = lane & 15, kg = lane >> 4, c7 = lc & 7, chi = lc >> 3;
     const int pc = nt * BN + 8 * wave + c7 + 32 * chi;
     const int qm = q0 + 16 * m + 4 * kg;
-    const int tm = qm + 3 * (qm & ~(d - 1));
-    const int dr = r + 3 * (r & ~(d - 1));
+    const int tm = wino43_frame(qm, d);
+    const int dr = wino43_frame(r, d);
     const float* Eb = E + (int64_t)b * e_bs + pc;
     float v[4];
 #pragma unroll

@@ -21,45 +21,18 @@
 //   * 64-byte LDS rows: 16-byte slot s of row r lives at r * 64 + ((s ^ ((r & 8) ? 3 : 0)) << 4), conflict-free for the ds_read_b128 lane
 //     groups of gfx950 ({0-3, 12-15, 20-27}, ...: per residue of r mod 4 the four lanes of a group hit slots 0, 1, 2, 3).
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BK = 32;
 constexpr int BN = 64;
 constexpr int NC = 6;
 constexpr int ROWB = BK * 2;   // bytes of one LDS row (32 bf16)
-
-__device__ __forceinline__ int swz64(int row) { return (row & 8) ? 3 : 0; }
-
-// two fp32 values -> their three bf16 terms, packed pairwise (low half = first value)
-__device__ __forceinline__ void split3(float x, float y, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
-  auto pk = [](float p, float q) {
-    const f32x2 v = {p, q};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-  };
-  hi = pk(x, y);
-  const float rx = x - __builtin_bit_cast(float, hi << 16), ry = y - __builtin_bit_cast(float, hi & 0xffff0000u);
-  mid = pk(rx, ry);
-  lo = pk(rx - __builtin_bit_cast(float, mid << 16), ry - __builtin_bit_cast(float, mid & 0xffff0000u));
-}
-
-__device__ __forceinline__ float4 vfma(float c, const float4& r, const float4& v) {
-  return make_float4(fmaf(c, r.x, v.x), fmaf(c, r.y, v.y), fmaf(c, r.z, v.z), fmaf(c, r.w, v.w));
-}
-__device__ __forceinline__ float2 vfma(float c, const float2& r, const float2& v) { return make_float2(fmaf(c, r.x, v.x), fmaf(c, r.y, v.y)); }
-__device__ __forceinline__ float4 vadd(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float2 vadd(const float2& a, const float2& b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float4 vsub(const float4& a, const float4& b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float2 vsub(const float2& a, const float2& b) { return make_float2(a.x - b.x, a.y - b.y); }
 
 template <int MT>
 __global__ __launch_bounds__(256, 2) void wino43_gate16x_kernel(const ss_conv_gemm_args a, const uint16_t* __restrict__ Wx,
@@ -89,12 +62,6 @@ __global__ __launch_bounds__(256, 2) void wino43_gate16x_kernel(const ss_conv_ge
   // weights: [n tile][wave][K chunk][component][plane][lane][8 bf16] (ss_split3_weights): one fetch instruction of a wave = 1 KB contiguous
   const int wtile = NC * 3 * a.Kp * BN;   // bf16 of one 64-column tile
 
-  auto uniform_ptr = [](const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(
@@ -111,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void wino43_gate16x_kernel(const ss_conv_ge
   int roffh[6];
   float mch[NC];
   auto row_setup = [&](int q, int col_floats, int (&ro)[6], auto&& set_mc) {
-    const int t = q + 3 * (q & ~(d - 1));
+    const int t = wino43_frame(q, d);
     float v[6];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
@@ -329,11 +296,11 @@ __global__ __launch_bounds__(256, 2) void wino43_gate16x_kernel(const ss_conv_ge
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int qm = q0 + 16 * m + 4 * kg;
-      const int tm = qm + 3 * (qm & ~(d - 1));
+      const int tm = wino43_frame(qm, d);
       const int e_base = tm * lde4 + (pc * 4 + oob);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int dr = r + 3 * (r & ~(d - 1));
+        const int dr = wino43_frame(r, d);
 #pragma unroll
         for (int o = 0; o < 4; ++o)
           pe[m][r][o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_e, e_base, (dr + o * d) * lde4, 0));
@@ -356,11 +323,11 @@ __global__ __launch_bounds__(256, 2) void wino43_gate16x_kernel(const ss_conv_ge
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int qm = q0 + 16 * m + 4 * kg;
-    const int tm = qm + 3 * (qm & ~(d - 1));
+    const int tm = wino43_frame(qm, d);
     const int c_base = (tm + my_first) * ldc4 + (oc * 4 + oob);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int dr = r + 3 * (r & ~(d - 1));
+      const int dr = wino43_frame(r, d);
       const float a0 = acc[0][m][r], a5 = acc[5][m][r];
       const float s12 = acc[1][m][r] + acc[2][m][r] + bs, d12 = acc[1][m][r] - acc[2][m][r] + bs;
       const float s34 = acc[3][m][r] + acc[4][m][r], d34 = acc[3][m][r] - acc[4][m][r];

@@ -14,6 +14,7 @@
 // the two N-waves of a tile hold the sigmoid half and the tanh half of the same 32 channels and swap activations
 // through LDS.  Main-loop skeleton (LDS swizzle, buffer-resource fetch, MFMA-shadow scheduling) = conv_gemm_kernel.h.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <type_traits>
 // SS_TRACE (debug builds only, tools/wave_trace.py): every wave of wino_gate_kernel_v2<1> sums, over its K chunks, the shader-clock
@@ -25,16 +26,13 @@ extern "C" int ss_debug_set_wino_trace(void* p) {
 }
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+using namespace ss_dev;
 
 constexpr int BK = 32;
 constexpr int LD = BK;
 constexpr int BP = 64;  // pairs per tile (= 128 output frames)
-
-__device__ __forceinline__ int lds_slot(int row, int slot) { return row * LD + ((slot ^ ((row >> 1) & 7)) << 2); }
 
 // TN = 32-column blocks per wave. TN=1: tile 64 pairs x 64 cols (fine-grained: best balance for the f0 pair), the two
 // N-waves swap activations through LDS. TN=2: tile 64 x 128, each wave owns both gate operands (twice the MFMAs per
@@ -69,12 +67,6 @@ __global__ __launch_bounds__(256) void wino_gate_kernel(const ss_conv_gemm_args 
   const int kchunks = a.Kp / BK;
   const int ldw = 4 * a.Kp;
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w =
@@ -406,12 +398,6 @@ __global__ __launch_bounds__(256) void wino_gate_kernel_v2(const ss_conv_gemm_ar
   const int kchunks = a.Kp / BK;
   const int ldw = 4 * a.Kp;
 
-  auto uniform_ptr = [](const float* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<float*>(((uint64_t)hi << 32) | lo);
-  };
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr(a.A + (int64_t)b * a.a_batch_stride), 0, __builtin_amdgcn_readfirstlane(len * a.lda * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_w =

@@ -36,11 +36,11 @@ def cycles(instr, addr_of_lane):
     return total, len(GROUPS[instr])
 
 
-def swz16(row):   # 128-byte rows (32 fp32): wino43_gate16.hip, gemm16.hip
+def swz16(row):   # 128-byte rows (32 fp32): csrc/device_prims.h (used by wino43_gate16.hip, gemm16.hip)
     return ((row >> 1) & 7) ^ ((((row >> 2) ^ (row >> 3)) & 1) << 1)
 
 
-def swz64(row):   # 64-byte rows (32 bf16): wino43_gate16x.hip, gemm16x.hip
+def swz64(row):   # 64-byte rows (32 bf16): csrc/device_prims.h (used by wino43_gate16x.hip, gemm16x.hip)
     return 3 if row & 8 else 0
 
 
