@@ -193,6 +193,34 @@ def test_graph_and_eager_agree_for_any_seed_history():
     assert torch.equal(ddim_g, ddim_e)
 
 
+def test_every_sampler_loop_captured_equals_eager_and_counts_its_captures():
+    """One dispatch runs every sampler loop (tape / captured graph / eager): for DDPM, DDIM (eta > 0) and ProDiff the captured model
+    equals the eager one bit for bit on the capturing call, on a replay with another seed and on the first seed again; PLMS is never
+    captured. T = 96 is padded to the 128-frame bucket and cropped; B = 2 uses the pair buffers. Captures: f0 + mel loop, + 1 for DDIM."""
+    def same(a, e, tag):
+        for k in ("mel_out", "uv_a", "pitch_coarse"):
+            assert (k in a) == (k in e) and (k not in a or torch.equal(a[k], e[k])), (tag, k)
+
+    for extra, n_first in ((dict(), 2), (dict(decoder="prodiff"), 2)):
+        hp = config.make_hparams(dict(timesteps=3, K_step=3, f0_timesteps=3, **extra))
+        b = {k: v.cuda() for k, v in synth.synth_batch(2, 96, 6, 70, hp, 3).items()}
+        gm, em = _model(hp, 3), _model(hp, 3)
+        gm.use_graphs, em.use_graphs = "on", "off"
+        for s in (21, 22, 21):                     # capture, replay with another seed, the first seed again
+            a, e = _fwd(gm, b, seed=s), _fwd(em, b, seed=s)
+            assert a["mel_out"].shape == (2, 96, 80)
+            same(a, e, (extra, s))
+        assert gm.n_captures == n_first and em.n_captures == 0
+        if extra:
+            continue
+        for s in (21, 22, 21):
+            kw = dict(sampler="ddim", ddim_steps=2, eta=0.5)
+            same(_fwd(gm, b, seed=s, **kw), _fwd(em, b, seed=s, **kw), ("ddim", s))
+        assert gm.n_captures == 3 and em.n_captures == 0
+        same(_fwd(gm, b, seed=21, sampler="plms", plms_interval=1), _fwd(em, b, seed=21, sampler="plms", plms_interval=1), "plms")
+        assert gm.n_captures == 3 and em.n_captures == 0
+
+
 def test_emotion_encoder_matches_reference_golden():
     """3 x LSTM-256 + mean/L2 (data_gen/tts/emotion/model.py:11-78, inference.py:139-151) vs the real reference's outputs."""
     from stylesinger_amd.emotion import EmotionEncoderHIP

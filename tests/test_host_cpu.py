@@ -98,7 +98,7 @@ def test_plan_cache_is_lru_bounded_by_bytes():
     class FakePlan:
         def __init__(self, b):
             self.bytes, self.uses = b, 0
-    import stylesinger_amd.model as M
+    import stylesinger_amd.plans as M
     orig = M._DiffPlan
     M._DiffPlan = lambda model, B, T, dev: FakePlan(B * T)
     try:
