@@ -836,6 +836,33 @@ int ss_vad_trim(const float* wav, int64_t wav_stride, const int32_t* n_samples, 
 int ss_resample_poly(const float* x, int64_t ldx, int Lx, const int32_t* n_in, float* y, int64_t ldy, int Ly, const int32_t* n_out_computed,
                      const int32_t* n_out, int B, const float* bank, int up, int down, int taps, int left, void* stream);
 
+/* ITU-R BS.1770 integrated loudness (mono) and loudness normalisation: what `pyln.Meter(sr).integrated_loudness` + `pyln.normalize.loudness`
+ * do to the reference audio when hparams['loud_norm'] is set (utils/audios/__init__.py:56-61; pyloudnorm is un-vendored: parity UNPINNED,
+ * `stylesinger_amd/loudness.py` holds the definition and builds the tables), and the writer's output LUFS target.
+ *   x [B][ldx] fp32, n[b] <= Lx valid samples (what the buffer holds past them is padding and never read into a result).
+ *   tab: 108 float64 on the device: [0..4] b0 b1 b2 a1 a2 of the high shelf, [5..9] of the high pass (each normalised by its a0), [10] T_g * rate
+ *        (the divisor of every block sum, a truncated block included), [11] unused, [12 + 16 i ...] the 4 x 4 matrix A^(C 2^i), i = 0 .. 5,
+ *        row-major: A = the cascade's state transition (both stages in the transposed direct form II, state (s1, s2, t1, t2)).
+ *   edges [B][lde] int32, n_blocks[b] <= lde - 4 gating blocks: block j of item b covers the samples [edges[j], edges[j + 4]) (400 ms blocks
+ *        every 100 ms), so a row holds n_blocks + 4 ascending edges, the first 0, consecutive ones at least C apart, only the last one cut to n[b].
+ *        n_blocks[b] = 0: the item is shorter than one block (lufs NaN, gain 1).
+ *   C    chunk length of the scan: a multiple of 32 in [32, 4096]. Float64 state throughout; every chunk runs from zero state, the carries are
+ *        propagated with the tabulated powers, every chunk is run again from its true initial state.
+ *   -> z [B][ldz] float64: z_j = sum of y^2 over block j / tab[10] (0 for j >= n_blocks[b]); lufs[b] = -0.691 + 10 log10(mean of z over the
+ *        blocks that pass the absolute (-70) and the relative (-10 LU) gate), -inf when none does; gain[b] = fl32(10^((target - lufs) / 20)), 1
+ *        where lufs is not finite; peak[b] = max |x| over the item.
+ * All sums are taken in a fixed order, no atomics: results are bit-identical from run to run and do not depend on B, Lx, ldx or the other
+ * items (they may depend on C). The workspace is the caller's (ss_loudness_workspace_bytes, 8-byte aligned): no allocation, graph-capturable. */
+int64_t ss_loudness_workspace_bytes(int B, int Lx, int C);
+int ss_loudness_measure(const float* x, int64_t ldx, int Lx, const int32_t* n, const int32_t* n_blocks, const int32_t* edges, int lde, int B,
+                        const double* tab, int C, double target, double* lufs, float* gain, float* peak, double* z, int ldz, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* y[b][t] = fl32(gain[b] * x[b][t]) for t < n[b]; where P = fl32(gain[b] * peak[b]) (= max |y|: rounding is monotone) exceeds 1, that value
+ * divided by P (IEEE fp32 division) - `pyln.normalize.loudness` followed by the reference's peak rule. Exact zeros for n[b] <= t < Ly.
+ * gain, peak: device arrays as ss_loudness_measure writes them. y must not alias x. */
+int ss_loudness_apply(const float* x, int64_t ldx, int Lx, const int32_t* n, const float* gain, const float* peak, float* y, int64_t ldy, int Ly,
+                      int B, void* stream);
+
 /* A pitch contour in Hz fitted to a score's frame count (input producer of forward(pitch_hz=...); definition: `contour_fit` in
  * stylesinger_amd/pitch.py). f0_hz [B][ldc], lens_c[b] <= Lc valid source frames (0 = unvoiced); out [B][ldo], T columns written; lens_t[b] <= T
  * target frames per item - a DEVICE array, e.g. what ss_length_regulate wrote, so the fit needs no host sync. Output frame t < lens_t[b] sits at

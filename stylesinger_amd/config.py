@@ -55,6 +55,8 @@ DEFAULT_HPARAMS = dict(
     use_gt_f0=False,
     # not a reference key: frame bucket of the hipGraph / plan cache (StyleSingerHIP.t_bucket)
     t_bucket=64,
+    # not a reference key: write the result at this BS.1770 integrated loudness in LUFS (loudness.py; None = as synthesised). Excludes out_wav_norm.
+    out_loudness_lufs=None,
 )
 
 # The released HiFi-GAN config ships only inside the un-vendored checkpoint

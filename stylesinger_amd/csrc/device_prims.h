@@ -34,6 +34,18 @@ __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
+// Wave-wide reductions (64 lanes, xor butterfly: every lane ends with the result, and the order of the additions is fixed)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
 // LDS-DMA of 64 x 16 bytes: lane i's 16 bytes land at lds_dst + 16 i (wave-uniform destination, per-lane source offset).
 // (A __device__ helper on purpose: with the builtin written directly inside the templated __global__ body, the host pass of hipcc
 //  (ROCm 7.2) silently drops the kernel's launch stub and the library no longer links.)

@@ -28,8 +28,10 @@ from .vocoder import get_vocoder_cls
 
 class StyleSingerInfer:
     def __init__(self, hparams=None, device=None, model_state=None, vocoder_state=None, vocoder_config=None, dictionary=None,
-                 emotion_state=None, speaker_state=None, phone_set=None):
-        """`emotion_state`: state_dict of the reference's emotion encoder checkpoint (`EmotionEncoder.load_model`,
+                 emotion_state=None, speaker_state=None, phone_set=None, loudness=None):
+        """`loudness`: "bs1770" = honour hparams['loud_norm'] with this project's BS.1770 meter (`loudness.py`; parity with pyloudnorm UNPINNED, so
+        the bare flag stays refused: `loudness.resolve_loudness`).
+        `emotion_state`: state_dict of the reference's emotion encoder checkpoint (`EmotionEncoder.load_model`,
         inference/StyleSinger.py:101) - enables the emotion branch of `preprocess_batch`.
         `speaker_state`: `model_state` of resemblyzer's `pretrained.pt` (`VoiceEncoder()`, inference/StyleSinger.py:100) - enables the
         speaker branch."""
@@ -46,10 +48,10 @@ class StyleSingerInfer:
             self.ph_encoder = build_token_encoder(phone_set)
             if dictionary is None:
                 dictionary = self.ph_encoder
-        if hparams and hparams.get("loud_norm"):
-            # process_audio passes loud_norm to librosa_wav2spec (inference/StyleSinger.py:85; utils/audios/__init__.py:55-59: pyloudnorm, un-vendored)
-            raise NotImplementedError("hparams['loud_norm'] is set: the pyloudnorm loudness normalisation of the reference mel is not implemented "
-                                      "(the released config leaves it off); refusing rather than computing a different mel")
+        from .loudness import resolve_loudness
+        self._loud_norm = resolve_loudness(hparams, loudness)   # refuses the bare flag, before a device is touched
+        if self.hparams.get("out_loudness_lufs") is not None and (self.hparams.get("out_wav_norm") or (hparams or {}).get("out_wav_norm")):
+            raise ValueError("hparams: out_loudness_lufs and out_wav_norm exclude each other (a loudness target or peak normalisation, not both)")
         if device is None:
             if not torch.cuda.is_available():
                 raise L.StyleSingerHipError("StyleSingerInfer (HIP) needs a GPU: there is no CPU path")
@@ -75,7 +77,7 @@ class StyleSingerInfer:
             self.speaker_encoder = SpeakerEncoderHIP(speaker_state, device=self.device)
 
     @classmethod
-    def from_checkpoints(cls, hparams, exp_dir, vocoder_dir, device=None, dictionary=None):
+    def from_checkpoints(cls, hparams, exp_dir, vocoder_dir, device=None, dictionary=None, loudness=None):
         """Build from the reference's on-disk checkpoints (inference/StyleSinger.py:34-39 + hifigan_nsf.py:46-61):
         `exp_dir` = checkpoints/<exp_name> (newest model_ckpt_steps_*.ckpt), `vocoder_dir` = hparams['vocoder_ckpt']."""
         from . import ckpt
@@ -83,7 +85,7 @@ class StyleSingerInfer:
         if state is None:
             raise FileNotFoundError(f"| ckpt not found in {exp_dir}.")
         vstate, vcfg = ckpt.load_vocoder_ckpt(vocoder_dir)
-        return cls(hparams, device=device, model_state=state, vocoder_state=vstate, vocoder_config=vcfg, dictionary=dictionary)
+        return cls(hparams, device=device, model_state=state, vocoder_state=vstate, vocoder_config=vcfg, dictionary=dictionary, loudness=loudness)
 
     def build_model(self, dictionary=None, state=None):
         model = StyleSingerHIP(dictionary, hparams=self.hparams)
@@ -93,11 +95,12 @@ class StyleSingerInfer:
 
     # ---- batched, device resident -------------------------------------------------------------
     @torch.no_grad()
-    def infer_batch(self, batch, noise=None, vocoder_noise=None, seed=None, vocode=True, plan_slot=0):
+    def infer_batch(self, batch, noise=None, vocoder_noise=None, seed=None, vocode=True, plan_slot=0, out_lufs=None):
         """batch: dict of device tensors (txt_tokens, note, note_dur, note_type, spk_embed, emo_embed, ref_mels,
         ref_f0, optional mel2ph).  Returns dict(mel [B,T,80], f0 [B,T], lens int32 [B], wav [B,T*hop]).
         Pitch control (StyleSingerHIP.forward): optional `f0` + `uv` [B, T] (the normalised contour, the reference's use_gt_f0 form), or
-        `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted."""
+        `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted.
+        `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain)."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
         pitch = {k: batch[k] for k in ("pitch_hz", "pitch_shift") if batch.get(k) is not None}
@@ -108,7 +111,19 @@ class StyleSingerInfer:
         res = dict(mel=out["mel_out"], f0=out["f0_denorm"], lens=out["lens"], model_out=out)
         if vocode:
             res["wav"] = self.vocode(out["mel_out"], out["f0_denorm"], out["lens"], noise=vocoder_noise, seed=seed + 101)
+            if out_lufs is not None:
+                res["wav"], res["lufs"] = self._to_lufs(res["wav"], [int(v) * self.vocoder.model.hop for v in out["lens"].cpu()], out_lufs)
         return res
+
+    def _to_lufs(self, wav, lens, target):
+        """The output loudness target (hparams['out_loudness_lufs'], `infer_batch(out_lufs=)`): wav [B, L] on the device, lens host ints ->
+        (every item at `target` LUFS, divided by its peak where that exceeds 1; lufs [B] float64 = the loudness measured before the gain). An
+        item shorter than one 0.4 s gating block has no loudness: it is returned untouched (lufs NaN), with one warning per call."""
+        from .loudness import normalize_batch
+        y, m = normalize_batch(wav, lens, int(self.hparams["audio_sample_rate"]), target=float(target), short="skip")
+        if 0 in m["n_blocks"]:
+            warnings.warn(f"out_loudness_lufs: {m['n_blocks'].count(0)} item(s) shorter than one 0.4 s gating block left at their own level")
+        return y, m["lufs"]
 
     @torch.no_grad()
     def infer_batches(self, batches, in_flight=3, seed=None, vocode=True):
@@ -174,7 +189,7 @@ class StyleSingerInfer:
         from .writer import wav_to_pcm16
         if not (self.hparams.get("use_gt_f0") and batch.get("f0") is not None and batch.get("uv") is not None):
             batch = {k: v for k, v in batch.items() if k not in ("f0", "uv")}
-        res = self.infer_batch(batch, seed=seed)
+        res = self.infer_batch(batch, seed=seed, out_lufs=self.hparams.get("out_loudness_lufs"))
         self.model.check_finite(res["model_out"])
         hop = self.vocoder.model.hop
         pcm = wav_to_pcm16(res["wav"], res["lens"], hop, norm=bool(self.hparams.get("out_wav_norm", False)))
@@ -301,13 +316,17 @@ class StyleSingerInfer:
 
     @torch.no_grad()
     def preprocess_batch(self, ref_wavs, ref_lens, spk_embed, f0_hz, txt_tokens, note, note_dur, note_type, mel2ph=None,
-                         emo_embed=None, emo_wavs=None, emo_lens=None, emo_vad_flags=None, ref_srs=None):
+                         emo_embed=None, emo_wavs=None, emo_lens=None, emo_vad_flags=None, ref_srs=None, loud_norm=None):
         """Batched device form of `preprocess_input` + `input_to_batch` (inference/StyleSinger.py:94-172): from reference audio to
         the dict `infer_batch` takes, with no host round trip of the data.
           ref_wavs [B, L] fp32 reference audio (zero beyond ref_lens[b]; ref_lens host ints)          -> ref_mels  (process_audio, :106-118)
                    at the model's sample rate, or at the per-item rates `ref_srs` (host ints): items of another rate are resampled on the
                    device first, as `librosa.core.load(path, sr=audio_sample_rate)` does (utils/audios/__init__.py:52; `resample.py`, parity
                    UNPINNED), one launch per distinct rate; None or all equal to the model's rate = no resampling
+          loud_norm None = the instance's resolved switch (hparams['loud_norm'] with `loudness="bs1770"`), or True / False: the audio at the model's
+                   rate is brought to -22 LUFS and divided by its peak where that exceeds 1 (utils/audios/__init__.py:56-61; `loudness.py`, parity
+                   with pyloudnorm UNPINNED) before the mel, the f0 tracker and the speaker encoder see it - what `process_audio` returns. The
+                   default emotion branch keeps the un-normalised audio: `preprocess_wav(ref_audio)` reloads the file (:105)
           f0_hz    [B, Tr] tracker contour in Hz aligned to the mel frames (align_f0_to_mel), 0 = unvoiced -> ref_f0 (norm_interp_f0, :152);
                    None -> tracked on the device from `process_audio`'s waveform as :112-135 does with parselmouth (`f0track.py`: Praat's
                    published autocorrelation method, 80-800 Hz, voicing threshold 0.6; parity UNPINNED - parselmouth is un-vendored)
@@ -331,6 +350,10 @@ class StyleSingerInfer:
         ref_wavs = ref_wavs.to(d).float()
         if ref_srs is not None and any(int(r) != int(self.hparams["audio_sample_rate"]) for r in ref_srs):
             ref_wavs, ref_lens_h = self._resample_refs(ref_wavs, ref_lens_h, ref_srs)
+        raw_wavs = ref_wavs
+        if self._loud_norm if loud_norm is None else loud_norm:
+            from .loudness import normalize_batch
+            ref_wavs, _ = normalize_batch(ref_wavs, ref_lens_h, int(self.hparams["audio_sample_rate"]))
         ref_mels, frames = self._mel_frontend.wav2mel(ref_wavs, torch.tensor(ref_lens_h, dtype=torch.int64))
         Tr = ref_mels.shape[1]
         hop = int(self.hparams["hop_size"])
@@ -349,7 +372,7 @@ class StyleSingerInfer:
                 if self._emo_frontend is None:
                     from .frontend import EmotionMelFrontendHIP
                     self._emo_frontend = EmotionMelFrontendHIP(d)
-                emo_wavs = self._emo_frontend.normalize_volume(ref_wavs, torch.tensor(ref_lens_h))
+                emo_wavs = self._emo_frontend.normalize_volume(raw_wavs, torch.tensor(ref_lens_h))
                 emo_lens = ref_lens_h
                 if isinstance(emo_vad_flags, str):
                     if emo_vad_flags != "webrtc":
@@ -544,6 +567,9 @@ class StyleSingerInfer:
         else:
             ins = cls(hparams, **ctor)
         out = ins.infer_once(inp, vad_flags=vad_flags)
+        if ins.hparams.get("out_loudness_lufs") is not None:
+            y, _ = ins._to_lufs(torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32))[None].to(ins.device), [len(out)], ins.hparams["out_loudness_lufs"])
+            out = y[0].cpu().numpy()
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         save_wav(out, out_path, int(ins.hparams["audio_sample_rate"]), norm=bool(ins.hparams.get("out_wav_norm", False)))
         print(f"Save at {out_path}.")
@@ -554,7 +580,8 @@ def main(argv=None):
     """`python -m stylesinger_amd.infer --exp-dir checkpoints/<exp> --vocoder-dir <hifigan dir> --emotion-ckpt <pt> --speaker-ckpt <pt>
     --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim]` = the reference's
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
-    sing the score on a given pitch contour instead of the predicted one."""
+    sing the score on a given pitch contour instead of the predicted one. `--loud-norm`: loudness-normalise the reference audio as a model trained with
+    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS."""
     import argparse
     ap = argparse.ArgumentParser(description="StyleSinger example_run on the HIP path")
     ap.add_argument("--exp-dir", required=True)
@@ -568,6 +595,9 @@ def main(argv=None):
     ap.add_argument("--pitch-audio", help="sing on the pitch of this guide vocal (a WAV file, tracked on the device, 80-800 Hz) instead of the predicted f0")
     ap.add_argument("--pitch-npy", help="sing on this contour: a .npy file holding a 1-D array of Hz at the mel hop, 0 = unvoiced")
     ap.add_argument("--pitch-shift", type=float, help="transpose the given contour by this many semitones")
+    ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
+                    "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
+    ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
     a = ap.parse_args(argv)
     if a.pitch_audio and a.pitch_npy:
         ap.error("--pitch-audio and --pitch-npy exclude each other")
@@ -587,9 +617,14 @@ def main(argv=None):
     if state is None:
         raise FileNotFoundError(f"| ckpt not found in {a.exp_dir}.")
     vstate, vcfg = ckpt.load_vocoder_ckpt(a.vocoder_dir)
-    StyleSingerInfer.example_run(None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, pitch=pitch, model_state=state, vocoder_state=vstate,
-                                 vocoder_config=vcfg, emotion_state=emo.get("model_state", emo), speaker_state=spk.get("model_state", spk),
-                                 phone_set=a.phone_set)
+    hp = {}
+    if a.loud_norm:
+        hp["loud_norm"] = True
+    if a.out_lufs is not None:
+        hp["out_loudness_lufs"] = a.out_lufs
+    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, pitch=pitch, model_state=state,
+                                 vocoder_state=vstate, vocoder_config=vcfg, emotion_state=emo.get("model_state", emo),
+                                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
 
 
 if __name__ == "__main__":

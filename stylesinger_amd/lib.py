@@ -123,7 +123,7 @@ class F0TrackParams(C.Structure):
 
 
 _CTYPE = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32,
-          "float": C.c_float, "void": None}
+          "float": C.c_float, "double": C.c_double, "void": None}
 
 
 def declarations():
