@@ -34,8 +34,8 @@ const char* ss_last_error(void);
 int ss_abi_version(void);
 /* number of compute units / name of device `dev` (sanity: must be gfx950) */
 int ss_device_info(int dev, int* n_cu, char* arch, int arch_len);
-/* out[0..2] = sizeof(ss_conv_gemm_args), sizeof(ss_wavenet), sizeof(ss_hifigan) (+ out[3] = sizeof(ss_gemm_bf16_args) when n >= 4):
- * lets a binding verify its mirror */
+/* out[0..5] = sizeof of ss_conv_gemm_args, ss_wavenet, ss_hifigan, ss_gemm_bf16_args, ss_f0track_params, ss_layer512_args, in that order
+ * (n >= 3; entries 3, 4 and 5 are written when n >= 4, 5 and 6): lets a binding verify the structs it passes */
 int ss_struct_sizes(int64_t* out, int n);
 /* process-wide performance knobs (results never change): "gate16" = 0|1|2|3 tiling of the F(4,3) gate launches inside the
  * denoiser loops (1 = per-launch pick, default; 0 = 32x32x2 tiles; 2|3 = force 16x16x4 tiles of 16*MT quads); "gate16_ks" = 0|1

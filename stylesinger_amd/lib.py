@@ -6,152 +6,29 @@ for device memory (`tensor.data_ptr()`) and streams.
 """
 import ctypes as C
 import os
-import re
 
 import torch
 
+from . import abi
+from .abi import declarations, declared_symbols  # noqa: F401  (part of this module's surface)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SS_LIB_PATH") or os.path.join(HERE, "libstylesinger_hip.so")  # SS_LIB_PATH: debug builds (tools/reproduce.sh trace-layer512)
-HEADER = os.path.join(os.path.dirname(HERE), "include", "stylesinger_hip.h")
 
-SS_MAX_TAPS = 16
-SS_MAX_LAYERS = 32
-SS_HG_MAX_UPS = 6
-SS_HG_MAX_KERNELS = 4
+# The C-ABI is read from the header by abi.py: constants, enumerators, struct layouts and prototypes. Nothing below restates it.
+SS_MAX_TAPS, SS_MAX_LAYERS, SS_HG_MAX_UPS, SS_HG_MAX_KERNELS = (abi.DEFINES[n] for n in ("SS_MAX_TAPS", "SS_MAX_LAYERS", "SS_HG_MAX_UPS", "SS_HG_MAX_KERNELS"))
+ABI_VERSION = abi.DEFINES["SS_ABI_VERSION"]
+EPI_STORE, EPI_GATE, EPI_RESSKIP, EPI_DDPM = (abi.ENUMS["SS_EPI_" + n] for n in ("STORE", "GATE", "RESSKIP", "DDPM"))
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_MISH, ACT_TANH, ACT_LRELU = (abi.ENUMS[f"SS_ACT_{n}_"] for n in ("NONE", "RELU", "GELU", "MISH", "TANH", "LRELU"))
+HEPI_STORE, HEPI_GATE, HEPI_RESX = (abi.ENUMS["SS_HEPI_" + n] for n in ("STORE", "GATE", "RESX"))
 
-ABI_VERSION = 20  # include/stylesinger_hip.h SS_ABI_VERSION
-EPI_STORE, EPI_GATE, EPI_RESSKIP, EPI_DDPM = 0, 1, 2, 3
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_MISH, ACT_TANH, ACT_LRELU = 0, 1, 2, 3, 4, 5
-
-_fp = C.POINTER(C.c_float)
-_vp = C.c_void_p
+# the C structs in the positional order of ss_struct_sizes (csrc/api.hip), and the names their ctypes classes have here
+_STRUCT_SIZES_ORDER = ("ss_conv_gemm_args", "ss_wavenet", "ss_hifigan", "ss_gemm_bf16_args", "ss_f0track_params", "ss_layer512_args")
+ConvGemmArgs, WaveNet, HifiGan, GemmBf16Args, F0TrackParams, Layer512Args = (abi.STRUCTURES[n] for n in _STRUCT_SIZES_ORDER)
 
 
 class StyleSingerHipError(RuntimeError):
     pass
-
-
-class ConvGemmArgs(C.Structure):
-    _fields_ = [
-        ("A", _vp), ("a_batch_stride", C.c_int64), ("lda", C.c_int32), ("Cin", C.c_int32), ("ntaps", C.c_int32),
-        ("tap_off", C.c_int32 * SS_MAX_TAPS), ("lens", _vp), ("B", C.c_int32), ("T", C.c_int32), ("a_bias", _vp),
-        ("a_scale", C.c_float), ("a_lrelu", C.c_float),
-        ("W", _vp), ("N", C.c_int32), ("Np", C.c_int32), ("Kp", C.c_int32),
-        ("epi", C.c_int32), ("bias", _vp), ("pre_scale", C.c_float), ("act", C.c_int32), ("act_slope", C.c_float),
-        ("E", _vp), ("lde", C.c_int32), ("e_batch_stride", C.c_int64), ("gate_mode", C.c_int32),
-        ("R", _vp), ("ldr", C.c_int32), ("r_batch_stride", C.c_int64), ("post_scale", C.c_float),
-        ("accumulate", C.c_int32), ("mask_rows", C.c_int32),
-        ("C", _vp), ("ldc", C.c_int32), ("c_batch_stride", C.c_int64),
-        ("C2", _vp), ("ldc2", C.c_int32), ("c2_batch_stride", C.c_int64), ("Nh", C.c_int32),
-        ("ddpm_recip", C.c_float), ("ddpm_recipm1", C.c_float), ("ddpm_c1", C.c_float), ("ddpm_c2", C.c_float),
-        ("ddpm_sigma", C.c_float), ("noise", _vp), ("seed", C.c_uint64), ("seed_dev", _vp), ("step", C.c_uint32), ("tile", C.c_int32),
-        ("group_size", C.c_int32), ("w_group_stride", C.c_int64), ("bias_group_stride", C.c_int64), ("a_bias_group_stride", C.c_int64),
-        ("mfma_bf16", C.c_int32), ("ddpm_x0_pred", C.c_int32), ("e_tiled", C.c_int32), ("reserved2_", C.c_int32),
-    ]
-
-
-class WaveNet(C.Structure):
-    _fields_ = [
-        ("C", C.c_int32), ("L", C.c_int32), ("cond_dim", C.c_int32), ("dil_cycle", C.c_int32), ("in_dim", C.c_int32),
-        ("out_dim", C.c_int32), ("steps", C.c_int32),
-        ("w_in", _vp), ("b_in", _vp), ("uv_embed", _vp), ("dstep", _vp),
-        ("w_dil", _vp * SS_MAX_LAYERS), ("w_out", _vp * SS_MAX_LAYERS), ("b_out", _vp * SS_MAX_LAYERS),
-        ("w_cond", _vp), ("b_cond", _vp), ("w_skip", _vp), ("b_skip", _vp), ("w_final", _vp), ("b_final", _vp),
-        ("sqrt_recip_ac", _vp), ("sqrt_recipm1_ac", _vp), ("post_c1", _vp), ("post_c2", _vp), ("post_logvar", _vp),
-        ("log_alpha", _vp), ("log_1m_alpha", _vp), ("log_cumprod_alpha", _vp), ("log_1m_cumprod_alpha", _vp),
-        ("n_groups", C.c_int32), ("w_dil_wino", _vp * SS_MAX_LAYERS), ("gs_w_dil_wino", C.c_int64),
-    ] + [(n, C.c_int64) for n in ("gs_w_in", "gs_b_in", "gs_uv_embed", "gs_dstep", "gs_w_dil", "gs_w_out", "gs_b_out", "gs_w_cond",
-                                  "gs_b_cond", "gs_w_skip", "gs_b_skip", "gs_w_final", "gs_b_final")] \
-        + [("mfma_bf16", C.c_int32), ("wino_m", C.c_int32), ("w_skipall", _vp), ("b_skipall", _vp),
-           ("gs_w_skipall", C.c_int64), ("gs_b_skipall", C.c_int64), ("skipall_folded", C.c_int32), ("mfma_x3", C.c_int32),
-           ("w_dil_h", _vp * SS_MAX_LAYERS), ("w_out_h", _vp * SS_MAX_LAYERS), ("w_skipall_h", _vp), ("w_cond_h", _vp),
-           ("gs_w_dil_h", C.c_int64), ("gs_w_out_h", C.c_int64), ("gs_w_skipall_h", C.c_int64), ("gs_w_cond_h", C.c_int64),
-           ("w_dil_x3", _vp * SS_MAX_LAYERS), ("gs_w_dil_x3", C.c_int64), ("w_dil_wino16", _vp * SS_MAX_LAYERS),
-           ("w_out16", _vp * SS_MAX_LAYERS), ("gs_w_out16", C.c_int64), ("w_skipall_x3", _vp), ("gs_w_skipall_x3", C.c_int64),
-           ("mfma_split", C.c_int32), ("mfma_out_scale", C.c_float),
-           ("w_dil_q", _vp * SS_MAX_LAYERS), ("gs_w_dil_q", C.c_int64), ("q_scale_gate", C.c_float), ("q_scale_z", C.c_float),
-           ("w_skipall_q", _vp), ("gs_w_skipall_q", C.c_int64),
-           ("w_dil_f", _vp * SS_MAX_LAYERS), ("w_out_f", _vp * SS_MAX_LAYERS),
-           ("n_wsets", C.c_int32), ("mfma_products", C.c_int32)] + [(n, C.c_int64) for n in ("ws_w_dil_h", "ws_w_out_h", "ws_w_skipall_h", "ws_w_dil_f", "ws_w_out_f")] \
-        + [("w_skipall_c", _vp), ("ws_w_skipall_c", C.c_int64), ("n_esets", C.c_int32), ("reserved3_", C.c_int32)]
-
-
-class GemmBf16Args(C.Structure):
-    _fields_ = [
-        ("A", _vp), ("a_batch_stride", C.c_int64), ("lda", C.c_int32), ("K", C.c_int32), ("ntaps", C.c_int32), ("tap_off", C.c_int32 * 4),
-        ("lens", _vp), ("B", C.c_int32), ("T", C.c_int32), ("W", _vp), ("w_group_stride", C.c_int64), ("N", C.c_int32), ("Np", C.c_int32),
-        ("epi", C.c_int32), ("act", C.c_int32), ("bias", _vp), ("bias_group_stride", C.c_int64), ("E", _vp), ("lde", C.c_int32),
-        ("gate_mode", C.c_int32), ("e_batch_stride", C.c_int64), ("X", _vp), ("x_batch_stride", C.c_int64), ("ldx", C.c_int32),
-        ("post_scale", C.c_float), ("next_bias", _vp), ("next_bias_group_stride", C.c_int64), ("Y", _vp), ("y_batch_stride", C.c_int64),
-        ("ldy", C.c_int32), ("ldc", C.c_int32), ("C", _vp), ("c_batch_stride", C.c_int64), ("mask_rows", C.c_int32), ("group_size", C.c_int32),
-        ("split", C.c_int32), ("out_scale", C.c_float), ("q_scale", C.c_float), ("one_product", C.c_int32), ("cur_bias", _vp), ("cur_bias_group_stride", C.c_int64),
-        ("a_compact", C.c_int32), ("reserved2_", C.c_int32),
-    ]
-
-
-HEPI_STORE, HEPI_GATE, HEPI_RESX = 0, 1, 2
-
-
-class Layer512Args(C.Structure):
-    _fields_ = [
-        ("Hin", _vp), ("d", C.c_int32), ("n_products", C.c_int32), ("Hout", _vp), ("P", _vp),
-        ("lens", _vp), ("B", C.c_int32), ("T", C.c_int32), ("Wg", _vp), ("Wr", _vp), ("E512", _vp), ("G", _vp), ("g_batch_stride", C.c_int64),
-        ("ldg", C.c_int32), ("mask_rows", C.c_int32), ("bias_r", _vp), ("next_bias", _vp), ("g_compact", C.c_int32), ("e_f16", C.c_int32), ("out_scale", C.c_float),
-        ("post_scale", C.c_float), ("cur_bias", _vp),
-    ]
-
-
-class HifiGan(C.Structure):
-    _fields_ = [
-        ("n_ups", C.c_int32), ("n_kernels", C.c_int32), ("c0", C.c_int32), ("sr", C.c_int32), ("harmonics", C.c_int32),
-        ("up_rate", C.c_int32 * SS_HG_MAX_UPS), ("up_k", C.c_int32 * SS_HG_MAX_UPS),
-        ("rb_k", C.c_int32 * SS_HG_MAX_KERNELS), ("rb_d", (C.c_int32 * 3) * SS_HG_MAX_KERNELS),
-        ("w_pre", _vp), ("b_pre", _vp),
-        ("w_up", (_vp * 2) * SS_HG_MAX_UPS), ("b_up", _vp * SS_HG_MAX_UPS),
-        ("w_noise", _vp * SS_HG_MAX_UPS), ("b_noise", _vp * SS_HG_MAX_UPS),
-        ("w_rb1", ((_vp * 3) * SS_HG_MAX_KERNELS) * SS_HG_MAX_UPS), ("b_rb1", ((_vp * 3) * SS_HG_MAX_KERNELS) * SS_HG_MAX_UPS),
-        ("w_rb2", ((_vp * 3) * SS_HG_MAX_KERNELS) * SS_HG_MAX_UPS), ("b_rb2", ((_vp * 3) * SS_HG_MAX_KERNELS) * SS_HG_MAX_UPS),
-        ("w_post", _vp), ("b_post", _vp), ("src_w", _vp), ("src_b", _vp), ("mfma_bf16", C.c_int32), ("wino", C.c_int32),
-        ("w_rb1_wino", ((_vp * 3) * SS_HG_MAX_KERNELS) * SS_HG_MAX_UPS), ("w_rb2_wino", ((_vp * 3) * SS_HG_MAX_KERNELS) * SS_HG_MAX_UPS),
-    ]
-
-
-class F0TrackParams(C.Structure):
-    _fields_ = [(n, C.c_double) for n in ("sample_rate", "time_step", "pitch_floor", "pitch_ceiling", "voicing_threshold", "silence_threshold",
-                                          "octave_cost", "octave_jump_cost", "voiced_unvoiced_cost")] \
-        + [(n, C.c_int32) for n in ("nsamp_window", "halfnsamp_window", "nsamp_period", "halfnsamp_period", "maximum_lag", "nlag", "hop", "reserved_")]
-
-
-_CTYPE = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32,
-          "float": C.c_float, "double": C.c_double, "void": None}
-
-
-def declarations():
-    """{name: (restype, [argtypes])} parsed from the public header, so the binding cannot drift from it."""
-    txt = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
-    txt = re.sub(r"//[^\n]*", " ", txt)
-    out = {}
-    for m in re.finditer(r"(const\s+char\s*\*|int64_t|int)\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", txt, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        restype = C.c_char_p if "char" in ret else _CTYPE[ret]
-        argtypes = []
-        if args and args != "void":
-            for a in args.split(","):
-                a = a.strip()
-                if "*" in a:
-                    argtypes.append(C.c_void_p)
-                else:
-                    base = [t for t in a.replace("const", " ").split() if t in _CTYPE]
-                    assert base, f"cannot parse parameter '{a}' of {name}"
-                    argtypes.append(_CTYPE[base[0]])
-        out[name] = (restype, argtypes)
-    return out
-
-
-def declared_symbols():
-    """Every `ss_*` function the public header declares."""
-    return sorted(declarations())
 
 
 _lib = None
@@ -175,12 +52,12 @@ def load():
         fn.argtypes = argtypes
     if lib.ss_abi_version() != ABI_VERSION:
         raise StyleSingerHipError(f"libstylesinger_hip.so has ABI {lib.ss_abi_version()}, this binding expects {ABI_VERSION}: rebuild it")
-    sizes = (C.c_int64 * 6)()
-    if lib.ss_struct_sizes(sizes, 6) != 0:
+    sizes = (C.c_int64 * len(_STRUCT_SIZES_ORDER))()
+    if lib.ss_struct_sizes(sizes, len(sizes)) != 0:
         raise StyleSingerHipError("ss_struct_sizes failed")
-    mine = (C.sizeof(ConvGemmArgs), C.sizeof(WaveNet), C.sizeof(HifiGan), C.sizeof(GemmBf16Args), C.sizeof(F0TrackParams), C.sizeof(Layer512Args))
-    if tuple(sizes) != mine:
-        raise StyleSingerHipError(f"ctypes mirror out of sync with include/stylesinger_hip.h: C={tuple(sizes)} py={mine}")
+    for name, c_size in zip(_STRUCT_SIZES_ORDER, sizes):
+        if C.sizeof(abi.STRUCTURES[name]) != c_size:
+            raise StyleSingerHipError(f"{name}: {C.sizeof(abi.STRUCTURES[name])} bytes as read from include/stylesinger_hip.h, {c_size} in libstylesinger_hip.so: rebuild it")
     _lib = lib
     for env, key in (("SS_GATE16", b"gate16"), ("SS_GATE16_KS", b"gate16_ks"), ("SS_GATE256", b"gate256"), ("SS_MEL_TAIL", b"mel_tail"), ("SS_GATE128", b"gate128"),
                      ("SS_Q4_FORCE", b"q4_force"), ("SS_SKIP_DENSE", b"skip_dense"), ("SS_LAYER512", b"layer512"), ("SS_LAYER512_TAIL", b"layer512_tail")):

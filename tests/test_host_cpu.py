@@ -4,12 +4,13 @@ deterministic, and the product refuses to run without a GPU instead of falling b
 import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from stylesinger_amd import config, lib, spec, synth
+from stylesinger_amd import abi, config, lib, spec, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,9 +28,95 @@ def test_library_loads_at_abi_20_and_exports_header_symbols():
 def test_ctypes_struct_mirror_matches_c():
     import ctypes
     l = lib.load()
-    sizes = (ctypes.c_int64 * 3)()
-    assert l.ss_struct_sizes(sizes, 3) == 0
-    assert tuple(sizes) == (ctypes.sizeof(lib.ConvGemmArgs), ctypes.sizeof(lib.WaveNet), ctypes.sizeof(lib.HifiGan))
+    sizes = (ctypes.c_int64 * 6)()
+    assert l.ss_struct_sizes(sizes, 6) == 0
+    assert tuple(sizes) == tuple(ctypes.sizeof(c) for c in (lib.ConvGemmArgs, lib.WaveNet, lib.HifiGan, lib.GemmBf16Args, lib.F0TrackParams, lib.Layer512Args))
+    assert tuple(sizes) == (400, 3616, 3888, 264, 104, 136)
+
+
+STRUCT_FIELDS = {"ss_conv_gemm_args": 56, "ss_wavenet": 89, "ss_gemm_bf16_args": 43, "ss_layer512_args": 22, "ss_hifigan": 27, "ss_f0track_params": 17}
+
+
+def test_every_struct_field_has_the_c_compilers_offset_and_size(tmp_path):
+    """abi.STRUCTS (read from the header) against the host C compiler: a C99 program generated from the parsed field NAMES prints sizeof of every
+    struct and offsetof / sizeof of every member of include/stylesinger_hip.h; the ctypes classes must agree on all of them, which two swapped
+    fields of one width or an array nested the wrong way round would not."""
+    import ctypes
+    assert set(abi.STRUCTS) >= set(STRUCT_FIELDS)
+    assert {n: len(abi.STRUCTS[n]) for n in STRUCT_FIELDS} == STRUCT_FIELDS
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "stylesinger_hip.h"', 'int main(void) {']
+    for name, fields in abi.STRUCTS.items():
+        lines.append(f'  printf("{name} - %zu 0\\n", sizeof({name}));')
+        lines += [f'  printf("{name} {f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, _ in fields]
+    src, exe = tmp_path / "abi_layout.c", str(tmp_path / "abi_layout")
+    src.write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    r = subprocess.run(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0
+    c_side = [tuple(ln.split()[:2]) + tuple(int(v) for v in ln.split()[2:]) for ln in r.stdout.splitlines()]
+    py_side = []
+    for name, fields in abi.STRUCTS.items():
+        cls = abi.STRUCTURES[name]
+        py_side.append((name, "-", ctypes.sizeof(cls), 0))
+        py_side += [(name, f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in fields]
+    assert len(py_side) == len(abi.STRUCTS) + sum(len(f) for f in abi.STRUCTS.values()) >= 6 + 254
+    assert py_side == c_side, [(p, c) for p, c in zip(py_side, c_side) if p != c][:5]
+
+
+def test_parsed_array_shapes_and_constants():
+    import ctypes
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    assert dict(lib.WaveNet._fields_)["w_dil"] is vp * 32
+    assert dict(lib.HifiGan._fields_)["rb_d"] is (i32 * 3) * 4
+    hg = lib.HifiGan()
+    assert (len(hg.w_rb1), len(hg.w_rb1[0]), len(hg.w_rb1[0][0])) == (6, 4, 3) and dict(lib.HifiGan._fields_)["w_rb1"] is ((vp * 3) * 4) * 6
+    hg.w_rb1[5][3][2] = 7      # the last element: the three-level indexing stylesinger_amd/vocoder.py uses
+    assert ctypes.cast(ctypes.byref(hg, lib.HifiGan.w_rb1.offset), ctypes.POINTER(vp))[6 * 4 * 3 - 1] == 7
+    assert len(lib.ConvGemmArgs().tap_off) == 16 and len(lib.GemmBf16Args().tap_off) == 4
+    assert (lib.SS_MAX_TAPS, lib.SS_MAX_LAYERS, lib.SS_HG_MAX_UPS, lib.SS_HG_MAX_KERNELS) == (16, 32, 6, 4)
+    assert lib.ABI_VERSION == 20 == abi.DEFINES["SS_ABI_VERSION"]
+    assert (lib.EPI_STORE, lib.EPI_GATE, lib.EPI_RESSKIP, lib.EPI_DDPM) == (0, 1, 2, 3)
+    assert (lib.ACT_NONE, lib.ACT_RELU, lib.ACT_GELU, lib.ACT_MISH, lib.ACT_TANH, lib.ACT_LRELU) == (0, 1, 2, 3, 4, 5)
+    assert (lib.HEPI_STORE, lib.HEPI_GATE, lib.HEPI_RESX) == (0, 1, 2)
+    assert [abi.ENUMS[n] for n in ("SS_TILE_AUTO", "SS_TILE_128x128", "SS_TILE_64x128", "SS_TILE_64x64", "SS_TILE_128x64", "SS_TILE_128x32")] == [0, 1, 2, 3, 4, 5]
+    assert lib.declarations is abi.declarations and lib.declared_symbols is abi.declared_symbols
+
+
+@pytest.mark.parametrize("what,snippet,offending", [
+    ("unknown base type", "typedef struct s { int32_t a; unsigned b; } s;", "unsigned b"),
+    ("unknown base type", "typedef struct s { uint16_t h; } s;", "uint16_t h"),          # uint16_t and void only behind a pointer
+    ("bit-field", "typedef struct s { int32_t a : 3; } s;", "int32_t a : 3"),
+    ("nested struct", "typedef struct s { struct { int32_t a; } in; int32_t b; } s;", "struct { int32_t a"),
+    ("nested union", "typedef struct s { int32_t t; union { float f; int32_t i; } u; } s;", "union { float f"),
+    ("preprocessor line", "typedef struct s {\n  int32_t a;\n#ifdef SS_WIDE\n  int64_t b;\n#endif\n} s;", "#ifdef SS_WIDE"),
+    ("dimension", "typedef struct s { float w[SS_NOT_DEFINED]; } s;", "float w[SS_NOT_DEFINED]"),
+    ("dimension", "typedef struct s { float w[SS_N + 1]; } s;", "float w[SS_N + 1]"),
+    ("mixed pointer list", "typedef struct s { const float* a, b; } s;", "const float* a, b"),
+    ("mixed pointer list", "typedef struct s { float a, *b; } s;", "float a, *b"),
+    ("four dimensions", "typedef struct s { float w[2][2][2][2]; } s;", "float w[2][2][2][2]"),
+])
+def test_struct_parser_refuses_what_it_cannot_read(what, snippet, offending):
+    with pytest.raises(abi.HeaderError) as e:
+        abi.parse_structs(snippet, {"SS_N": 4})
+    assert offending in str(e.value), (what, str(e.value))
+
+
+def test_struct_parser_reads_the_accepted_grammar_and_requires_enum_values():
+    import ctypes
+    got = abi.parse_structs("typedef struct s {\n  const float* p, *q[2];\n  int32_t a, b[SS_N], c[2][3];\n  double d;\n  void* v;\n} s;", {"SS_N": 4})
+    vp = ctypes.c_void_p
+    assert got == {"s": [("p", vp), ("q", vp * 2), ("a", ctypes.c_int32), ("b", ctypes.c_int32 * 4), ("c", (ctypes.c_int32 * 3) * 2), ("d", ctypes.c_double), ("v", vp)]}
+    assert abi.parse_enums("enum { A = 0, B = 5 };") == {"A": 0, "B": 5}
+    with pytest.raises(abi.HeaderError) as e:
+        abi.parse_enums("enum { A = 0, B };")
+    assert "'B'" in str(e.value)
+
+
+def test_abi_module_imports_without_torch():
+    r = subprocess.run([sys.executable, "-c", "import sys; import stylesinger_amd.abi as a; assert len(a.STRUCTURES) >= 6; print('torch' in sys.modules)"],
+                       capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0 and r.stdout.strip() == "False", r.stdout + r.stderr[-2000:]
 
 
 def test_argument_errors_are_reported_not_crashed():
