@@ -91,9 +91,10 @@ def run_acoustic_case(name, B, T, Tp, Tr, steps_mel, steps_f0, give_mel2ph=True,
     print(f"[gen_golden] {name}: T_out={out['mel_out'].shape[1]} draws={len(tape.log)} keys={sorted(out)}")
 
 
-def run_vocoder_case(name, B, T, seed=1234):
+def run_vocoder_case(name, B, T, seed=1234, cfg_over=None):
+    """`cfg_over`: generator shape overrides (config.make_vocoder_config), kept in meta["cfg_over"] for harness.vocoder_case_setup."""
     R = refimport.load()
-    cfg = config.make_vocoder_config()
+    cfg = config.make_vocoder_config(cfg_over)
     gen = R["HifiGanGenerator"](cfg)
     vsd = synth.synth_vocoder_state_dict(cfg, seed)
     gen.load_state_dict(vsd, strict=True)
@@ -109,7 +110,7 @@ def run_vocoder_case(name, B, T, seed=1234):
     with torch.no_grad(), tape_rng(tape):
         wav = gen(mel.transpose(1, 2), f0)
     hook.remove()
-    torch.save(dict(meta=dict(B=B, T=T, seed=seed, tape_seed=seed + 2, tape_log=tape.log),
+    torch.save(dict(meta=dict(B=B, T=T, seed=seed, tape_seed=seed + 2, tape_log=tape.log, **(dict(cfg_over=dict(cfg_over)) if cfg_over else {})),
                     inp=dict(mel=mel, f0=f0), out=dict(wav=wav[:, 0].clone(), har=grabbed["har"][:, :, 0].clone())),
                os.path.join(GOLD, name + ".pt"))
     print(f"[gen_golden] {name}: wav {tuple(wav.shape)} draws={len(tape.log)}")
@@ -350,6 +351,12 @@ def main():
     run_vocoder_case("vocoder_t12", B=1, T=12)
     run_vocoder_case("vocoder_b2_t9", B=2, T=9)
     run_vocoder_case("vocoder_t200", B=1, T=200)   # 51 200 samples: the NSF phase integration and the 4-stage generator at a length where tile interiors exist
+    # the REAL reference at other generator shapes (tests/vocoder_shape_cases.py: hop 512 with five stages, hop 64 with two ResBlock kernels)
+    run_vocoder_case("vocoder_hop512_t6", B=1, T=6, cfg_over=dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4, 4],
+                                                                 audio_sample_rate=44100))
+    run_vocoder_case("vocoder_hop64_b2_t9", B=2, T=9, cfg_over=dict(
+        upsample_rates=[8, 8], upsample_kernel_sizes=[16, 16], upsample_initial_channel=128, audio_sample_rate=16000,
+        resblock_kernel_sizes=[3, 5], resblock_dilation_sizes=[[1, 2, 4], [1, 3, 5]]))
     run_plms_case("plms_t40_k20_i3", T=40, steps_mel=20, interval=3)
     run_plms_case("plms_t24_k12_i4", T=24, steps_mel=12, interval=4)
     round2_cases()

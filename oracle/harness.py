@@ -31,6 +31,6 @@ def run_restatement_case(meta):
 
 
 def vocoder_case_setup(meta):
-    cfg = config.make_vocoder_config()
+    cfg = config.make_vocoder_config(meta.get("cfg_over"))
     vsd = synth.synth_vocoder_state_dict(cfg, meta["seed"])
     return cfg, vsd

@@ -831,9 +831,12 @@ def nsf_source(vsd, cfg, f0, tape):
     return merged[:, :, 0]
 
 
-def hifigan_forward(vsd, cfg, mel, f0, tape):
-    """HifiGanGenerator.forward after remove_weight_norm. mel [B,T,80], f0 [B,T] Hz -> wav [B, T*hop], har [B,L]."""
-    har = nsf_source(vsd, cfg, f0, tape)
+def hifigan_forward(vsd, cfg, mel, f0, tape, har=None):
+    """HifiGanGenerator.forward after remove_weight_norm. mel [B,T,80], f0 [B,T] Hz -> wav [B, T*hop], har [B,L].
+    `har` given: the generator alone on that harmonic source (f0 and tape are not read), in the dtype of vsd / mel / har - the float64
+    yardstick of the vocoder shape tests is this function on float64 copies of the weights, the mel and the fp32 run's source."""
+    if har is None:
+        har = nsf_source(vsd, cfg, f0, tape)
     rates, ks = cfg["upsample_rates"], cfg["upsample_kernel_sizes"]
     nk = len(cfg["resblock_kernel_sizes"])
     x = F.conv1d(_r(mel.transpose(1, 2)), _r(weight_norm_fold(vsd, "conv_pre")), vsd["conv_pre.bias"], padding=3)

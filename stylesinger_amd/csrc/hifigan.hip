@@ -16,6 +16,7 @@ namespace {
 
 constexpr int NH = 9;      // fundamental + 8 overtones (hifigan_nsf.py:112)
 constexpr int HOP_MAX = 1024;
+constexpr size_t LDS_MAX = 160 * 1024;  // LDS of one CU: the most a workgroup can ask for
 
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int round_up32(int x) { return (x + 31) / 32 * 32; }
@@ -263,21 +264,25 @@ __global__ void src_final_kernel(const float* __restrict__ f0, const double* __r
 }
 
 // x[b][n][c] += bias[c] + sum_j w[c][j] * har[b][n*s - pad + j]      (noise_convs, hifigan_nsf.py:124-130,155-157)
+// blockIdx.y picks a chunk of Cc channels (the host sizes Cc so that the chunk's weights fit the LDS); a thread walks its chunk's channels in
+// steps of 256, so chunks wider than the workgroup are covered too. Every element is bias + sum_j in tap order, whatever the chunking.
 __global__ __launch_bounds__(256) void noise_conv_kernel(const float* __restrict__ har, const float* __restrict__ w,
                                                          const float* __restrict__ bias, float* __restrict__ x,
                                                          const int32_t* __restrict__ lens_out,
                                                          const int32_t* __restrict__ lens_samples, int B, int Tout,
-                                                         int64_t L, int C, int k, int s, int pad, int npos) {
+                                                         int64_t L, int C, int Cc, int k, int s, int pad, int npos) {
   extern __shared__ float smem[];
-  float* wsh = smem;             // [k][C]
-  float* hsh = smem + k * C;     // [npos*s + k]
+  const int cb = blockIdx.y * Cc;
+  const int cn = C - cb < Cc ? C - cb : Cc;
+  float* wsh = smem;             // [k][cn]
+  float* hsh = smem + k * Cc;    // [npos*s + k]
   const int tiles = (Tout + npos - 1) / npos;
   const int b = blockIdx.x / tiles;
   const int n0 = (blockIdx.x % tiles) * npos;
   const int tid = threadIdx.x;
-  for (int i = tid; i < k * C; i += 256) {
-    const int j = i / C, c = i % C;
-    wsh[i] = w[c * k + j];
+  for (int i = tid; i < k * cn; i += 256) {
+    const int j = i / cn, c = i % cn;
+    wsh[i] = w[(cb + c) * k + j];
   }
   const int64_t valid = lens_samples ? (int64_t)lens_samples[b] : L;
   const int seg = npos * s + k;
@@ -286,18 +291,19 @@ __global__ __launch_bounds__(256) void noise_conv_kernel(const float* __restrict
     hsh[i] = (idx >= 0 && idx < valid) ? har[(int64_t)b * L + idx] : 0.f;
   }
   __syncthreads();
-  const int groups = 256 / C > 0 ? 256 / C : 1;
-  const int c = tid % C;
-  const int g = tid / C;
+  const int groups = 256 / cn > 0 ? 256 / cn : 1;
+  const int g = tid / cn;
   if (g >= groups) return;
   const int len_out = lens_out ? lens_out[b] : Tout;
-  const float bs = bias[c];
-  for (int p = g; p < npos; p += groups) {
-    const int n = n0 + p;
-    if (n >= Tout || n >= len_out) continue;
-    float acc = bs;
-    for (int j = 0; j < k; ++j) acc += wsh[j * C + c] * hsh[p * s + j];
-    x[((int64_t)b * Tout + n) * C + c] += acc;
+  for (int c = tid % cn; c < cn; c += 256) {
+    const float bs = bias[cb + c];
+    for (int p = g; p < npos; p += groups) {
+      const int n = n0 + p;
+      if (n >= Tout || n >= len_out) continue;
+      float acc = bs;
+      for (int j = 0; j < k; ++j) acc += wsh[j * cn + c] * hsh[p * s + j];
+      x[((int64_t)b * Tout + n) * C + cb + c] += acc;
+    }
   }
 }
 
@@ -507,10 +513,16 @@ extern "C" int ss_hifigan_forward(const ss_hifigan* hg, const float* mel, const 
       const int kk = (i + 1 < hg->n_ups) ? 2 * s : 1;
       const int pd = (i + 1 < hg->n_ups) ? s / 2 : 0;
       const int npos = 64;
-      const size_t lds = ((size_t)kk * cout + (size_t)npos * s + kk) * sizeof(float);
+      // the weights of all `cout` channels when they fit the LDS of a CU (every shape the default rates give), else channel chunks
+      int nchunk = 1;
+      auto lds_of = [&](int cc) { return ((size_t)kk * cc + (size_t)npos * s + kk) * sizeof(float); };
+      while (lds_of(ss_cdiv(cout, nchunk)) > LDS_MAX && nchunk < cout) nchunk *= 2;
+      const int cc = ss_cdiv(cout, nchunk);
+      const size_t lds = lds_of(cc);
+      SS_CHECK_ARG(lds <= LDS_MAX, "ss_hifigan_forward: noise conv of stage %d needs %zu bytes of LDS", i, lds);
       const int tiles = (rows_out + npos - 1) / npos;
-      hipLaunchKernelGGL(noise_conv_kernel, dim3(B * tiles), dim3(256), lds, stream, har, hg->w_noise[i], hg->b_noise[i],
-                         w.x, lens_out, w.lens + (int64_t)hg->n_ups * B, B, rows_out, L, cout, kk, s, pd, npos);
+      hipLaunchKernelGGL(noise_conv_kernel, dim3(B * tiles, ss_cdiv(cout, cc)), dim3(256), lds, stream, har, hg->w_noise[i], hg->b_noise[i],
+                         w.x, lens_out, w.lens + (int64_t)hg->n_ups * B, B, rows_out, L, cout, cc, kk, s, pd, npos);
       SS_CHECK_LAUNCH("noise_conv_kernel");
     }
     // xs = mean_j ResBlock1_j(x)   (hifigan_nsf.py:54-61,158-164)
@@ -544,6 +556,7 @@ extern "C" int ss_hifigan_forward(const ss_hifigan* hg, const float* mel, const 
   {
     const int k = 7;
     const size_t lds = ((size_t)(256 + k - 1) * (cin + 1) + (size_t)k * cin) * sizeof(float);
+    SS_CHECK_ARG(lds <= LDS_MAX, "ss_hifigan_forward: conv_post over %d channels needs %zu bytes of LDS", cin, lds);
     const int tiles = (int)((L + 255) / 256);
     hipLaunchKernelGGL(conv_post_kernel, dim3(B * tiles), dim3(256), lds, stream, cur, hg->w_post, hg->b_post, wav,
                        w.lens + (int64_t)hg->n_ups * B, B, L, cin, k);

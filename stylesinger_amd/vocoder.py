@@ -29,6 +29,60 @@ def get_vocoder_cls(hparams):
     return REGISTERED_VOCODERS[hparams["vocoder"]]
 
 
+CONV_POST_MAX_CHANNELS = 128   # conv_post_kernel keeps a 262-sample tile of all channels in LDS: (262 (C + 1) + 7 C) * 4 bytes <= 160 KiB
+HOP_UNIT, HOP_MAX = 64, 1024   # the NSF source kernels run one thread per sample of a frame, in whole waves
+
+
+def check_config(cfg):
+    """The generator shapes `ss_hifigan_forward` computes, in one place (pure: no device, no library). Raises StyleSingerHipError naming the
+    offending key of the checkpoint's config; whatever passes runs, whatever does not is refused here and never launched."""
+    def bad(key, why):
+        raise L.StyleSingerHipError(f"vocoder config: {key}={cfg.get(key)!r} is not supported: {why}")
+
+    def ints(v):
+        return isinstance(v, (list, tuple)) and all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in v)
+
+    if str(cfg.get("resblock")) != "1":
+        bad("resblock", "only ResBlock1 ('1') is implemented")
+    if not cfg.get("use_pitch_embed", True):
+        bad("use_pitch_embed", "the generator is NSF only (harmonic source + noise convs)")
+    if cfg.get("harmonic_num") != 8:
+        bad("harmonic_num", "the harmonic source is the fundamental + 8 overtones")
+    sr = cfg.get("audio_sample_rate")
+    if not isinstance(sr, (int, np.integer)) or sr <= 0:
+        bad("audio_sample_rate", "must be a positive integer")
+    rates, ks = cfg.get("upsample_rates"), cfg.get("upsample_kernel_sizes")
+    if not ints(rates) or not 1 <= len(rates) <= L.SS_HG_MAX_UPS:
+        bad("upsample_rates", f"1 to {L.SS_HG_MAX_UPS} integer rates")
+    if not ints(ks) or len(ks) != len(rates):
+        bad("upsample_kernel_sizes", "one integer kernel size per upsampling stage")
+    for u, k in zip(rates, ks):
+        if u < 2 or u % 2:
+            bad("upsample_rates", f"rate {u}: the polyphase upsampler needs an even rate")
+        if k != 2 * u:
+            bad("upsample_kernel_sizes", f"kernel {k} of the rate-{u} stage: must be twice the rate")
+    hop = int(np.prod(rates))
+    if hop % HOP_UNIT or hop > HOP_MAX:
+        bad("upsample_rates", f"their product (the hop, {hop}) must be a multiple of {HOP_UNIT} and at most {HOP_MAX}")
+    c0 = cfg.get("upsample_initial_channel")
+    if not isinstance(c0, (int, np.integer)) or c0 <= 0 or c0 % (4 << len(rates)):
+        bad("upsample_initial_channel", f"must halve {len(rates)} times into a multiple of 4 channels")
+    if c0 >> len(rates) > CONV_POST_MAX_CHANNELS:
+        bad("upsample_initial_channel", f"leaves {c0 >> len(rates)} channels for conv_post, at most {CONV_POST_MAX_CHANNELS}")
+    rk, rd = cfg.get("resblock_kernel_sizes"), cfg.get("resblock_dilation_sizes")
+    if not ints(rk) or not 1 <= len(rk) <= L.SS_HG_MAX_KERNELS:
+        bad("resblock_kernel_sizes", f"1 to {L.SS_HG_MAX_KERNELS} integer kernel sizes")
+    for k in rk:
+        if k < 1 or k % 2 == 0 or k > L.SS_MAX_TAPS:
+            bad("resblock_kernel_sizes", f"kernel {k}: odd and at most {L.SS_MAX_TAPS} taps")
+    if not isinstance(rd, (list, tuple)) or len(rd) != len(rk):
+        bad("resblock_dilation_sizes", "one list of dilations per ResBlock kernel size")
+    for d in rd:
+        if not ints(d) or len(d) != 3 or min(d) < 1:
+            bad("resblock_dilation_sizes", f"{list(d) if isinstance(d, (list, tuple)) else d!r}: exactly three positive dilations per ResBlock")
+    return cfg
+
+
 class HifiGanGeneratorHIP(torch.nn.Module):
     """Device-side HifiGanGenerator (modules/hifigan/hifigan_nsf.py:105-169), inference only."""
 
@@ -71,7 +125,7 @@ class HifiGanGeneratorHIP(torch.nn.Module):
         return v, L.weight_norm_scale(v, g)
 
     def pack(self):
-        h = self.h
+        h = check_config(self.h)
         dev = self.p("conv_pre.bias").device
         if dev.type != "cuda":
             raise L.StyleSingerHipError("HifiGanGeneratorHIP needs its weights on a GPU: there is no CPU path")

@@ -76,7 +76,8 @@ def test_acoustic_hip_matches_reference_golden(name):
     assert l1 <= CASE_MEL_L1_TOL.get(name, MEL_L1_TOL), f"{name}: mel L1 {l1:.3e}"
 
 
-@pytest.mark.parametrize("name", ["vocoder_t12", "vocoder_b2_t9", "vocoder_t200"])   # t200: 51 200 samples of the REAL reference (round 4)
+# t200: 51 200 samples of the REAL reference (round 4); hop512_t6 / hop64_b2_t9: the REAL reference at other generator shapes (meta["cfg_over"])
+@pytest.mark.parametrize("name", ["vocoder_t12", "vocoder_b2_t9", "vocoder_t200", "vocoder_hop512_t6", "vocoder_hop64_b2_t9"])
 def test_vocoder_hip_matches_reference_golden(name):
     case = harness.load_case(name)
     meta = case["meta"]
@@ -84,7 +85,7 @@ def test_vocoder_hip_matches_reference_golden(name):
     voc = HifiGAN(cfg, vsd, device="cuda:0")
     tape = synth.NoiseTape(meta["tape_seed"])
     B, T = meta["B"], meta["T"]
-    noise = synth.draw_vocoder_noise(tape, B, T * 256)
+    noise = synth.draw_vocoder_noise(tape, B, T * voc.model.hop)
     assert tape.log == meta["tape_log"]
     wav, har = voc.model(case["inp"]["mel"].cuda(), case["inp"]["f0"].cuda(), noise=noise, return_source=True)
     e_h = (har.cpu() - case["out"]["har"]).abs().max().item()

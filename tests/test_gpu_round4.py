@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from conftest import record_measurement  # noqa: E402
+from vocoder_shape_cases import ItemTape as _ItemTape  # noqa: E402
 from oracle import harness  # noqa: E402
 from oracle import restatement as R  # noqa: E402
 from stylesinger_amd import config, synth  # noqa: E402
@@ -121,18 +122,6 @@ def test_vocoder_direct_kernel_fallback_for_items_beyond_32bit_offsets():
         print(f"{name}: wav max err item0 {e0:.3e} item1 (ragged) {e1:.3e}")
         assert max(e0, e1) <= WAV_TOL
     assert lib.ss_set_tuning(b"voc_wino_max_mb", 0) != 0 and lib.ss_get_tuning(b"no_such_knob") < 0
-
-
-class _ItemTape:
-    """Replays item `i` of a pre-drawn vocoder noise dict in the order hifigan_forward draws (rand_ini, sine noise, unused source noise)."""
-    def __init__(self, noise, i, n):
-        self.q = [noise["rand_ini"][i:i + 1], noise["sine_noise"][i:i + 1, :n], torch.zeros(1, n, 1)]
-
-    def rand(self, *shape):
-        return self.q.pop(0).clone()
-
-    def randn(self, *shape):
-        return self.q.pop(0).clone()
 
 
 _RCCL_CHILD = r"""
