@@ -156,8 +156,10 @@ def brent_minimize(f, a, b, tol=1e-10, itermax=60):
     return x, fx
 
 
-def frame_candidates(r, g, voicing_threshold):
-    """r: normalised, window-corrected autocorrelation for lags 0 .. brent_ixmax. Returns (freqs, strengths) of the voiced candidates."""
+def frame_candidates(r, g, voicing_threshold, with_lags=False, counts=None):
+    """r: normalised, window-corrected autocorrelation for lags 0 .. brent_ixmax. Returns (freqs, strengths) of the voiced candidates, in the
+    order of their places (a replacement overwrites the weakest in place); with `with_lags` also the integer lag each was found at. `counts`
+    (a dict) collects how often the full list "replaced" its weakest entry and how often it "rejected" the newcomer."""
     bi, dx = g["brent_ixmax"], g["dx"]
     y = np.concatenate([r[:0:-1], r])                     # positions 1 .. 2 bi + 1 hold lags -bi .. bi
     off = bi + 1                                          # position = lag + off
@@ -178,56 +180,68 @@ def frame_candidates(r, g, voicing_threshold):
                     local = strengths[k] - OCTAVE_COST * math.log2(g["pitch_floor"] / freqs[k])
                     if local < weakest:
                         weakest, place = local, k
-                if s - OCTAVE_COST * math.log2(g["pitch_floor"] / f) > weakest:
+                replace = s - OCTAVE_COST * math.log2(g["pitch_floor"] / f) > weakest
+                if replace:
                     freqs[place], strengths[place], imax[place] = f, s, i
+                if counts is not None:
+                    key = "replaced" if replace else "rejected"
+                    counts[key] = counts.get(key, 0) + 1
     for k in range(len(freqs)):
         depth = 700 if freqs[k] > 0.3 / dx else 70
         xm, fm = brent_minimize(lambda x: -interpolate_sinc(y, x, depth), imax[k] + off - 1, imax[k] + off + 1)
         ymid = -fm
         freqs[k] = 1.0 / dx / (xm - off)
         strengths[k] = 1.0 / ymid if ymid > 1.0 else ymid
-    return freqs, strengths
+    return (freqs, strengths, imax) if with_lags else (freqs, strengths)
 
 
-def analyse_frames(wav, sr, time_step, pitch_floor=80.0, pitch_ceiling=800.0, voicing_threshold=0.6):
-    """-> (geometry, per-frame list of (freqs, strengths) incl. the voiceless candidate first, intensities, normalised autocorrelations)"""
+def analyse_frames(wav, sr, time_step, pitch_floor=80.0, pitch_ceiling=800.0, voicing_threshold=0.6, with_lags=False, r_given=None):
+    """-> (geometry, per-frame list of (freqs, strengths) incl. the voiceless candidate first, intensities, normalised autocorrelations);
+    with `with_lags` a fifth element: per frame the integer lags of the candidates (0 for the voiceless one). `r_given` (per frame an array
+    of lags 0 .. brent_ixmax, or None) replaces the autocorrelation computed here for that frame - silent frames keep their zeros."""
     x = np.asarray(wav, dtype=np.float64)
     g = geometry(len(x), sr, time_step, pitch_floor, pitch_ceiling)
     nw, bi = g["nsamp_window"], g["brent_ixmax"]
     window = hanning_window(nw)
     window_r = window_autocorrelation(window, g["nfft"], bi)
     global_peak = float(np.max(np.abs(x - x.mean()))) if len(x) else 0.0
-    frames, intens, acs = [], [], []
+    frames, intens, acs, lags = [], [], [], []
     lo = g["halfnsamp_window"] + 1 - g["halfnsamp_period"]
     hi = g["halfnsamp_window"] + g["halfnsamp_period"]
     lo, hi = max(lo, 1), min(hi, nw)
     for i in range(g["n_frames"]):
         if global_peak == 0.0:
-            frames.append(([0.0], [0.0])), intens.append(0.0), acs.append(np.zeros(bi + 1))
+            frames.append(([0.0], [0.0])), intens.append(0.0), acs.append(np.zeros(bi + 1)), lags.append([0])
             continue
         ws, ms, me = frame_start(g, i)
         frame = (x[ws:ws + nw] - x[ms:me].mean()) * window
         local_peak = float(np.max(np.abs(frame[lo - 1:hi])))
         intens.append(1.0 if local_peak > global_peak else local_peak / global_peak)
         if local_peak == 0.0:
-            frames.append(([0.0], [0.0])), acs.append(np.zeros(bi + 1))
+            frames.append(([0.0], [0.0])), acs.append(np.zeros(bi + 1)), lags.append([0])
             continue
-        spec = np.fft.rfft(frame, g["nfft"])
-        ac = np.fft.irfft(spec.real ** 2 + spec.imag ** 2, g["nfft"])
-        r = np.empty(bi + 1)
-        r[0] = 1.0
-        r[1:] = ac[1:bi + 1] / (ac[0] * window_r[1:bi + 1])
-        f, s = frame_candidates(r, g, voicing_threshold)
-        frames.append(([0.0] + f, [0.0] + s)), acs.append(r)
+        if r_given is not None and r_given[i] is not None:
+            r = np.asarray(r_given[i], dtype=np.float64)
+        else:
+            spec = np.fft.rfft(frame, g["nfft"])
+            ac = np.fft.irfft(spec.real ** 2 + spec.imag ** 2, g["nfft"])
+            r = np.empty(bi + 1)
+            r[0] = 1.0
+            r[1:] = ac[1:bi + 1] / (ac[0] * window_r[1:bi + 1])
+        f, s, k = frame_candidates(r, g, voicing_threshold, with_lags=True)
+        frames.append(([0.0] + f, [0.0] + s)), acs.append(r), lags.append([0] + k)
+    if with_lags:
+        return g, frames, np.asarray(intens), acs, lags
     return g, frames, np.asarray(intens), acs
 
 
 def path_finder(frames, intens, g, voicing_threshold, silence_threshold=SILENCE_THRESHOLD, octave_cost=OCTAVE_COST,
-                octave_jump_cost=OCTAVE_JUMP_COST, voiced_unvoiced_cost=VOICED_UNVOICED_COST):
-    """Viterbi over the per-frame candidates -> selected frequency per frame (0 = unvoiced)."""
+                octave_jump_cost=OCTAVE_JUMP_COST, voiced_unvoiced_cost=VOICED_UNVOICED_COST, with_nodes=False):
+    """Viterbi over the per-frame candidates -> selected frequency per frame (0 = unvoiced); with `with_nodes` -> (that, per-node best
+    path values delta[frame][candidate], back pointers psi[frame][candidate], selected candidate per frame)."""
     n = len(frames)
     if n == 0:
-        return np.zeros(0)
+        return (np.zeros(0), [], [], np.zeros(0, dtype=np.int64)) if with_nodes else np.zeros(0)
     ceiling = g["ceiling"]
     corr = 0.01 / g["time_step"]
     ojc, vuc = octave_jump_cost * corr, voiced_unvoiced_cost * corr
@@ -254,11 +268,12 @@ def path_finder(frames, intens, g, voicing_threshold, silence_threshold=SILENCE_
             delta[i][c2] = best
             psi[i][c2] = place
     place = int(np.argmax(delta[-1]))
-    out = np.zeros(n)
+    out, places = np.zeros(n), np.zeros(n, dtype=np.int64)
     for i in range(n - 1, -1, -1):
         out[i] = frames[i][0][place]
+        places[i] = place
         place = psi[i][place]
-    return out
+    return (out, delta, psi, places) if with_nodes else out
 
 
 def to_pitch_ac(wav, sr=48000, time_step=256 / 48000, pitch_floor=80.0, pitch_ceiling=800.0, voicing_threshold=0.6):

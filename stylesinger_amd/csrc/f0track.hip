@@ -16,6 +16,12 @@
 #include "common.h"
 #include "../../include/stylesinger_hip.h"
 
+// No fused multiply-adds but the ones written out (the autocorrelation's fma calls). Brent's refinement ends by comparing interpolated values
+// ~5e-14 apart; with the compiler contracting a * b + c in f0t_sinc and in the parabola step, one candidate in ten left the published
+// algorithm's float64 path by a whole termination step (1e-5 samples, 1e-5 Hz at 220 Hz, 5.7e-2 Hz on a lag-2 candidate - found by
+// tests/test_gpu_f0track_stages.py). Uncontracted, every refined candidate is within 8e-8 Hz of the CPU restatement.
+#pragma clang fp contract(off)
+
 namespace {
 
 constexpr int F0T_MAXC = 15;   // max_number_of_candidates of to_pitch_ac, the unvoiced candidate included
@@ -132,27 +138,28 @@ __device__ double f0t_sinc(const double* __restrict__ r, int nlag, double x, int
   if (depth <= 0) return y((int)floor(x + 0.5));
   if (depth == 1) return y(midleft) + (x - midleft) * (y(midright) - y(midleft));
   const int left = midright - depth, right = midleft + depth;
+  // Every term from its own a = pi (x - ix), as the published formula states it. A running a += pi / aa += pi / (x - left + 1) is cheaper by a
+  // division per term but lets ~70 roundings pile up in a (~220 at the far end) and aa: 1e-14 of noise on the interpolated value, which near the
+  // flat top of a peak moves Brent's maximum by 1e-7 samples (tests/test_gpu_f0track_stages.py found 5.7e-6 Hz on a 1500 Hz candidate).
   double res = 0.0;
-  double a = F0T_PI * (x - midleft), halfsina = 0.5 * sin(a), aa = a / (x - left + 1), daa = F0T_PI / (x - left + 1);
+  const double hsl = 0.5 * sin(F0T_PI * (x - midleft)), denl = x - left + 1;
   for (int ix = midleft; ix >= left; --ix) {
-    res += y(ix) * (halfsina / a * (1.0 + cos(aa)));
-    a += F0T_PI;
-    aa += daa;
-    halfsina = -halfsina;
+    const double a = F0T_PI * (x - ix);
+    res += y(ix) * (((midleft - ix) & 1) ? -hsl : hsl) / a * (1.0 + cos(a / denl));
   }
-  a = F0T_PI * (midright - x);
-  halfsina = 0.5 * sin(a);
-  aa = a / (right - x + 1);
-  daa = F0T_PI / (right - x + 1);
+  const double hsr = 0.5 * sin(F0T_PI * (midright - x)), denr = right - x + 1;
   for (int ix = midright; ix <= right; ++ix) {
-    res += y(ix) * (halfsina / a * (1.0 + cos(aa)));
-    a += F0T_PI;
-    aa += daa;
-    halfsina = -halfsina;
+    const double a = F0T_PI * (ix - x);
+    res += y(ix) * (((ix - midright) & 1) ? -hsr : hsr) / a * (1.0 + cos(a / denr));
   }
   return res;
 }
 
+// Depths at the two callers of f0t_sinc. Both sample at x = lag + nlag + 1 with lag < maximum_lag = nsamp_window / 3 + 2 and nlag = nsamp_window / 2
+// (three periods per window), so nx - midleft >= nlag - maximum_lag = nsamp_window / 6 - 2: the clipping of depth 30 / 70 at the array ends cannot
+// happen for nsamp_window >= 432 (every geometry from 11.6 kHz up at the 80 Hz floor). Depth 700 needs a candidate above 0.3 x the sample rate,
+// i.e. a peak at lag 2 or 3 - a tone above 14.4 kHz at 48 kHz; the 800 Hz ceiling does not prevent it (candidates above the ceiling are kept), but
+// no voice does it and no test input has one: that branch, and its clipping at short windows, are untested.
 // thread per frame: the candidate list (slot 0 = unvoiced)
 __global__ __launch_bounds__(64) void f0t_candidates_kernel(const double* __restrict__ R, const double* __restrict__ intensity,
                                                             const int32_t* __restrict__ n_frames, int max_frames, int B, int nlag, int maximum_lag,

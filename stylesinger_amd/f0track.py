@@ -83,6 +83,28 @@ WS_CAP_BYTES = 256 << 20   # peak workspace of one tracker launch group (a 30 s 
 N_TRACK_CALLS = 0   # launches of the tracker since import (tests assert that the entry point tracks each reference audio ONCE)
 
 
+def launch_setup(n_samples, buffer_len, sr=48000, hop_size=256, pitch_floor=80.0, pitch_ceiling=800.0, voicing_threshold=0.6):
+    """Everything `ss_f0track` is told that does not live on the device - no launch, no device memory: (geometry, [(n_frames, left0)] per item,
+    max_frames, the parameter struct, lpad = 2 * pad_size). Refuses an item whose frame windows would leave its `n_samples` or the buffer."""
+    pad_size = {128: 4, 256: 2}[int(hop_size)]
+    time_step = hop_size / sr * 1000 / 1000            # the reference's own expression (ms and back)
+    g = geometry(sr, time_step, pitch_floor, pitch_ceiling)
+    ns = [int(v) for v in n_samples]
+    grid = [frame_grid(g, n) for n in ns]
+    for (nf, left), n in zip(grid, ns):
+        if nf > 0 and (left + 1 - g["nsamp_period"] < 0 or left + 1 - g["halfnsamp_window"] < 0 or
+                       left + (nf - 1) * g["hop"] + 1 + max(g["nsamp_period"], g["halfnsamp_window"]) > max(n, 0) or n > buffer_len):
+            raise ValueError("f0 tracker: a frame window leaves the waveform buffer")
+    max_frames = max(1, max(nf for nf, _ in grid))
+    prm = L.F0TrackParams()
+    prm.sample_rate, prm.time_step, prm.pitch_floor, prm.pitch_ceiling = g["sr"], g["time_step"], g["pitch_floor"], g["pitch_ceiling"]
+    prm.voicing_threshold, prm.silence_threshold = float(voicing_threshold), SILENCE_THRESHOLD
+    prm.octave_cost, prm.octave_jump_cost, prm.voiced_unvoiced_cost = OCTAVE_COST, OCTAVE_JUMP_COST, VOICED_UNVOICED_COST
+    for k in ("nsamp_window", "halfnsamp_window", "nsamp_period", "halfnsamp_period", "maximum_lag", "nlag", "hop"):
+        setattr(prm, k, g[k])
+    return g, grid, max_frames, prm, 2 * pad_size
+
+
 @torch.no_grad()
 def track_f0_device(wavs, n_samples, n_out, sr=48000, hop_size=256, pitch_floor=80.0, pitch_ceiling=800.0, voicing_threshold=0.6):
     """wavs fp32 [B, L] on the device (zero beyond n_samples[b]; host ints) -> f0 fp32 [B, n_out] in Hz (0 = unvoiced) on the mel frame grid:
@@ -92,26 +114,12 @@ def track_f0_device(wavs, n_samples, n_out, sr=48000, hop_size=256, pitch_floor=
         raise L.StyleSingerHipError("track_f0_device needs device tensors: there is no CPU path")
     global N_TRACK_CALLS
     N_TRACK_CALLS += 1
-    pad_size = {128: 4, 256: 2}[int(hop_size)]
-    time_step = hop_size / sr * 1000 / 1000            # the reference's own expression (ms and back)
-    g = geometry(sr, time_step, pitch_floor, pitch_ceiling)
     wavs = wavs.float().contiguous()
     B = wavs.shape[0]
     ns = [int(v) for v in n_samples]
-    grid = [frame_grid(g, n) for n in ns]
-    for (nf, left), n in zip(grid, ns):
-        if nf > 0 and (left + 1 - g["nsamp_period"] < 0 or left + 1 - g["halfnsamp_window"] < 0 or
-                       left + (nf - 1) * g["hop"] + 1 + max(g["nsamp_period"], g["halfnsamp_window"]) > max(n, 0) or n > wavs.shape[1]):
-            raise ValueError("f0 tracker: a frame window leaves the waveform buffer")
-    max_frames = max(1, max(nf for nf, _ in grid))
+    g, grid, max_frames, prm, lpad = launch_setup(ns, wavs.shape[1], sr, hop_size, pitch_floor, pitch_ceiling, voicing_threshold)
     dev = wavs.device
     win, win_r = _window_tables(g, dev)
-    prm = L.F0TrackParams()
-    prm.sample_rate, prm.time_step, prm.pitch_floor, prm.pitch_ceiling = g["sr"], g["time_step"], g["pitch_floor"], g["pitch_ceiling"]
-    prm.voicing_threshold, prm.silence_threshold = float(voicing_threshold), SILENCE_THRESHOLD
-    prm.octave_cost, prm.octave_jump_cost, prm.voiced_unvoiced_cost = OCTAVE_COST, OCTAVE_JUMP_COST, VOICED_UNVOICED_COST
-    for k in ("nsamp_window", "halfnsamp_window", "nsamp_period", "halfnsamp_period", "maximum_lag", "nlag", "hop"):
-        setattr(prm, k, g[k])
     lib = L.load()
     # ONE int32 table [3][B] that stays referenced until the launches are queued (three temporaries would be freed - and their memory handed to
     # the next one - before the kernels read them)
@@ -127,7 +135,7 @@ def track_f0_device(wavs, n_samples, n_out, sr=48000, hop_size=256, pitch_floor=
     for b0 in range(0, B, group):
         nb = min(group, B - b0)
         L.check(lib.ss_f0track(L.ptr(wavs[b0:]), wavs.shape[1], L.ptr(meta[0, b0:]), L.ptr(meta[1, b0:]), L.ptr(meta[2, b0:]), nb,
-                               max_frames, ctypes.byref(prm), L.ptr(win), L.ptr(win_r), L.ptr(out[b0:]), int(n_out), 2 * pad_size, L.ptr(ws), ws.numel(),
+                               max_frames, ctypes.byref(prm), L.ptr(win), L.ptr(win_r), L.ptr(out[b0:]), int(n_out), lpad, L.ptr(ws), ws.numel(),
                                L.stream_ptr()), "ss_f0track")
     meta.record_stream(torch.cuda.current_stream(dev))
     return out
