@@ -873,6 +873,26 @@ int ss_loudness_apply(const float* x, int64_t ldx, int Lx, const int32_t* n, con
 int ss_contour_fit(const float* f0_hz, int64_t ldc, int Lc, const int32_t* lens_c, const int32_t* lens_t, float shift_semitones, float* out,
                    int64_t ldo, int T, int B, void* stream);
 
+/* A song from separately rendered segments (StyleSingerInfer.sing_score; csrc/song.hip, restated on the host in tests/song_ref.py). The S segments
+ * of a score are rows of ordinary batches, in an order chosen for batching; their frame counts are device values. Neither entry allocates or
+ * synchronises: both are graph-capturable.
+ * ss_song_offsets: offsets[s] = sum of max(lens[i], 0) over i < s for s = 0 .. S (S + 1 values; lens in SONG order, frames). Any S >= 0.
+ * ss_song_place: src [B][lds] fp32 (every row holds lds floats), seg[b] = song index of row b (< 0: the row is skipped). Row b contributes its
+ *   first n = lens[seg[b]] * unit floats at out[offsets[seg[b]] * unit ...]; unit = floats per frame (hop for a waveform, 80 for a mel, 1 for f0).
+ *   The timeline is the concatenation of the segments: they never overlap, every output float has one writer, no atomics. Joint fades (fade > 0):
+ *   f = min(fade, n / 2); a segment with song index s > 0 has float k < f multiplied by win[((2 k + 1) * fade) / (2 f)] (integer division; win[k]
+ *   when f == fade), a segment with s < S - 1 has float n - 1 - k multiplied by the same entry; the song's own start and end are not faded. win
+ *   [fade] fp32, by convention fl32(0.5 - 0.5 cos(pi (j + 0.5) / fade)) computed in float64 (song.fade_window). The gain is ONE fp32 multiply.
+ *   Reads stop at lds floats of a row, writes at `cap` floats of `out`; a row with seg[b] >= S or a negative offset is skipped. Each of these sets
+ *   its SS_SONG_FLAG_* bit in flags[0] (device int32, may be NULL; updated by one thread per launch, so launches that share the word must share a
+ *   stream) and none reads or writes out of bounds. 16-byte accesses when unit % 4 == 0, lds % 4 == 0 and src, out are 16-byte aligned. */
+#define SS_SONG_FLAG_READ 1
+#define SS_SONG_FLAG_WRITE 2
+#define SS_SONG_FLAG_INDEX 4
+int ss_song_offsets(const int32_t* lens, int S, int64_t* offsets, void* stream);
+int ss_song_place(const float* src, int64_t lds, const int32_t* seg, int B, const int32_t* lens, const int64_t* offsets, int S, int unit,
+                  const float* win, int fade, float* out, int64_t cap, int32_t* flags, void* stream);
+
 /* Emotion encoder (input producer; data_gen/tts/emotion/model.py:11-78 = nn.LSTM(40, 256, 3) + Linear, inference.py:39-53,
  * 139-151). One LSTM layer's recurrence as a persistent launch (one workgroup per sequence):
  *   xproj  [P][n][H][4] = x_t . W_ih^T + b_ih + b_hh for every step, gate-interleaved (i,f,g,o per hidden unit) - one

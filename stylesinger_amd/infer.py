@@ -12,6 +12,7 @@ they are computed on the host when the package is importable, or given by the ca
 (`vad_flags=False`), never a silent default.
 `infer_once(inp)` = the reference's entry point (inference/StyleSinger.py:175-179) with the features kept on the device between the producers and
 the model; `python -m stylesinger_amd.infer` = `example_run` (:181-331).
+`sing_score(inp)` (`--score song.json`) sings a score of any length: split at its rests (`song.py`), rendered as batches, stitched on the device.
 """
 import json
 import os
@@ -100,10 +101,13 @@ class StyleSingerInfer:
         ref_f0, optional mel2ph).  Returns dict(mel [B,T,80], f0 [B,T], lens int32 [B], wav [B,T*hop]).
         Pitch control (StyleSingerHIP.forward): optional `f0` + `uv` [B, T] (the normalised contour, the reference's use_gt_f0 form), or
         `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted.
-        `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain)."""
+        `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain).
+        Optional `style_cache`: what `model.encode_style` returned for the batch's references; the style encoder is then skipped."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
         pitch = {k: batch[k] for k in ("pitch_hz", "pitch_shift") if batch.get(k) is not None}
+        if batch.get("style_cache") is not None:   # the references' style, encoded once by the caller (model.encode_style; `sing_score`)
+            pitch["style_cache"] = batch["style_cache"]
         out = self.model(batch["txt_tokens"], mel2ph=batch.get("mel2ph"), spk_embed=batch["spk_embed"], emo_embed=batch["emo_embed"],
                          ref_mels=batch["ref_mels"], ref_f0=batch["ref_f0"], f0=batch.get("f0"), uv=batch.get("uv"), global_steps=320000,
                          infer=True, note=batch["note"], note_dur=batch["note_dur"], note_type=batch["note_type"], noise=noise, seed=seed,
@@ -551,6 +555,92 @@ class StyleSingerInfer:
         res = self.infer_batch({k: v for k, v in batch.items() if k not in ("n_mel", "ref_f0_hz")}, noise=noise, vocode=False)
         return self.postprocess_output(self._wav_from_result(res, vocoder_noise))
 
+    # ---- a whole score -----------------------------------------------------------------------------
+    def _song_reference(self, inp, vad_flags):
+        """The reference of a song, processed ONCE: (ref_mels [1, Tr, 80], ref_f0 [1, Tr], spk_embed [1, 256], emo_embed [1, 256]) on the device,
+        from the features in `inp` (`mel`, `spk_embed`, `emo_embed`, `f0`: as `infer_once` accepts them) or from inp['ref_audio'] through the
+        producers of `_device_batch`."""
+        d = self.device
+        if all(k in inp for k in ("mel", "spk_embed", "emo_embed", "f0")):
+            from .pitch import norm_interp_f0
+            t = lambda x: torch.as_tensor(np.asarray(x), dtype=torch.float32)[None].to(d)
+            f0, _uv = norm_interp_f0(np.asarray(inp["f0"]), self.hparams)
+            return t(inp["mel"]), f0[None].to(d), t(inp["spk_embed"]), t(inp["emo_embed"])
+        if inp.get("ref_audio") is None:
+            raise ValueError("sing_score: give inp['ref_audio'] (the reference voice), or its features mel / spk_embed / emo_embed / f0")
+        one = {k: inp[k] for k in ("ref_audio", "ref_sr", "ph", "ph_token", "note", "note_dur", "note_type") if k in inp}
+        b = self._device_batch(one, vad_flags)
+        inp.setdefault("ph_token", one["ph_token"])
+        return b["ref_mels"], b["ref_f0"], b["spk_embed"], b["emo_embed"]
+
+    @torch.no_grad()
+    def sing_score(self, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None):
+        """Sing a score of any length in the reference's voice: `inp` = the reference's input dict (`ph` | `ph_token`, `note`, `note_dur`, `note_type`,
+        optionally `ph_dur` = seconds per phone, `pitch_hz` | `pitch_audio`, `pitch_shift`; `ref_audio` or the reference's features). The score
+        is cut into phrases at its rests (`song.plan_song`: policy and limits there), the reference is processed and its style encoded ONCE, the
+        plan's batches run through `infer_batches` (batch i with seed + i), and the segments are put on one timeline on the device
+        (`ss_song_offsets` + three `ss_song_place` per batch: the waveform with a raised-cosine fade of `fade_ms` on both sides of every joint, the
+        mel and the f0 as they are). Segments never overlap: the song is their concatenation. ONE host sync at the end learns the length. Loudness
+        (`out_lufs`, else hparams['out_loudness_lufs']) is applied to the WHOLE song, never per segment: that would flatten its dynamics.
+        -> dict(wav [N], mel [F, 80], f0 [F] on the device, segments = [{first, last, start_frame, n_frames, batch, row}] (phones [first, last)),
+        plan (the SongPlan; its batches in their device form), lufs (float, the loudness before the gain) when a target is set)."""
+        from . import song
+        hp, d = self.hparams, self.device
+        sr, hop = int(hp["audio_sample_rate"]), int(self.vocoder.model.hop)
+        inp = dict(inp)
+        song.check_pitch_keys(inp)   # pitch control without ph_dur is refused before a device is touched
+        seed = hp["seed"] if seed is None else seed
+        ref_mels, ref_f0, spk, emo = self._song_reference(inp, vad_flags)
+        if inp.get("pitch_audio") is not None:   # the guide vocal is tracked on the device; the planner takes its contour
+            hz, _n = self._pitch_inputs({"pitch_audio": inp.pop("pitch_audio")})["pitch_hz"]
+            inp["pitch_hz"] = hz[0].cpu().numpy()
+        plan = song.plan_song(inp, sr=sr, hop=hop, max_seconds=max_seconds, segment_batch=segment_batch, ph_encoder=self.ph_encoder)
+        S = len(plan.segments)
+        style = self.model.encode_style(ref_mels, ref_f0)
+        fade = max(0, int(round(float(fade_ms) * sr / 1000.0))) if S > 1 else 0
+        win = torch.from_numpy(song.fade_window(fade)).to(d) if fade else None
+        segs_dev, rows_dev = [], []
+        for i, hb in enumerate(plan.batches):   # everything the stitch needs from the host goes up before the first batch runs
+            nb = len(plan.rows[i])
+            b = {k: ((v[0].to(d), v[1]) if k == "pitch_hz" else v.to(d) if torch.is_tensor(v) else v) for k, v in hb.items()}
+            rep = lambda x: x.expand(nb, *x.shape[1:]).contiguous()
+            b.update(spk_embed=rep(spk), emo_embed=rep(emo), ref_mels=ref_mels.expand(nb, -1, -1), ref_f0=ref_f0.expand(nb, -1),
+                     style_cache={k: rep(v) for k, v in style.items()})
+            plan.batches[i] = b
+            rows_dev.append(torch.tensor(plan.rows[i], dtype=torch.long).to(d))
+            segs_dev.append(rows_dev[-1].to(torch.int32))
+        results = list(self.infer_batches(plan.batches, in_flight=in_flight, seed=seed))
+        lens = torch.zeros(S, device=d, dtype=torch.int32)
+        for rows, res in zip(rows_dev, results):
+            lens.index_copy_(0, rows, res["lens"].to(torch.int32))
+        offsets = song.song_offsets(lens)
+        cap = sum(int(res["mel"].shape[0]) * int(res["mel"].shape[1]) for res in results)   # frames: no segment is longer than its batch
+        wav, mel, f0 = (torch.empty(cap * u, device=d, dtype=torch.float32) for u in (hop, 80, 1))
+        flags = torch.zeros(1, device=d, dtype=torch.int32)
+        for seg, res in zip(segs_dev, results):
+            song.song_place(res["wav"].contiguous(), seg, lens, offsets, hop, wav, win=win, flags=flags)
+            song.song_place(res["mel"].contiguous(), seg, lens, offsets, 80, mel, flags=flags)
+            song.song_place(res["f0"].contiguous(), seg, lens, offsets, 1, f0, flags=flags)
+        *starts, flagged = (int(v) for v in torch.cat([offsets, flags.to(torch.int64)]).cpu())   # the one host sync of the stitch
+        if flagged != 0:
+            raise L.StyleSingerHipError(f"sing_score: ss_song_place clamped or refused a segment (flags {flagged}): the plan and the rendered "
+                                        "batches disagree")
+        F = starts[-1]
+        out = dict(wav=wav[:F * hop], mel=mel[:F * 80].view(F, 80), f0=f0[:F], plan=plan, segments=[])
+        for s, g in enumerate(plan.segments):
+            g["start_frame"], g["n_frames"] = starts[s], starts[s + 1] - starts[s]
+            out["segments"].append({k: g[k] for k in ("first", "last", "start_frame", "n_frames", "batch", "row")})
+        long_ = [s for s, g in enumerate(plan.segments) if g["n_frames"] > 3000]
+        if long_:
+            warnings.warn(f"sing_score: {len(long_)} segment(s) came out longer than the 3000 frames the model was trained on (first: phones "
+                          f"[{plan.segments[long_[0]]['first']}, {plan.segments[long_[0]]['last']}), {plan.segments[long_[0]]['n_frames']} frames); lower "
+                          "max_seconds or add rests")
+        target = out_lufs if out_lufs is not None else hp.get("out_loudness_lufs")
+        if target is not None:
+            y, lufs = self._to_lufs(out["wav"][None], [F * hop], target)
+            out["wav"], out["lufs"] = y[0], float(lufs[0])
+        return out
+
     @classmethod
     def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, pitch=None, **ctor):
         """inference/StyleSinger.py:181-331: the example score (stylesinger_amd/example_input.json = that method's input dict, extracted by
@@ -576,12 +666,32 @@ class StyleSingerInfer:
         return out
 
 
+def _score_run(score, hparams, out_path, segments_out=None, vad_flags=None, max_seconds=12.0, segment_batch=8, fade_ms=5.0, **ctor):
+    """`--score`: sing the score dict with `StyleSingerInfer.sing_score`, write the song as 16-bit PCM and, with `segments_out`, the timeline as JSON
+    (per segment its phone range, start sample and sample count: for lining the vocal up with an accompaniment)."""
+    from .writer import save_wav
+    ins = StyleSingerInfer(hparams, **ctor)
+    res = ins.sing_score(score, max_seconds=max_seconds, segment_batch=segment_batch, fade_ms=fade_ms, vad_flags=vad_flags)
+    sr, hop = int(ins.hparams["audio_sample_rate"]), int(ins.vocoder.model.hop)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    save_wav(res["wav"].cpu().numpy(), out_path, sr, norm=bool(ins.hparams.get("out_wav_norm", False)))
+    if segments_out:
+        with open(segments_out, "w") as fh:
+            json.dump(dict(sample_rate=sr, hop=hop, n_samples=int(res["wav"].numel()),
+                           segments=[dict(first_phone=g["first"], last_phone=g["last"], start_sample=g["start_frame"] * hop,
+                                          n_samples=g["n_frames"] * hop) for g in res["segments"]]), fh, indent=1)
+    print(f"Save at {out_path}.")
+    return res
+
+
 def main(argv=None):
     """`python -m stylesinger_amd.infer --exp-dir checkpoints/<exp> --vocoder-dir <hifigan dir> --emotion-ckpt <pt> --speaker-ckpt <pt>
     --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim]` = the reference's
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
     sing the score on a given pitch contour instead of the predicted one. `--loud-norm`: loudness-normalise the reference audio as a model trained with
-    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS."""
+    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS.
+    `--score song.json [--max-seconds 12] [--segment-batch 8] [--fade-ms 5] [--segments-out timeline.json]`: sing a score of any length (the keys of
+    example_input.json, optionally `ph_dur`; its `ref_audio` unless --ref-audio is given) with `sing_score`; pitch flags then need `ph_dur` in the score."""
     import argparse
     ap = argparse.ArgumentParser(description="StyleSinger example_run on the HIP path")
     ap.add_argument("--exp-dir", required=True)
@@ -589,7 +699,7 @@ def main(argv=None):
     ap.add_argument("--emotion-ckpt", required=True, help="the reference's emotion encoder checkpoint (hparams['emotion_encoder_path'])")
     ap.add_argument("--speaker-ckpt", required=True, help="resemblyzer's pretrained.pt")
     ap.add_argument("--phone-set", required=True)
-    ap.add_argument("--ref-audio", default="test/test.wav")
+    ap.add_argument("--ref-audio", help="the reference voice (default: the score file's ref_audio, else test/test.wav)")
     ap.add_argument("--out", default="infer_out/test.wav")
     ap.add_argument("--no-vad-trim", action="store_true", help="explicit opt-out of trim_long_silences (webrtcvad missing)")
     ap.add_argument("--pitch-audio", help="sing on the pitch of this guide vocal (a WAV file, tracked on the device, 80-800 Hz) instead of the predicted f0")
@@ -598,6 +708,12 @@ def main(argv=None):
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
+    ap.add_argument("--score", help="a score of any length as JSON (the keys of example_input.json, optionally ph_dur = seconds per phone): split at "
+                    "its rests, rendered in batches, stitched on the device")
+    ap.add_argument("--max-seconds", type=float, default=12.0, help="--score: longest merged segment")
+    ap.add_argument("--segment-batch", type=int, default=8, help="--score: segments per batch")
+    ap.add_argument("--fade-ms", type=float, default=5.0, help="--score: raised-cosine fade on both sides of every joint")
+    ap.add_argument("--segments-out", help="--score: write the timeline (phone ranges and start samples per segment) to this JSON file")
     a = ap.parse_args(argv)
     if a.pitch_audio and a.pitch_npy:
         ap.error("--pitch-audio and --pitch-npy exclude each other")
@@ -610,6 +726,24 @@ def main(argv=None):
         pitch["pitch_hz"] = np.load(a.pitch_npy)
     if a.pitch_shift is not None:
         pitch["pitch_shift"] = a.pitch_shift
+    score = None
+    if a.score:
+        with open(a.score) as fh:
+            score = {k: v for k, v in json.load(fh).items() if k != "source"}
+        if pitch and score.get("ph_dur") is None:
+            ap.error("--score with a pitch flag needs 'ph_dur' (seconds per phone) in the score: without it the segment frame counts are not known "
+                     "before rendering")
+        score.update(pitch)
+        from . import song
+        try:
+            song.check_pitch_keys(score)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.ref_audio or not score.get("ref_audio"):
+            score["ref_audio"] = a.ref_audio or "test/test.wav"
+    elif a.segments_out:
+        ap.error("--segments-out needs --score")
+    a.ref_audio = a.ref_audio or "test/test.wav"
     emo = torch.load(a.emotion_ckpt, map_location="cpu", weights_only=False)
     spk = torch.load(a.speaker_ckpt, map_location="cpu", weights_only=False)
     from . import ckpt
@@ -622,9 +756,13 @@ def main(argv=None):
         hp["loud_norm"] = True
     if a.out_lufs is not None:
         hp["out_loudness_lufs"] = a.out_lufs
-    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, pitch=pitch, model_state=state,
-                                 vocoder_state=vstate, vocoder_config=vcfg, emotion_state=emo.get("model_state", emo),
-                                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
+    ctor = dict(model_state=state, vocoder_state=vstate, vocoder_config=vcfg, emotion_state=emo.get("model_state", emo),
+                speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
+    if score is not None:
+        _score_run(score, hp or None, a.out, segments_out=a.segments_out, vad_flags=False if a.no_vad_trim else None, max_seconds=a.max_seconds,
+                   segment_batch=a.segment_batch, fade_ms=a.fade_ms, **ctor)
+        return
+    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, pitch=pitch, **ctor)
 
 
 if __name__ == "__main__":

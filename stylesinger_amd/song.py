@@ -1,0 +1,227 @@
+"""A score of any length: split into phrases at its rests, rendered as ordinary batches, stitched into one timeline on the device.
+
+The reference was trained on segments of at most `max_frames: 3000` (16 s) and its self-attention and style aligner run over the whole frame
+axis, so a song cannot go through `forward` as one item. `plan_song` (host, pure: no device is touched) cuts the reference's `inp` dict into
+segments and batches; `StyleSingerInfer.sing_score` renders the plan's batches and puts the results on one timeline with the two kernels of
+csrc/song.hip (`song_offsets`, `song_place` below). DESIGN.md §3.4h.
+
+Policy
+  * A phone is a REST when note_type == 1 or note == 0. A MINIMAL PHRASE ends at phone i when i is a rest and i + 1 is not, or i is the last phone:
+    rests close a phrase (as in the example score); leading rests do not end a phrase that holds no note yet, they open the first one; a score
+    without rests is one phrase. A minimal phrase is never cut.
+  * Seconds of a phone range: with inp['ph_dur'] (seconds per phone) the exact sum; without, an ESTIMATE from the notes: the sum of note_dur[i]
+    over the phones i that start the range or whose (note, note_dur, note_type) differs from phone i - 1 - consecutive phones that share a note
+    count once. Immediately repeated EQUAL notes (same pitch, same length, same type) are indistinguishable from one note held over several phones
+    and are therefore under-counted; give ph_dur where that matters.
+  * Minimal phrases are merged greedily, left to right, while the merged range stays <= max_seconds (default 12 s: below the 16 s training limit,
+    because without ph_dur the durations are the model's own). A minimal phrase that is longer on its own stays whole, with one warning.
+  * With ph_dur the frame grid is global: b_i = floor(cumsum_f64(ph_dur)[i] * sr / hop + 0.5), phone i owns the frames [b_i, b_{i+1}) (possibly
+    none), and a segment's explicit mel2ph is cut from that grid: the segments' frame counts sum to the song's and every segment starts on its score
+    time. Without ph_dur, mel2ph is left to the duration predictor and the frame counts are known only after rendering.
+  * Song-level pitch control (pitch_hz | pitch_audio, pitch_shift) needs ph_dur: the contour is fitted ONCE to the song's frame count
+    (`pitch.contour_fit`, float64) and sliced per segment; every slice has its segment's length, so `ss_contour_fit` copies it bit for bit.
+  * Batches: segments ordered by frame count (phone count when frames are unknown), descending, ties in song order; `segment_batch` per batch.
+"""
+import dataclasses
+import warnings
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+PITCH_KEYS = ("pitch_hz", "pitch_audio", "pitch_shift")
+NO_PH_DUR = ("song-level pitch control ({keys}) needs inp['ph_dur'] (seconds per phone): without it the durations are the model's own, so the "
+             "segment frame counts are not known before rendering and the contour cannot be cut into per-segment slices")
+
+
+def is_rest(note, note_type):
+    return (np.asarray(note_type) == 1) | (np.asarray(note) == 0)
+
+
+def minimal_phrases(note, note_type):
+    """-> [(first, last)] phone ranges (last exclusive) that tile [0, P) in order."""
+    rest = is_rest(note, note_type)
+    P = len(rest)
+    out, first = [], 0
+    for i in range(P):
+        # a rest followed by a note closes the phrase - unless the phrase holds nothing but rests so far: leading rests open the first phrase
+        if i == P - 1 or (rest[i] and not rest[i + 1] and not rest[first:i + 1].all()):
+            out.append((first, i + 1))
+            first = i + 1
+    return out
+
+
+def range_seconds(first, last, note, note_dur, note_type, ph_dur=None):
+    """Seconds of the phones [first, last): exact with ph_dur, else the estimate of the module docstring."""
+    if ph_dur is not None:
+        return float(np.sum(np.asarray(ph_dur, dtype=np.float64)[first:last]))
+    s = 0.0
+    for i in range(first, last):
+        if i == first or (note[i], note_dur[i], note_type[i]) != (note[i - 1], note_dur[i - 1], note_type[i - 1]):
+            s += float(note_dur[i])
+    return s
+
+
+def merge_phrases(phrases, seconds_of, max_seconds):
+    """Greedy left-to-right merge of minimal phrases while seconds_of(first, last) <= max_seconds. -> [(first, last)]"""
+    out = []
+    for first, last in phrases:
+        if out and seconds_of(out[-1][0], last) <= max_seconds:
+            out[-1] = (out[-1][0], last)
+            continue
+        own = seconds_of(first, last)
+        if own > max_seconds:
+            warnings.warn(f"plan_song: the phrase of phones [{first}, {last}) takes {own:.2f} s on its own, more than max_seconds={max_seconds:g}: "
+                          "it has no rest to cut at and is rendered whole")
+        out.append((first, last))
+    return out
+
+
+def frame_bounds(ph_dur, sr, hop):
+    """b_i = floor(cumsum_f64(ph_dur)[i] * sr / hop + 0.5) for i = 0 .. P: int64 [P + 1], b_0 = 0."""
+    d = np.asarray(ph_dur, dtype=np.float64)
+    if d.ndim != 1 or not np.isfinite(d).all() or (d < 0).any():
+        raise ValueError("plan_song: inp['ph_dur'] must be finite, non-negative seconds per phone")
+    t = np.concatenate([[0.0], np.cumsum(d, dtype=np.float64)])
+    return np.floor(t * float(sr) / float(hop) + 0.5).astype(np.int64)
+
+
+def fade_window(fade):
+    """win[j] = 0.5 - 0.5 cos(pi (j + 0.5) / fade), j < fade: float64 rounded to fp32 (the table of ss_song_place)."""
+    j = np.arange(int(fade), dtype=np.float64)
+    return (0.5 - 0.5 * np.cos(np.pi * (j + 0.5) / max(int(fade), 1))).astype(np.float32)
+
+
+@dataclasses.dataclass
+class SongPlan:
+    """What `plan_song` returns, and what the renderer and the tests consume.
+    segments[s] (song order): dict(index, first, last (exclusive), seconds, n_frames | None, start_frame | None, batch, row);
+    batches[i]: dict of host tensors as `infer_batch` takes them (txt_tokens, note, note_dur, note_type [nb, Tp] zero padded; with ph_dur mel2ph
+        [nb, T]; with a contour pitch_hz = ([nb, T] fp32, [n_frames]) and pitch_shift) - `sing_score` replaces each by its device form, with the
+        reference's features and style encoding added, so `infer_batch(plan.batches[i], seed=seed + i)` is what was rendered;
+    rows[i][r] = song index of row r of batch i; n_frames = the song's frame count (None without ph_dur)."""
+    segments: list
+    batches: list
+    rows: list
+    n_frames: object
+    sr: int
+    hop: int
+    max_seconds: float
+    segment_batch: int
+    pitch_hz: object = None    # the contour fitted to n_frames (fp32), before any pitch_shift
+
+
+def check_pitch_keys(inp):
+    """Song-level pitch keys without ph_dur are refused, with the reason (before anything is loaded or rendered)."""
+    keys = [k for k in PITCH_KEYS if inp.get(k) is not None]
+    if keys and inp.get("ph_dur") is None:
+        raise ValueError("plan_song: " + NO_PH_DUR.format(keys=", ".join(keys)))
+    return keys
+
+
+def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_encoder=None):
+    """inp: the reference's input dict at any length - `ph` (or `ph_token`), `note`, `note_dur`, `note_type`, optionally `ph_dur`, `pitch_hz`
+    (a 1-D contour in Hz over the whole song, any length), `pitch_shift`. -> SongPlan."""
+    keys = check_pitch_keys(inp)
+    if "pitch_audio" in keys:
+        raise ValueError("plan_song: the planner runs on the host; track inp['pitch_audio'] first and give its contour as inp['pitch_hz'] "
+                         "(StyleSingerInfer.sing_score does)")
+    if "pitch_shift" in keys and "pitch_hz" not in keys:
+        raise ValueError("plan_song: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
+    if inp.get("ph_token") is not None:
+        tokens = np.asarray(inp["ph_token"], dtype=np.int64)
+    elif ph_encoder is not None and inp.get("ph") is not None:
+        tokens = np.asarray(ph_encoder.encode(" ".join(inp["ph"])), dtype=np.int64)
+    else:
+        raise ValueError("plan_song: give inp['ph_token'], or inp['ph'] and a phone encoder (StyleSingerInfer(..., phone_set=<phone_set.json>))")
+    note = np.asarray(inp["note"], dtype=np.int64)
+    note_dur = np.asarray(inp["note_dur"], dtype=np.float64)
+    note_type = np.asarray(inp["note_type"], dtype=np.int64)
+    P = len(tokens)
+    if P == 0 or not (len(note) == len(note_dur) == len(note_type) == P):
+        raise ValueError(f"plan_song: {P} phones, {len(note)} note, {len(note_dur)} note_dur, {len(note_type)} note_type entries")
+    ph_dur = inp.get("ph_dur")
+    if ph_dur is not None and len(ph_dur) != P:
+        raise ValueError(f"plan_song: {len(ph_dur)} ph_dur entries for {P} phones")
+    if int(segment_batch) < 1 or not float(max_seconds) > 0:
+        raise ValueError(f"plan_song: segment_batch={segment_batch}, max_seconds={max_seconds}")
+    nl, dl, tl = note.tolist(), note_dur.tolist(), note_type.tolist()
+    ranges = merge_phrases(minimal_phrases(note, note_type), lambda a, b: range_seconds(a, b, nl, dl, tl, ph_dur), float(max_seconds))
+    bounds = frame_bounds(ph_dur, sr, hop) if ph_dur is not None else None
+    segments = []
+    for s, (first, last) in enumerate(ranges):
+        seg = dict(index=s, first=first, last=last, seconds=range_seconds(first, last, nl, dl, tl, ph_dur), n_frames=None, start_frame=None)
+        if bounds is not None:
+            seg["n_frames"], seg["start_frame"] = int(bounds[last] - bounds[first]), int(bounds[first])
+            if seg["n_frames"] == 0:
+                raise ValueError(f"plan_song: the segment of phones [{first}, {last}) has no frame on the {hop / sr * 1000:.2f} ms grid (ph_dur sums to "
+                                 f"{seg['seconds']:.4f} s)")
+        segments.append(seg)
+    F = int(bounds[-1]) if bounds is not None else None
+    contour = None
+    if inp.get("pitch_hz") is not None:
+        from .pitch import contour_fit
+        hz = np.asarray(inp["pitch_hz"], dtype=np.float64)
+        if hz.ndim != 1 or hz.size == 0:
+            raise ValueError(f"plan_song: inp['pitch_hz'] must be a non-empty 1-D contour in Hz (got shape {hz.shape})")
+        contour = contour_fit(hz, F).astype(np.float32)
+    order = sorted(range(len(segments)), key=lambda s: -(segments[s]["n_frames"] if bounds is not None else segments[s]["last"] - segments[s]["first"]))
+    batches, rows = [], []
+    for i in range(0, len(order), int(segment_batch)):
+        idx = order[i:i + int(segment_batch)]
+        Tp = max(segments[s]["last"] - segments[s]["first"] for s in idx)
+        b = dict(txt_tokens=torch.zeros(len(idx), Tp, dtype=torch.long), note=torch.zeros(len(idx), Tp, dtype=torch.long),
+                 note_dur=torch.zeros(len(idx), Tp, dtype=torch.float32), note_type=torch.zeros(len(idx), Tp, dtype=torch.long))
+        if bounds is not None:
+            T = max(segments[s]["n_frames"] for s in idx)
+            b["mel2ph"] = torch.zeros(len(idx), T, dtype=torch.long)
+            if contour is not None:
+                b["pitch_hz"] = (torch.zeros(len(idx), T, dtype=torch.float32), [segments[s]["n_frames"] for s in idx])
+                if inp.get("pitch_shift") is not None:
+                    b["pitch_shift"] = float(inp["pitch_shift"])
+        for r, s in enumerate(idx):
+            first, last = segments[s]["first"], segments[s]["last"]
+            segments[s]["batch"], segments[s]["row"] = len(batches), r
+            n = last - first
+            b["txt_tokens"][r, :n] = torch.from_numpy(tokens[first:last])
+            b["note"][r, :n] = torch.from_numpy(note[first:last])
+            b["note_dur"][r, :n] = torch.from_numpy(note_dur[first:last].astype(np.float32))
+            b["note_type"][r, :n] = torch.from_numpy(note_type[first:last])
+            if bounds is not None:
+                f0, nf = segments[s]["start_frame"], segments[s]["n_frames"]
+                b["mel2ph"][r, :nf] = torch.from_numpy(np.repeat(np.arange(1, n + 1, dtype=np.int64), np.diff(bounds[first:last + 1])))
+                if contour is not None:
+                    b["pitch_hz"][0][r, :nf] = torch.from_numpy(contour[f0:f0 + nf])
+        batches.append(b)
+        rows.append(idx)
+    return SongPlan(segments=segments, batches=batches, rows=rows, n_frames=F, sr=int(sr), hop=int(hop), max_seconds=float(max_seconds),
+                    segment_batch=int(segment_batch), pitch_hz=contour)
+
+
+# ---- the two kernels (csrc/song.hip): argument marshalling only ---------------------------------------------------------------------------
+FLAG_READ, FLAG_WRITE, FLAG_INDEX = (L.abi.DEFINES["SS_SONG_FLAG_" + n] for n in ("READ", "WRITE", "INDEX"))
+
+
+@torch.no_grad()
+def song_offsets(lens, out=None):
+    """lens int32 [S] on the device (frames, song order) -> offsets int64 [S + 1] (exclusive scan; no host sync)."""
+    lens = lens.to(torch.int32).contiguous()
+    S = lens.numel()
+    out = torch.empty(S + 1, device=lens.device, dtype=torch.int64) if out is None else out
+    L.check(L.load().ss_song_offsets(L.ptr(lens), S, L.ptr(out), L.stream_ptr()), "ss_song_offsets")
+    return out
+
+
+@torch.no_grad()
+def song_place(src, seg, lens, offsets, unit, out, win=None, flags=None, cap=None):
+    """src fp32 [B, ...] contiguous rows on the device, seg int32 [B] (song index per row, < 0 = skip), lens int32 [S], offsets int64 [S + 1],
+    unit floats per frame, out fp32 (flat), win fp32 [fade] or None, flags int32 [1] or None. `cap`: floats of `out` that may be written (all)."""
+    B = src.shape[0]
+    assert src.is_contiguous() and src.dtype == torch.float32 and out.dtype == torch.float32 and out.is_contiguous()
+    assert seg.dtype == torch.int32 and lens.dtype == torch.int32 and offsets.dtype == torch.int64 and seg.numel() == B
+    lds = src.numel() // B
+    L.check(L.load().ss_song_place(L.ptr(src), lds, L.ptr(seg), B, L.ptr(lens), L.ptr(offsets), lens.numel(), int(unit), L.ptr(win),
+                                   0 if win is None else win.numel(), L.ptr(out), out.numel() if cap is None else int(cap), L.ptr(flags),
+                                   L.stream_ptr()), "ss_song_place")
+    return out
