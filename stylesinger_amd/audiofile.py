@@ -72,3 +72,27 @@ def load_audio(path):
     raw = raw[:len(raw) // align * align]
     x = _decode(raw, tag, bits, name).reshape(-1, channels)
     return (x[:, 0].copy() if channels == 1 else x.mean(axis=1, dtype=np.float32)), int(rate)
+
+
+def as_waveform(audio, default_sr, what):
+    """The audio entries of `preprocess_input`'s dict (`what` = the key: "ref_audio", "pitch_audio"): the path of a WAV file (str / bytes /
+    PathLike -> `load_audio`), a `(waveform, sample_rate)` pair, or a bare array read at `default_sr` Hz - refused where the key has no rate
+    to read it at (`default_sr=None`). -> (float32 mono samples, sample rate, the decoded path or None)."""
+    if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__"):
+        return (*load_audio(audio), os.fsdecode(audio))
+    if isinstance(audio, (tuple, list)) and len(audio) == 2 and np.ndim(audio[1]) == 0 and np.ndim(audio[0]) == 1:
+        return np.asarray(audio[0], dtype=np.float32), int(audio[1]), None
+    if default_sr is None:
+        raise ValueError(f"preprocess_input: inp['{what}'] must be a WAV path or a (waveform, sample_rate) pair")
+    return np.asarray(audio, dtype=np.float32), int(default_sr), None
+
+
+def load_pcm16(path, want_sr):
+    """The strict static loader: a 16-bit PCM WAV at exactly `want_sr` Hz -> float32 mono in [-1, 1); anything else is a ValueError.
+    (`preprocess_input` reads files through `load_audio` + `resample.resample_batch`, which take other formats and rates.)"""
+    import wave
+    with wave.open(os.fsdecode(path), "rb") as wf:
+        if wf.getsampwidth() != 2 or wf.getframerate() != want_sr:
+            raise ValueError(f"{path}: need 16-bit PCM at {want_sr} Hz (got {8 * wf.getsampwidth()} bit, {wf.getframerate()} Hz)")
+        pcm = np.frombuffer(wf.readframes(wf.getnframes()), dtype="<i2").astype(np.float32).reshape(-1, wf.getnchannels())
+    return pcm.mean(axis=1) / 32768.0

@@ -2,8 +2,8 @@
 
 The reference was trained on segments of at most `max_frames: 3000` (16 s) and its self-attention and style aligner run over the whole frame
 axis, so a song cannot go through `forward` as one item. `plan_song` (host, pure: no device is touched) cuts the reference's `inp` dict into
-segments and batches; `StyleSingerInfer.sing_score` renders the plan's batches and puts the results on one timeline with the two kernels of
-csrc/song.hip (`song_offsets`, `song_place` below). DESIGN.md §3.4h.
+segments and batches; `sing_score` below (what `StyleSingerInfer.sing_score` runs) renders the plan's batches and puts the results on one timeline
+with the two kernels of csrc/song.hip (`song_offsets`, `song_place` below). DESIGN.md §3.4h.
 
 Policy
   * A phone is a REST when note_type == 1 or note == 0. A MINIMAL PHRASE ends at phone i when i is a rest and i + 1 is not, or i is the last phone:
@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .producers import has_features, row
 
 PITCH_KEYS = ("pitch_hz", "pitch_audio", "pitch_shift")
 NO_PH_DUR = ("song-level pitch control ({keys}) needs inp['ph_dur'] (seconds per phone): without it the durations are the model's own, so the "
@@ -224,4 +225,84 @@ def song_place(src, seg, lens, offsets, unit, out, win=None, flags=None, cap=Non
     L.check(L.load().ss_song_place(L.ptr(src), lds, L.ptr(seg), B, L.ptr(lens), L.ptr(offsets), lens.numel(), int(unit), L.ptr(win),
                                    0 if win is None else win.numel(), L.ptr(out), out.numel() if cap is None else int(cap), L.ptr(flags),
                                    L.stream_ptr()), "ss_song_place")
+    return out
+
+
+# ---- the renderer: `StyleSingerInfer.sing_score` ----------------------------------------------------------------------------------------------
+def _song_reference(ins, inp, vad_flags):
+    """The reference of a song, processed ONCE: (ref_mels [1, Tr, 80], ref_f0 [1, Tr], spk_embed [1, 256], emo_embed [1, 256]) on the device,
+    from the features in `inp` (`mel`, `spk_embed`, `emo_embed`, `f0`: as `infer_once` accepts them) or from inp['ref_audio'] through the
+    producers of `_device_batch`."""
+    d = ins.device
+    if has_features(inp):
+        from .pitch import norm_interp_f0
+        f0, _uv = norm_interp_f0(np.asarray(inp["f0"]), ins.hparams)
+        return (row(inp["mel"], torch.float32).to(d), f0[None].to(d), row(inp["spk_embed"], torch.float32).to(d),
+                row(inp["emo_embed"], torch.float32).to(d))
+    if inp.get("ref_audio") is None:
+        raise ValueError("sing_score: give inp['ref_audio'] (the reference voice), or its features mel / spk_embed / emo_embed / f0")
+    one = {k: inp[k] for k in ("ref_audio", "ref_sr", "ph", "ph_token", "note", "note_dur", "note_type") if k in inp}
+    b = ins._device_batch(one, vad_flags)
+    inp.setdefault("ph_token", one["ph_token"])
+    return b["ref_mels"], b["ref_f0"], b["spk_embed"], b["emo_embed"]
+
+
+@torch.no_grad()
+def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None):
+    """The body of `StyleSingerInfer.sing_score` (arguments and result: its docstring); `ins` = the infer object. The flow is the module docstring's:
+    reference once, plan, batches through `infer_batches`, stitch on the device, loudness over the whole song."""
+    hp, d = ins.hparams, ins.device
+    sr, hop = int(hp["audio_sample_rate"]), int(ins.vocoder.model.hop)
+    inp = dict(inp)
+    check_pitch_keys(inp)   # pitch control without ph_dur is refused before a device is touched
+    seed = hp["seed"] if seed is None else seed
+    ref_mels, ref_f0, spk, emo = _song_reference(ins, inp, vad_flags)
+    if inp.get("pitch_audio") is not None:   # the guide vocal is tracked on the device; the planner takes its contour
+        hz, _n = ins._pitch_inputs({"pitch_audio": inp.pop("pitch_audio")})["pitch_hz"]
+        inp["pitch_hz"] = hz[0].cpu().numpy()
+    plan = plan_song(inp, sr=sr, hop=hop, max_seconds=max_seconds, segment_batch=segment_batch, ph_encoder=ins.ph_encoder)
+    S = len(plan.segments)
+    style = ins.model.encode_style(ref_mels, ref_f0)
+    fade = max(0, int(round(float(fade_ms) * sr / 1000.0))) if S > 1 else 0
+    win = torch.from_numpy(fade_window(fade)).to(d) if fade else None
+    segs_dev, rows_dev = [], []
+    for i, hb in enumerate(plan.batches):   # everything the stitch needs from the host goes up before the first batch runs
+        nb = len(plan.rows[i])
+        b = {k: ((v[0].to(d), v[1]) if k == "pitch_hz" else v.to(d) if torch.is_tensor(v) else v) for k, v in hb.items()}
+        rep = lambda x: x.expand(nb, *x.shape[1:]).contiguous()
+        b.update(spk_embed=rep(spk), emo_embed=rep(emo), ref_mels=ref_mels.expand(nb, -1, -1), ref_f0=ref_f0.expand(nb, -1),
+                 style_cache={k: rep(v) for k, v in style.items()})
+        plan.batches[i] = b
+        rows_dev.append(torch.tensor(plan.rows[i], dtype=torch.long).to(d))
+        segs_dev.append(rows_dev[-1].to(torch.int32))
+    results = list(ins.infer_batches(plan.batches, in_flight=in_flight, seed=seed))
+    lens = torch.zeros(S, device=d, dtype=torch.int32)
+    for rows, res in zip(rows_dev, results):
+        lens.index_copy_(0, rows, res["lens"].to(torch.int32))
+    offsets = song_offsets(lens)
+    cap = sum(int(res["mel"].shape[0]) * int(res["mel"].shape[1]) for res in results)   # frames: no segment is longer than its batch
+    wav, mel, f0 = (torch.empty(cap * u, device=d, dtype=torch.float32) for u in (hop, 80, 1))
+    flags = torch.zeros(1, device=d, dtype=torch.int32)
+    for seg, res in zip(segs_dev, results):
+        song_place(res["wav"].contiguous(), seg, lens, offsets, hop, wav, win=win, flags=flags)
+        song_place(res["mel"].contiguous(), seg, lens, offsets, 80, mel, flags=flags)
+        song_place(res["f0"].contiguous(), seg, lens, offsets, 1, f0, flags=flags)
+    *starts, flagged = (int(v) for v in torch.cat([offsets, flags.to(torch.int64)]).cpu())   # the one host sync of the stitch
+    if flagged != 0:
+        raise L.StyleSingerHipError(f"sing_score: ss_song_place clamped or refused a segment (flags {flagged}): the plan and the rendered "
+                                    "batches disagree")
+    F = starts[-1]
+    out = dict(wav=wav[:F * hop], mel=mel[:F * 80].view(F, 80), f0=f0[:F], plan=plan, segments=[])
+    for s, g in enumerate(plan.segments):
+        g["start_frame"], g["n_frames"] = starts[s], starts[s + 1] - starts[s]
+        out["segments"].append({k: g[k] for k in ("first", "last", "start_frame", "n_frames", "batch", "row")})
+    long_ = [s for s, g in enumerate(plan.segments) if g["n_frames"] > 3000]
+    if long_:
+        warnings.warn(f"sing_score: {len(long_)} segment(s) came out longer than the 3000 frames the model was trained on (first: phones "
+                      f"[{plan.segments[long_[0]]['first']}, {plan.segments[long_[0]]['last']}), {plan.segments[long_[0]]['n_frames']} frames); lower "
+                      "max_seconds or add rests")
+    target = out_lufs if out_lufs is not None else hp.get("out_loudness_lufs")
+    if target is not None:
+        y, lufs = ins._to_lufs(out["wav"][None], [F * hop], target)
+        out["wav"], out["lufs"] = y[0], float(lufs[0])
     return out

@@ -681,7 +681,7 @@ def test_entry_point_host_logic_without_a_gpu(tmp_path, golden_dir):
     import wave
     import warnings
     import numpy as np
-    from stylesinger_amd import vadtrim, writer
+    from stylesinger_amd import audiofile, vadtrim, writer
     from stylesinger_amd.infer import StyleSingerInfer
     inf = StyleSingerInfer.__new__(StyleSingerInfer)       # no device: only the host helpers are exercised
     if not vadtrim.have_webrtcvad():
@@ -706,11 +706,11 @@ def test_entry_point_host_logic_without_a_gpu(tmp_path, golden_dir):
         wf.setsampwidth(2)
         wf.setframerate(48000)
         wf.writeframes(pcm.tobytes())
-    a = StyleSingerInfer._load_wav(str(p), 48000)
-    b = StyleSingerInfer._load_wav(os.fsencode(str(p)), 48000)
+    a = audiofile.load_pcm16(str(p), 48000)
+    b = audiofile.load_pcm16(os.fsencode(str(p)), 48000)
     assert np.array_equal(a, b) and np.array_equal(a, pcm.astype(np.float32) / 32768.0)
     with pytest.raises(ValueError, match="16-bit PCM at 44100"):
-        StyleSingerInfer._load_wav(str(p), 44100)
+        audiofile.load_pcm16(str(p), 44100)
     # the example score = the reference's example_run input (fixture generated from the reference by oracle/gen_golden.py --round6)
     gold = json.load(open(os.path.join(golden_dir, "token_encoder.json")))
     ex = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylesinger_amd", "example_input.json")))
@@ -722,3 +722,63 @@ def test_entry_point_host_logic_without_a_gpu(tmp_path, golden_dir):
     with wave.open(str(tmp_path / "o.wav"), "rb") as wf:
         got = np.frombuffer(wf.readframes(wf.getnframes()), dtype="<i2")
     assert np.array_equal(got, (x * 32767).astype(np.int16)) and x[1] == 0.5, "input not modified"
+
+
+def test_as_waveform_is_the_one_audio_argument_rule(tmp_path):
+    """`audiofile.as_waveform`: what `inp['ref_audio']` / `inp['pitch_audio']` may be - a path (str / bytes / PathLike), a `(waveform, sample_rate)`
+    pair, or (where the key has a default rate) a bare array. Anything that is not a path or a well-formed pair takes the bare-array branch, as
+    the intake always did: a 2-D array comes back as it is, a pair with a non-scalar rate is what numpy makes of it (a ragged-array ValueError)."""
+    import pathlib
+    import wave
+    from stylesinger_amd import audiofile
+    p = tmp_path / "a.wav"
+    pcm = (np.arange(-500, 500) * 30).astype("<i2")
+    with wave.open(str(p), "wb") as wf:
+        wf.setnchannels(1)
+        wf.setsampwidth(2)
+        wf.setframerate(48000)
+        wf.writeframes(pcm.tobytes())
+    want = pcm.astype(np.float32) / 32768.0
+    for what, default_sr in (("ref_audio", 44100), ("pitch_audio", None)):
+        for arg in (str(p), os.fsencode(str(p)), pathlib.Path(p)):
+            wav, sr, path = audiofile.as_waveform(arg, default_sr, what)
+            assert wav.dtype == np.float32 and np.array_equal(wav, want) and sr == 48000 and path == str(p), (what, type(arg))
+        for pair in ((want.astype(np.float64), 44100), [want, np.int64(44100)]):
+            wav, sr, path = audiofile.as_waveform(pair, default_sr, what)
+            assert wav.dtype == np.float32 and np.array_equal(wav, want) and sr == 44100 and type(sr) is int and path is None
+    wav, sr, path = audiofile.as_waveform(want.tolist(), 32000, "ref_audio")
+    assert wav.dtype == np.float32 and np.array_equal(wav, want) and sr == 32000 and path is None
+    two_d = np.stack([want, want])
+    wav, sr, path = audiofile.as_waveform(two_d, 32000, "ref_audio")
+    assert wav.shape == (2, 1000) and sr == 32000 and path is None
+    with pytest.raises(ValueError, match="inhomogeneous|sequence"):
+        audiofile.as_waveform((want, [44100]), 32000, "ref_audio")
+    with pytest.raises(ValueError, match="inhomogeneous|sequence"):
+        audiofile.as_waveform((two_d, 44100), 32000, "ref_audio")
+    for bad in (want, two_d, (want, [44100]), (two_d, 44100)):
+        with pytest.raises(ValueError, match=r"preprocess_input: inp\['pitch_audio'\] must be a WAV path or a \(waveform, sample_rate\) pair"):
+            audiofile.as_waveform(bad, None, "pitch_audio")
+
+
+def test_from_checkpoints_forwards_the_constructor_keywords(monkeypatch):
+    """`from_checkpoints(hparams, exp_dir, vocoder_dir, **ctor)`: the form `example_run`'s docstring advertises (`emotion_state`, `speaker_state`,
+    `phone_set` next to the two directories) reaches the constructor; a missing model checkpoint is still the reference's FileNotFoundError."""
+    from stylesinger_amd import ckpt
+    from stylesinger_amd.infer import StyleSingerInfer
+    model, voc, vcfg, emo, spk = (object() for _ in range(5))
+    asked = []
+    monkeypatch.setattr(ckpt, "read_state", lambda d, name: (asked.append((d, name)), (model if d == "exp" else None, None))[1])
+    monkeypatch.setattr(ckpt, "load_vocoder_ckpt", lambda d: (asked.append(d), (voc, vcfg))[1])
+
+    class Recorder(StyleSingerInfer):
+        def __init__(self, hparams=None, **kw):
+            self.seen = dict(kw, hparams=hparams)
+    hp = dict(seed=3)
+    ins = Recorder.from_checkpoints(hp, "exp", "voc", emotion_state=emo, speaker_state=spk, phone_set="ps.json", loudness="bs1770", device="cuda:1")
+    assert type(ins) is Recorder and asked == [("exp", "model"), "voc"]
+    assert ins.seen == dict(hparams=hp, model_state=model, vocoder_state=voc, vocoder_config=vcfg, emotion_state=emo, speaker_state=spk,
+                            phone_set="ps.json", loudness="bs1770", device="cuda:1")
+    for k, v in dict(model_state=model, vocoder_state=voc, vocoder_config=vcfg, emotion_state=emo, speaker_state=spk).items():
+        assert ins.seen[k] is v, k
+    with pytest.raises(FileNotFoundError, match=r"\| ckpt not found in nowhere\."):
+        Recorder.from_checkpoints(hp, "nowhere", "voc")
