@@ -205,9 +205,15 @@ int64_t ss_split3_gemm16_elems(int Np, int Kp);
  * bias, residual R, post_scale, accumulate, row mask) and the input leaky-relu of the HiFi-GAN ResBlocks (hifigan_nsf.py:54-61 /
  * hifigan.py ResBlock1): the taps are split into ceil(k/3) groups of three, each an F(4,3) product, six accumulators over all groups.
  * args as for ss_conv_gemm with W = ss_pack_conv_weight of the transformed taps [C][C][6*ceil(k/3)] (ss_wino43_weight_transform per
- * group, zero-padded last group), Kp == Np == N == Cin == C (multiple of 64), fp32 only. ss_wino43_conv_ok: 1 if (C, k, dilation) is covered. */
+ * group, zero-padded last group), fp32 only. ss_wino43_conv_ok: 1 if the square conv (C, k, dilation) is covered: C a multiple of 32
+ * (multiples of 64 run 64-column tiles, the others - the C = 32 stage - 32-column tiles), k = 3 | 7 | 11, dilation 1 | 3 | 5.
+ * The same kernel takes rectangular convs (ss_wino43_conv_ok4; additive export, ABI 20): Cin a multiple of 32 with Kp == Cin, any N <= Np
+ * (Np a multiple of 32 as ss_pack_conv_weight leaves it; W = the transformed taps [N][Cin][6*ceil(k/3)]), any odd k = 3..11, and the
+ * SS_ACT_GELU_ epilogue (without an input leaky-relu) next to none | leaky-relu; pre_scale, mask_rows = 0 and the residual / accumulate
+ * forms as in ss_conv_gemm. Rows outside [0, lens[b]) of an item read as 0 whatever mask_rows says, exactly as in ss_conv_gemm. */
 int ss_wino43_conv(const ss_conv_gemm_args* args, int k, int dilation, void* stream);
 int ss_wino43_conv_ok(int C, int k, int dilation);
+int ss_wino43_conv_ok4(int Cin, int Cout, int k, int dilation);
 /* Winograd F(2,3) form of the 3-tap dilated conv + SS_EPI_GATE epilogue (net.py:66-73): same arguments as the
  * direct call except that W is the TRANSFORMED weight packed as a 4-"tap" tensor (ss_wino_weight_transform then
  * ss_pack_conv_weight(k=4, interleave_half=C)) and the dilation is passed explicitly (power of two). 1.5x fewer
@@ -745,7 +751,7 @@ typedef struct ss_hifigan {
   const float* src_b; /* [1] */
   /* 1 = bf16-operand MFMA for conv_pre, the transposed convs and the residual blocks (conv_post and the NSF source stay fp32) */
   int32_t mfma_bf16;
-  /* 1 = ResBlock convs with a Winograd pack below run as grouped F(4,3) (ss_wino43_conv; fp32 mode, C a multiple of 64, k in {3,7,11},
+  /* 1 = ResBlock convs with a Winograd pack below run as grouped F(4,3) (ss_wino43_conv; fp32 mode, C a multiple of 32, k in {3,7,11},
    * dilation in {1,3,5}); 0 / NULL pack = direct ss_conv_gemm. Same results to fp32 rounding (wav max error 1.3e-7 vs 0.9e-7 on the
    * reference's golden cases, oracle/wino_vocoder_numerics.py) */
   int32_t wino;

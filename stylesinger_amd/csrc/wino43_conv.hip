@@ -11,13 +11,19 @@
 // waveforms): wav max error 1.1e-7 / 1.3e-7 on the two golden cases (direct fp32: 0.9e-7); tests keep WAV_TOL = 1e-5.
 //
 // Quads are formed inside groups of 4 d frames (t = (q / d) 4 d + q % d) for ANY dilation (D is a template parameter: the vocoder's 1, 3, 5).
-// Tile = 64 quads (256 frames) x 64 output channels, 4 waves x 6 accumulators of 32 x 32; K loop over (group, 32-channel chunk), six
+// Tile = 64 quads (256 frames) x 64 output channels (x 32 where Np is no multiple of 64: the C = 32 stage), 4 (2) waves x 6 accumulators of 32 x 32; K loop over (group, 32-channel chunk), six
 // components per step, one LDS tile + barrier per component as in wino43_gate.hip; components are consumed in the order c1, c0, c5, c2, c3,
 // c4 with the shared terms of wino43_gate16.hip (18 VALU per element instead of 28; the raw rows are dead after the third build, so the
 // rows of the next step are fetched three components ahead). Rows outside [0, len) are out of the buffer range -> read 0: the row offset
 // lives in a VGPR (negative = out of range), the K-chunk offset in an SGPR; moving to the next tap group adds 3 d rows to the VGPRs.
 // The leaky-relu of the input is applied ONCE per fetched row register (max(x, slope x) == x >= 0 ? x : slope x for 0 < slope < 1): one
 // packed multiply per two elements + one bare v_max_f32 per element (ss_lrelu_max).
+//
+// The same kernel runs rectangular convs (Cin != N: Kp / 32 input chunks and Np / BN column tiles are independent loops) with any odd
+// k = 3..11, e.g. the k = 9, 256 -> 1024 first FFN conv of the FFT decoder blocks (three tap groups, 18 of the 36 direct products, GELU
+// epilogue). Zero-padding rule, the one of conv_gemm_kernel.h: the A operand of item b is a buffer of lens[b] * lda floats (lens[b]
+// clamped to [0, T]; T without lens), so every tap that lands on a row < 0 or >= lens[b] reads 0 - with mask_rows = 0 too; mask_rows only
+// decides whether OUTPUT rows >= lens[b] are written as 0 or as the conv of that zero-extended input. Rows >= T are never written.
 #include "common.h"
 #include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
@@ -30,7 +36,6 @@ using namespace ss_dev;
 constexpr int BK = 32;
 constexpr int LD = BK;
 constexpr int BQ = 64;  // quads per tile (= 256 output frames)
-constexpr int BN = 64;
 constexpr int NC = 6;
 
 template <int D>
@@ -39,9 +44,18 @@ __device__ __forceinline__ int frame_of_quad(int q) {
   else return (q / D) * (4 * D) + (q % D);
 }
 
-template <int D, bool LRELU>
-__global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_args a, int q_tiles_per_item, int q_tiles, int n_tiles,
-                                                             int groups, int lo_rows) {
+// BN = column-tile width. 64: four waves as 2 x 2 wave tiles of 32 quads x 32 columns (256 threads, two staging passes per operand).
+// 32: two waves stacked over the 64 quads, one column block (128 threads: four staging passes for the quad rows, two for the weights) - at
+// C = 32 the only column tile, so every input row is transformed once; one wave per SIMD, two or more workgroups per CU.
+// GELU: the epilogue activation of the FFT blocks' first FFN conv (ss_gelu, the expression ss_conv_gemm applies for SS_ACT_GELU_).
+template <int D, bool LRELU, int BN, bool GELU>
+__global__ __launch_bounds__(BN * 4, BN == 64 ? 2 : 1) void wino43_conv_kernel(const ss_conv_gemm_args a, int q_tiles_per_item, int q_tiles,
+                                                                               int n_tiles, int groups, int lo_rows) {
+  static_assert(BN == 64 || BN == 32, "column tile of 64 or 32");
+  constexpr int NT = BN * 4;        // threads
+  constexpr int RP = NT / 8;        // tile rows staged per pass (8 threads x float4 cover a 32-wide K chunk)
+  constexpr int AP = BQ / RP;       // staging passes over the quad rows
+  constexpr int BP = BN / RP;       // staging passes over the weight rows
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                  // [2][BQ][LD]
   float* Bs = smem + 2 * BQ * LD;    // [2][BN][LD]
@@ -58,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
   const int n0 = nt * BN;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
+  const int wm = BN == 64 ? wave >> 1 : wave, wn = BN == 64 ? wave & 1 : 0;
   const int l31 = lane & 31, lh = lane >> 5;
 
   const int len = ss_uniform_len(a.lens, b, a.T);
@@ -71,39 +85,39 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
       __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.W), 0, __builtin_amdgcn_readfirstlane(a.Np * ldw * 4), 0x00020000);
 
   const int st_c4 = tid & 7;
-  const int st_row = tid >> 3;  // 0..31; two passes cover the 64 quad rows / 64 weight rows
+  const int st_row = tid >> 3;  // 0..RP-1; AP passes cover the 64 quad rows, BP passes the BN weight rows
   // roff[i][r] = byte offset of raw row r of quad row i for the CURRENT tap group: frame t - lo + r d (+ 3 d per group). A negative
   // offset is >= 2^31 as the unsigned offset the buffer check sees -> out of range -> 0, like every frame >= len.
-  int roff[2][6];
+  int roff[AP][6];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int t = frame_of_quad<D>(q0 + st_row + i * 32);
+  for (int i = 0; i < AP; ++i) {
+    const int t = frame_of_quad<D>(q0 + st_row + i * RP);
 #pragma unroll
     for (int r = 0; r < 6; ++r) roff[i][r] = ((t - lo_rows + r * D) * a.lda + st_c4 * 4) * 4;
   }
   const int group_step = 3 * D * a.lda * 4;
-  int w_voff[2];
+  int w_voff[BP];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) w_voff[i] = ((n0 + st_row + i * 32) * ldw + st_c4 * 4) * 4;
+  for (int i = 0; i < BP; ++i) w_voff[i] = ((n0 + st_row + i * RP) * ldw + st_c4 * 4) * 4;
 
-  u32x4 rr[2][6], rb[2];
+  u32x4 rr[AP][6], rb[BP];
   auto load_rows = [&](int ci0b) {  // ci0b = byte offset of the K chunk inside a row (wave-uniform -> SGPR soffset)
     ci0b = __builtin_amdgcn_readfirstlane(ci0b);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < AP; ++i)
 #pragma unroll
       for (int r = 0; r < 6; ++r) rr[i][r] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, roff[i][r], ci0b, 0);
   };
   auto load_b = [&](int cb) {  // cb = byte offset of the weight chunk inside a packed row (wave-uniform)
     cb = __builtin_amdgcn_readfirstlane(cb);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[i], cb, 0);
+    for (int i = 0; i < BP; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[i], cb, 0);
   };
   const float slope = a.a_lrelu;
   auto act_rows = [&]() {
     if constexpr (LRELU) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < AP; ++i)
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
           const f32x4 v = __builtin_bit_cast(f32x4, rr[i][r]);
@@ -117,15 +131,17 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
         }
     }
   };
-  const int a_wr[2] = {lds_slot(st_row, st_c4), lds_slot(st_row + 32, st_c4)};
+  int a_wr[AP];
+#pragma unroll
+  for (int i = 0; i < AP; ++i) a_wr[i] = lds_slot(st_row + i * RP, st_c4);
   // position p builds component ORD[p] (c1, c0, c5, c2, c3, c4) from the raw rows / the kept terms
   //   A = r4 - 4 r2, B = r3 - 4 r1, C = r4 - r2, Dd = r3 - r1   ->   c1 = A + B, c2 = A - B, c3 = C + 2 Dd, c4 = C - 2 Dd
   //   c0 = 4 r0 - 5 r2 + r4, c5 = 4 r1 - 5 r3 + r5
-  float4 tA[2], tB[2], tC[2], tD[2];
+  float4 tA[AP], tB[AP], tC[AP], tD[AP];
   auto store_a = [&](float* Ad, auto ptag) {
     constexpr int P = decltype(ptag)::value;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < AP; ++i) {
       auto R = [&](int q) { return __builtin_bit_cast(float4, rr[i][q]); };
       float4 v;
       if constexpr (P == 0) {
@@ -150,8 +166,8 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
   };
   auto store_b = [&](float* Bd) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-      *reinterpret_cast<float4*>(Bd + lds_slot(st_row + i * 32, st_c4)) = __builtin_bit_cast(float4, rb[i]);
+    for (int i = 0; i < BP; ++i)
+      *reinterpret_cast<float4*>(Bd + lds_slot(st_row + i * RP, st_c4)) = __builtin_bit_cast(float4, rb[i]);
   };
 
   f32x16 acc[NC];
@@ -216,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
     if constexpr (decltype(fetch_rows_tag)::value) {
       if (new_group) {   // wave-uniform: the next step starts the next tap group, 3 d frames further
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < AP; ++i)
 #pragma unroll
           for (int r = 0; r < 6; ++r) roff[i][r] += group_step;
       }
@@ -309,7 +325,8 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
       for (int o = 0; o < 4; ++o) {
         const int t = tq[e] + o * D;
         float v = (z[o] + bs) * a.pre_scale;
-        if (lrelu_out) v = ss_lrelu(v, a.act_slope);
+        if constexpr (GELU) v = ss_gelu(v);
+        else if (lrelu_out) v = ss_lrelu(v, a.act_slope);
         v = (v + rv[e][o]) * a.post_scale + pv[e][o];
         if (t >= row_lim) v = 0.f;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc_c, t * ldc4 + (col * 4 + oob), 0, 0);
@@ -318,37 +335,57 @@ __global__ __launch_bounds__(256, 2) void wino43_conv_kernel(const ss_conv_gemm_
   }
 }
 
-template <int D>
+template <int D, int BN>
 void launch_conv(const ss_conv_gemm_args& a, int k, hipStream_t stream) {
   const int quads_per_item = ss_cdiv(a.T, 4 * D) * D;
   const int q_tiles_per_item = ss_cdiv(quads_per_item, BQ);
   const int q_tiles = q_tiles_per_item * a.B;
   const int n_tiles = a.Np / BN;
   const int grid = ss_cdiv(q_tiles, 8) * 8 * n_tiles;
-  const size_t lds = (size_t)2 * (BQ + BN) * LD * sizeof(float);
+  const size_t lds = (size_t)2 * (BQ + BN) * LD * sizeof(float);   // 32 KB (BN = 64) / 24 KB (BN = 32)
   const int groups = (k + 2) / 3, lo = (k - 1) / 2 * D;
-  if (a.a_lrelu != 1.0f)
-    hipLaunchKernelGGL((wino43_conv_kernel<D, true>), dim3(grid), dim3(256), lds, stream, a, q_tiles_per_item, q_tiles, n_tiles, groups, lo);
-  else
-    hipLaunchKernelGGL((wino43_conv_kernel<D, false>), dim3(grid), dim3(256), lds, stream, a, q_tiles_per_item, q_tiles, n_tiles, groups, lo);
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(BN * 4), lds, stream, a, q_tiles_per_item, q_tiles, n_tiles, groups, lo); };
+  if (a.act == SS_ACT_GELU_) {
+    go(wino43_conv_kernel<D, false, BN, true>);   // the FFN form: no input activation (checked by the caller)
+  } else if (a.a_lrelu != 1.0f) {
+    go(wino43_conv_kernel<D, true, BN, false>);
+  } else {
+    go(wino43_conv_kernel<D, false, BN, false>);
+  }
+}
+
+template <int D>
+void launch_conv(const ss_conv_gemm_args& a, int k, hipStream_t stream) {
+  if (a.Np % 64 == 0) launch_conv<D, 64>(a, k, stream);
+  else launch_conv<D, 32>(a, k, stream);
 }
 
 }  // namespace
 
+// Which convs the kernel covers. Cin % 32 == 0 (Kp == Cin: a K chunk never runs past the channels of a row), any Cout (the pack pads it to
+// Np, a multiple of 32; Np % 64 == 0 takes the 64-column tile, otherwise the 32-column one), odd k = 3..11, dilation 1 | 3 | 5.
+extern "C" int ss_wino43_conv_ok4(int Cin, int Cout, int k, int dilation) {
+  return (Cin > 0 && Cin % 32 == 0) && Cout > 0 && (k >= 3 && k <= 11 && (k & 1)) && (dilation == 1 || dilation == 3 || dilation == 5) ? 1 : 0;
+}
+
+// The square ResBlock convs of the vocoder: k = 3 | 7 | 11 as before, C a multiple of 32 (was 64).
 extern "C" int ss_wino43_conv_ok(int C, int k, int dilation) {
-  return (C % 64 == 0) && (k == 3 || k == 7 || k == 11) && (dilation == 1 || dilation == 3 || dilation == 5) ? 1 : 0;
+  return (k == 3 || k == 7 || k == 11) ? ss_wino43_conv_ok4(C, C, k, dilation) : 0;
 }
 
 extern "C" int ss_wino43_conv(const ss_conv_gemm_args* args, int k, int dilation, void* stream) {
   SS_CHECK_ARG(args != nullptr, "ss_wino43_conv: null args");
   const ss_conv_gemm_args& a = *args;
   SS_CHECK_ARG(a.A && a.W && a.C, "ss_wino43_conv: null A/W/C");
-  SS_CHECK_ARG(ss_wino43_conv_ok(a.Cin, k, dilation), "ss_wino43_conv: C=%d (multiple of 64), k=%d (3|7|11), dilation=%d (1|3|5)", a.Cin, k, dilation);
-  SS_CHECK_ARG(a.Kp == a.Cin && a.Np == a.Cin && a.N == a.Cin && (a.lda & 3) == 0, "ss_wino43_conv: square conv with Kp == Np == N == Cin");
-  SS_CHECK_ARG(a.epi == SS_EPI_STORE && (a.act == SS_ACT_NONE_ || a.act == SS_ACT_LRELU_) && !a.a_bias && a.a_scale == 1.0f && !a.mfma_bf16 &&
-                   a.group_size == 0,
-               "ss_wino43_conv: STORE epilogue, act none|lrelu, no input bias/scale, fp32, one weight set");
+  SS_CHECK_ARG(ss_wino43_conv_ok4(a.Cin, a.N, k, dilation), "ss_wino43_conv: Cin=%d (multiple of 32), N=%d, k=%d (odd, 3..11), dilation=%d (1|3|5)",
+               a.Cin, a.N, k, dilation);
+  SS_CHECK_ARG(a.Kp == a.Cin && a.Np % 32 == 0 && a.N <= a.Np && (a.lda & 3) == 0 && a.lda >= a.Cin,
+               "ss_wino43_conv: Kp == Cin, Np a multiple of 32 with N <= Np, lda a multiple of 4");
+  SS_CHECK_ARG(a.epi == SS_EPI_STORE && (a.act == SS_ACT_NONE_ || a.act == SS_ACT_LRELU_ || a.act == SS_ACT_GELU_) && !a.a_bias &&
+                   a.a_scale == 1.0f && !a.mfma_bf16 && a.group_size == 0,
+               "ss_wino43_conv: STORE epilogue, act none|lrelu|gelu, no input bias/scale, fp32, one weight set");
   SS_CHECK_ARG(a.a_lrelu > 0.0f && a.a_lrelu <= 1.0f, "ss_wino43_conv: input leaky-relu slope %g must be in (0, 1]", (double)a.a_lrelu);
+  SS_CHECK_ARG(a.act != SS_ACT_GELU_ || a.a_lrelu == 1.0f, "ss_wino43_conv: the GELU epilogue comes without an input leaky-relu");
   SS_CHECK_ARG(((int64_t)a.T + 1024) * a.lda * 4 < (1ll << 31) && (int64_t)a.T * a.ldc * 4 < (1ll << 31) &&
                    (!a.R || (int64_t)a.T * a.ldr * 4 < (1ll << 31)) && (int64_t)a.Np * ((k + 2) / 3) * NC * a.Kp * 4 < (1ll << 31),
                "ss_wino43_conv: item too large for 32-bit offsets");

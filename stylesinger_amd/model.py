@@ -177,8 +177,11 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
                     act=act, pre_scale=pre_scale, R=R, ldr=(N if R is not None else 0), mask_rows=mask_rows, **kw)
         return out
 
-    def _fft_blocks(self, pkb, x, B, T, lens):
-        """4 x EncSALayer + final LN (tts_modules.py:281-306, common_layers.py:649-673), in place on x [B,T,H]."""
+    def _fft_blocks(self, pkb, x, B, T, lens, ffn_wino=False):
+        """4 x EncSALayer + final LN (tts_modules.py:281-306, common_layers.py:649-673), in place on x [B,T,H].
+        ffn_wino: the first FFN conv as grouped Winograd F(4,3) where a pack exists (fp32 mode). The frame-level decoder asks for it; the
+        phoneme-level encoder (~28 rows against the kernel's 256-frame tile) stays on the direct kernel for that geometric reason, not a
+        measured one. The choice is per stack, never per T: a forward padded to its frame bucket must equal the unpadded one bit for bit."""
         H = self.hp["hidden_size"]
         nh = self.hp["num_heads"]
         D = H // nh
@@ -194,8 +197,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
                         ldo=H, q_bs=T * 3 * H, k_bs=T * 3 * H, v_bs=T * 3 * H, o_bs=T * H, qlens=lens, klens=lens, scale=D ** -0.5)
             self._gemm(att, ly["out"], x, B, T, lens=lens, R=x)
             L.layernorm(x, *ly["ln2"], B=B, T=T, C_=H, out=h)
-            k = ly["ffn1"].k
-            self._gemm(h, ly["ffn1"], ff, B, T, lens=lens, act=L.ACT_GELU, pre_scale=k ** -0.5, mask_rows=False)
+            f1 = ly["ffn1"]
+            if ffn_wino and f1.W43 is not None:
+                L.wino43_conv(h, f1.W43, ff, k=f1.k, dilation=1, B=B, T=T, Cin=f1.Cin, N=f1.Cout, Np=f1.Np, Kp=f1.Kp, lens=lens, bias=f1.bias,
+                              act=L.ACT_GELU, pre_scale=f1.k ** -0.5, mask_rows=False)
+            else:
+                self._gemm(h, f1, ff, B, T, lens=lens, act=L.ACT_GELU, pre_scale=f1.k ** -0.5, mask_rows=False)
             self._gemm(ff, ly["ffn2"], x, B, T, lens=lens, R=x)
         L.layernorm(x, *pkb["ln"], B=B, T=T, C_=H, out=x, lens=lens, mask_rows=True)
         return x
@@ -553,7 +560,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         L.check(lib.ss_make_positions(None, L.ptr(dec_inp), H, T * H, L.ptr(pos_t), B, T, st()), "pos dec")
         L.check(lib.ss_table_add(L.ptr(pos_t), L.ptr(tabt), tabt.shape[0], L.ptr(xd), H, T * H, B, T, H,
                                  L.ptr(self.p("decoder.pos_embed_alpha")), 1.0, 1, st()), "pos add dec")
-        xd = self._fft_blocks(pk["dec"], xd, B, T, c.lens_t)
+        xd = self._fft_blocks(pk["dec"], xd, B, T, c.lens_t, ffn_wino=True)
         ret["decoder_out"] = xd
         c.coarse_mel = torch.empty(B, T, hp["audio_num_mel_bins"], **c.f32)
         self._gemm(xd, pk["mel_out"], c.coarse_mel, B, T, lens=c.lens_t)

@@ -11,11 +11,12 @@ from . import lib as L
 
 class _Packed:
     """A conv/linear weight in the MFMA kernel's layout + its metadata."""
-    __slots__ = ("W", "bias", "Cout", "Cin", "k", "Np", "Kp", "half")
+    __slots__ = ("W", "bias", "Cout", "Cin", "k", "Np", "Kp", "half", "W43")
 
     def __init__(self, W, bias, Cout, Cin, k, half=0):
         self.W, self.bias, self.Cout, self.Cin, self.k, self.half = W, bias, Cout, Cin, k, half
         self.Np, self.Kp = W.shape[0], W.shape[1] // k
+        self.W43 = None   # the same conv as grouped F(4,3) tap groups (ss_wino43_conv), where one was packed
 
 
 def _sin_table(n, dim):
@@ -298,7 +299,14 @@ class Packing:
             sched["alphas_cumprod_f64"] = np.ascontiguousarray(np.cumprod(1.0 - betas64))
         return sched
 
-    def _pack_fft(self, prefix, n_layers):
+    def _pack_ffn1(self, p, wino):
+        """The k-tap first FFN conv; wino (the decoder, fp32 mode): also its grouped Winograd F(4,3) pack when ss_wino43_conv covers the shape."""
+        pk = self._pack_conv(p + ".ffn.ffn_1.weight", p + ".ffn.ffn_1.bias")
+        if wino and self.use_wino and pk.k >= 3 and L.load().ss_wino43_conv_ok4(pk.Cin, pk.Cout, pk.k, 1):
+            pk.W43 = L.pack_conv_weight(L.wino43_group_weight(self.p(p + ".ffn.ffn_1.weight")))
+        return pk
+
+    def _pack_fft(self, prefix, n_layers, ffn_wino=False):
         layers = []
         for i in range(n_layers):
             p = f"{prefix}.layers.{i}.op"
@@ -307,7 +315,7 @@ class Packing:
                 qkv=self._pack_conv(p + ".self_attn.in_proj_weight"),
                 out=self._pack_conv(p + ".self_attn.out_proj.weight"),
                 ln2=(self.p(p + ".layer_norm2.weight"), self.p(p + ".layer_norm2.bias")),
-                ffn1=self._pack_conv(p + ".ffn.ffn_1.weight", p + ".ffn.ffn_1.bias"),
+                ffn1=self._pack_ffn1(p, ffn_wino),
                 ffn2=self._pack_conv(p + ".ffn.ffn_2.weight", p + ".ffn.ffn_2.bias")))
         return dict(layers=layers, ln=(self.p(prefix + ".layer_norm.weight"), self.p(prefix + ".layer_norm.bias")))
 
@@ -319,7 +327,7 @@ class Packing:
             raise L.StyleSingerHipError("StyleSingerHIP needs its weights on a GPU (model.to('cuda')): there is no CPU path")
         pk = {}
         pk["enc"] = self._pack_fft("encoder", hp["enc_layers"])
-        pk["dec"] = self._pack_fft("decoder", hp["dec_layers"])
+        pk["dec"] = self._pack_fft("decoder", hp["dec_layers"], ffn_wino=True)
         pk["mel_out"] = self._pack_conv("mel_out.weight", "mel_out.bias")
         pk["spk"] = self._pack_conv("spk_embed_proj.weight", "spk_embed_proj.bias")
         pk["emo"] = self._pack_conv("emo_embed_proj.weight", "emo_embed_proj.bias")
