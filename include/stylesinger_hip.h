@@ -869,6 +869,27 @@ int ss_loudness_measure(const float* x, int64_t ldx, int Lx, const int32_t* n, c
 int ss_loudness_apply(const float* x, int64_t ldx, int Lx, const int32_t* n, const float* gain, const float* peak, float* y, int64_t ldy, int Ly,
                       int B, void* stream);
 
+/* Vocoder output denoise: what `denoise(wav_out, v=hparams['vocoder_denoise_c'])` does at the end of HifiGAN.spec2wav
+ * (tasks/tts/vocoder_infer/hifigan_nsf.py:14-22, 73-74): a spectral subtraction between librosa 0.8's stft(center=True, pad_mode='constant') and
+ * istft(center=True) - librosa is un-vendored: parity UNPINNED, `stylesinger_amd/denoise.py` holds the definition and builds the table. With
+ * N = n_fft, H = hop and xz = x[b] inside [0, n[b]) and zero outside (what the buffer holds past n[b] <= Lx is padding and never read into a result):
+ *   F = 1 + n / H frames, frame i = xz[i H - N/2 ... i H + N/2 - 1]; w[k] = 0.5 - 0.5 cos(2 pi k / N); X = rfft(w frame); m = |X|;
+ *   Y = X (m - v) / m where m > v, else 0 (also for m = 0); t = w irfft(Y); frame i added at offset i H, the sum divided by the envelope sum w^2
+ *   wherever that exceeds float32 tiny; N/2 samples cut from each end.
+ *   -> y[b][0 .. n_out[b]) with n_out[b] = H (n[b] / H), written to the device array n_out; y[b][n_out[b] .. Ly) = 0. Ly >= H (Lx / H).
+ * Geometry: N a power of two in [256, 2048], H a divisor of N with 64 <= H <= N (window length = N); v finite and >= 0.
+ * table: 3 N float64 on the device followed by the same 3 N values rounded to float32: N complex twiddles by butterfly span, [2 (s + j)],
+ *   [2 (s + j) + 1] = cos, -sin of 2 pi j / (2 s) for s = 1, 2, 4, ..., N / 2 and j < s (entry 0 unused), then w[0 .. N). H < N runs in fp32 on
+ *   the float copy; H == N, where the envelope falls to 0 at every frame edge and the division
+ *   amplifies rounding error by 1 / w, runs in float64.
+ * One launch: a workgroup transforms the frames of its run of outputs in LDS (two frames per transform, halo frames recomputed) and overlap-adds them there in
+ * ascending frame order. No atomics: bit-identical from run to run, and an item's row does not depend on B, Lx, Ly or the other items.
+ * ss_wav_denoise_workspace_bytes: 0 for every supported geometry (ws may then be NULL), < 0 for an unsupported one. No allocation:
+ * graph-capturable. y must not alias x: the ranges [x, x + (B - 1) ldx + Lx) and [y, y + (B - 1) ldy + Ly) must be disjoint (checked). */
+int64_t ss_wav_denoise_workspace_bytes(int B, int Lx, int n_fft, int hop);
+int ss_wav_denoise(const float* x, int64_t ldx, int Lx, const int32_t* n, float* y, int64_t ldy, int Ly, int32_t* n_out, int B, int n_fft, int hop,
+                   float v, const double* table, void* ws, int64_t ws_bytes, void* stream);
+
 /* A pitch contour in Hz fitted to a score's frame count (input producer of forward(pitch_hz=...); definition: `contour_fit` in
  * stylesinger_amd/pitch.py). f0_hz [B][ldc], lens_c[b] <= Lc valid source frames (0 = unvoiced); out [B][ldo], T columns written; lens_t[b] <= T
  * target frames per item - a DEVICE array, e.g. what ss_length_regulate wrote, so the fit needs no host sync. Output frame t < lens_t[b] sits at

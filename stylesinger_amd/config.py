@@ -57,6 +57,9 @@ DEFAULT_HPARAMS = dict(
     t_bucket=64,
     # not a reference key: write the result at this BS.1770 integrated loudness in LUFS (loudness.py; None = as synthesised). Excludes out_wav_norm.
     out_loudness_lufs=None,
+    # vocoder output denoise (egs/egs_bases/tts/base.yaml:107; hifigan_nsf.py:73-74): > 0 = spectral subtraction of this magnitude after the generator
+    # (denoise.py), with the geometry keys fft_size / win_size / hop_size of the caller's hparams
+    vocoder_denoise_c=0.0,
 )
 
 # The released HiFi-GAN config ships only inside the un-vendored checkpoint
@@ -74,7 +77,7 @@ def make_hparams(overrides=None):
         for k in hp:
             if k in overrides:
                 hp[k] = overrides[k]
-        for k in ("vocab_size",):
+        for k in ("vocab_size", "fft_size", "win_size"):   # (the last two have no default here: frontend.py and denoise.py hold theirs)
             if k in overrides:
                 hp[k] = overrides[k]
     return hp

@@ -67,6 +67,8 @@ class StyleSingerInfer(ReferenceProducers):
                 dictionary = self.ph_encoder
         from .loudness import resolve_loudness
         self._loud_norm = resolve_loudness(hparams, loudness)   # refuses the bare flag, before a device is touched
+        from .denoise import resolve_denoise
+        resolve_denoise(self.hparams)   # hparams['vocoder_denoise_c'] > 0: a geometry the kernel does not compute is refused here (the vocoder plugin applies it)
         if self.hparams.get("out_loudness_lufs") is not None and (self.hparams.get("out_wav_norm") or (hparams or {}).get("out_wav_norm")):
             raise ValueError("hparams: out_loudness_lufs and out_wav_norm exclude each other (a loudness target or peak normalisation, not both)")
         if device is None:
@@ -175,6 +177,9 @@ class StyleSingerInfer(ReferenceProducers):
         # side stream: a default size up front, and a batch longer than that grows it when the batch is pulled (the tables only grow).
         warm = 2048
         self.model.warm_caches(warm, self.device)
+        if getattr(self.vocoder, "_denoise_v", None) is not None:   # the denoise table of this device: uploaded here, not on a side stream
+            from .denoise import device_table, geometry
+            device_table(geometry(self.vocoder.hparams)[0], self.device)
         for i, batch in enumerate(batches):
             need = max(int(batch["mel2ph"].shape[1]) if batch.get("mel2ph") is not None else 0, int(batch["ref_mels"].shape[1]))
             if need > warm:
@@ -195,6 +200,9 @@ class StyleSingerInfer(ReferenceProducers):
 
     @torch.no_grad()
     def vocode(self, mel, f0, lens, noise=None, seed=1234):
+        """Clip the mel and run the vocoder plugin's batched form; with hparams['vocoder_denoise_c'] > 0 that denoises every item on the device right
+        after the generator (`HifiGAN.spec2wav_batch`): before `out_lufs`, before the PCM16 writer and, in `sing_score`, per segment before the stitch -
+        the song then holds what single `spec2wav` calls would return."""
         hp = self.hparams
         mel_c = torch.empty_like(mel)
         L.check(L.load().ss_clip(L.ptr(mel), L.ptr(mel_c), mel.numel(), float(hp["mel_vmin"]), float(hp["mel_vmax"]), L.stream_ptr()), "ss_clip")
@@ -309,7 +317,8 @@ def main(argv=None):
     --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim]` = the reference's
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
     sing the score on a given pitch contour instead of the predicted one. `--loud-norm`: loudness-normalise the reference audio as a model trained with
-    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS.
+    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
+    subtraction of V, e.g. 0.1) after the generator, before the loudness target and the writer.
     `--score song.json [--max-seconds 12] [--segment-batch 8] [--fade-ms 5] [--segments-out timeline.json]`: sing a score of any length (the keys of
     example_input.json, optionally `ph_dur`; its `ref_audio` unless --ref-audio is given) with `sing_score`; pitch flags then need `ph_dur` in the score."""
     import argparse
@@ -328,6 +337,8 @@ def main(argv=None):
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
+    ap.add_argument("--vocoder-denoise-c", type=float, help="spectral subtraction of this magnitude on the vocoder's output "
+                    "(hparams['vocoder_denoise_c'], e.g. 0.1; 0 = off)")
     ap.add_argument("--score", help="a score of any length as JSON (the keys of example_input.json, optionally ph_dur = seconds per phone): split at "
                     "its rests, rendered in batches, stitched on the device")
     ap.add_argument("--max-seconds", type=float, default=12.0, help="--score: longest merged segment")
@@ -371,6 +382,8 @@ def main(argv=None):
         hp["loud_norm"] = True
     if a.out_lufs is not None:
         hp["out_loudness_lufs"] = a.out_lufs
+    if a.vocoder_denoise_c is not None:
+        hp["vocoder_denoise_c"] = a.vocoder_denoise_c
     ctor = dict(exp_dir=a.exp_dir, vocoder_dir=a.vocoder_dir, emotion_state=emo.get("model_state", emo),
                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
     if score is not None:

@@ -14,6 +14,7 @@ import torch
 from . import lib as L
 from . import spec as _spec
 from .config import make_hparams, make_vocoder_config
+from .denoise import denoise_batch, geometry as denoise_geometry, resolve_denoise
 
 REGISTERED_VOCODERS = {}
 
@@ -228,6 +229,8 @@ class HifiGAN(BaseVocoder):
 
     def __init__(self, config=None, state_dict=None, device="cuda", hparams=None):
         self.hparams = make_hparams(hparams)
+        # hparams['vocoder_denoise_c'] > 0 (hifigan_nsf.py:73-74): v, or None = off; its geometry keys are checked here, before a device is touched
+        self._denoise_v = resolve_denoise(self.hparams)
         self.config = make_vocoder_config(config)
         self.device = torch.device(device)
         self.model = HifiGanGeneratorHIP(self.config)
@@ -244,8 +247,21 @@ class HifiGAN(BaseVocoder):
         c = torch.as_tensor(np.asarray(mel), dtype=torch.float32)[None].to(self.device)
         f = torch.as_tensor(np.asarray(f0), dtype=torch.float32)[None].to(self.device)
         y = self.model(c, f, noise=kwargs.get("noise"), seed=kwargs.get("seed", 1234))
+        if self._denoise_v is not None:   # the hparams' own geometry, as the reference's denoise(); length hop_size * (len // hop_size)
+            n_fft, hop = denoise_geometry(self.hparams)
+            y, _ = denoise_batch(y, [y.shape[1]], n_fft, hop, n_fft, self._denoise_v)
         return y.view(-1).cpu().numpy()
 
     def spec2wav_batch(self, mel, f0, lens=None, **kwargs):
-        """Device tensors in/out: mel [B,T,80], f0 [B,T], lens int32 [B] -> wav [B,T*hop]."""
-        return self.model(mel, f0, lens=lens, **kwargs)
+        """Device tensors in/out: mel [B,T,80], f0 [B,T], lens int32 [B] -> wav [B,T*hop]. With hparams['vocoder_denoise_c'] > 0 every item is
+        denoised over its own lens[b] * hop samples right after the generator (what single `spec2wav` calls would return; zeros beyond)."""
+        out = self.model(mel, f0, lens=lens, **kwargs)
+        if self._denoise_v is None:
+            return out
+        n_fft, hop = denoise_geometry(self.hparams)
+        if hop != self.model.hop:   # then n_out == n: the frame grid of the batch stays what `lens` says
+            raise L.StyleSingerHipError(f"vocoder_denoise_c: hop_size={hop} is not supported on the batched path: must equal the generator's hop "
+                                        f"({self.model.hop})")
+        wav = out[0] if isinstance(out, tuple) else out
+        wav, _ = denoise_batch(wav, None if lens is None else lens * hop, n_fft, hop, n_fft, self._denoise_v)
+        return (wav,) + tuple(out[1:]) if isinstance(out, tuple) else wav
