@@ -10,6 +10,7 @@
 //   times 2^(shift / 12). fr == 0 takes the source sample itself (no log2 / exp2 round trip): with shift == 0, n_c == n_t is a bit-exact copy.
 // One thread per output frame, plain vector loads and stores, no atomics: an item's frames do not depend on B, T, Lc or the other items.
 #include "common.h"
+#include "pitch_fit.h"
 #include "../../include/stylesinger_hip.h"
 
 namespace {
@@ -23,29 +24,7 @@ __global__ __launch_bounds__(PF_THREADS) void contour_fit_kernel(const float* __
   const int t = blockIdx.x * PF_THREADS + threadIdx.x;
   if (t >= T) return;
   const int n_c = ss_uniform_len(lens_c, b, Lc), n_t = ss_uniform_len(lens_t, b, T);   // clamped to [0, Lc] / [0, T]
-  float v = 0.f;
-  if (t < n_t && n_c > 0) {
-    const float* f = f0_hz + (int64_t)b * ldc;
-    const int64_t den = 2 * (int64_t)n_t;
-    int64_t num = (2 * (int64_t)t + 1) * n_c - n_t;
-    const int64_t hi = (int64_t)(n_c - 1) * den;
-    num = num < 0 ? 0 : (num > hi ? hi : num);
-    const int i0 = (int)(num / den);
-    const int64_t rem = num - (int64_t)i0 * den;
-    const int i1 = i0 + 1 < n_c ? i0 + 1 : n_c - 1;
-    const float a = f[i0], c = f[i1];
-    const float near = 2 * rem >= den ? c : a;
-    if (near > 0.f) {
-      if (rem == 0 || !(a > 0.f && c > 0.f)) {
-        v = near;   // rem == 0: near is a = the source sample itself
-      } else {
-        const float fr = (float)((double)rem / (double)den);
-        const float la = log2f(a), lc = log2f(c);
-        v = exp2f(la + fr * (lc - la));
-      }
-      v *= scale;
-    }
-  }
+  const float v = (t < n_t && n_c > 0) ? ss_contour_fit_frame(f0_hz + (int64_t)b * ldc, n_c, n_t, t, scale) : 0.f;
   out[(int64_t)b * ldo + t] = v;
 }
 

@@ -118,12 +118,15 @@ class StyleSingerInfer(ReferenceProducers):
         """batch: dict of device tensors (txt_tokens, note, note_dur, note_type, spk_embed, emo_embed, ref_mels,
         ref_f0, optional mel2ph).  Returns dict(mel [B,T,80], f0 [B,T], lens int32 [B], wav [B,T*hop]).
         Pitch control (StyleSingerHIP.forward): optional `f0` + `uv` [B, T] (the normalised contour, the reference's use_gt_f0 form), or
-        `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted.
+        `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted. With
+        `pitch_align` = "dtw" (+ `pitch_align_band`, guide frames; 0 / None = full) the contour is warped onto the score's notes instead of
+        being scaled linearly; items the aligner left to the linear fit (`model_out['pitch_align_status']` != 0) are named in a warning where
+        this method reads the lengths on the host anyway (`out_lufs`), never through a sync of its own.
         `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain).
         Optional `style_cache`: what `model.encode_style` returned for the batch's references; the style encoder is then skipped."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
-        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift") if batch.get(k) is not None}
+        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band") if batch.get(k) is not None}
         if batch.get("style_cache") is not None:   # the references' style, encoded once by the caller (model.encode_style; `sing_score`)
             passed_on["style_cache"] = batch["style_cache"]
         out = self.model(batch["txt_tokens"], mel2ph=batch.get("mel2ph"), spk_embed=batch["spk_embed"], emo_embed=batch["emo_embed"],
@@ -135,7 +138,19 @@ class StyleSingerInfer(ReferenceProducers):
             res["wav"] = self.vocode(out["mel_out"], out["f0_denorm"], out["lens"], noise=vocoder_noise, seed=seed + 101)
             if out_lufs is not None:
                 res["wav"], res["lufs"] = self._to_lufs(res["wav"], [int(v) * self.vocoder.model.hop for v in out["lens"].cpu()], out_lufs)
+                self._warn_unaligned(out)   # (the copy above synchronised)
         return res
+
+    @staticmethod
+    def _warn_unaligned(model_out, what="items"):
+        """pitch_align: name the items the aligner did not align (status != 0: they got the linear fit). Call only where the host has just waited for
+        the forward: this reads a device tensor."""
+        st = model_out.get("pitch_align_status")
+        bad = [] if st is None else [i for i, v in enumerate(st.cpu().tolist()) if v != 0]
+        if bad:
+            warnings.warn(f"pitch_align: {what} {bad} not aligned (more guide frames per score frame than the band allows, or empty): they got the "
+                          "linear fit; widen pitch_align_band")
+        return bad
 
     def _to_lufs(self, wav, lens, target):
         """The output loudness target (hparams['out_loudness_lufs'], `infer_batch(out_lufs=)`): wav [B, L] on the device, lens host ints ->
@@ -241,6 +256,7 @@ class StyleSingerInfer(ReferenceProducers):
         """inference/StyleSinger.py:53-63: drop all-zero frames, clip the mel, vocode with the predicted f0 (one item)."""
         mel_pred = res["mel"].cpu().numpy()
         self.model.check_finite(res["model_out"])   # (the copy above synchronised)
+        self._warn_unaligned(res["model_out"])
         f0_pred = res["f0"].cpu().numpy()
         mask = np.abs(mel_pred).sum(-1) > 0
         mel_pred = np.clip(mel_pred[mask], self.hparams["mel_vmin"], self.hparams["mel_vmax"])
@@ -266,7 +282,9 @@ class StyleSingerInfer(ReferenceProducers):
 
     def sing_score(self, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None):
         """Sing a score of any length in the reference's voice: `inp` = the reference's input dict (`ph` | `ph_token`, `note`, `note_dur`, `note_type`,
-        optionally `ph_dur` = seconds per phone, `pitch_hz` | `pitch_audio`, `pitch_shift`; `ref_audio` or the reference's features). The score
+        optionally `ph_dur` = seconds per phone, `pitch_hz` | `pitch_audio`, `pitch_shift`, `pitch_align` (+ `pitch_align_band_s`): every segment
+        then warps ITS slice of the contour onto its own notes, the slice's ends pinned; the planner's cut of the contour stays linear;
+        `ref_audio` or the reference's features). The score
         is cut into phrases at its rests (`song.plan_song`: policy and limits there), the reference is processed and its style encoded ONCE, the
         plan's batches run through `infer_batches` (batch i with seed + i), and the segments are put on one timeline on the device
         (`ss_song_offsets` + three `ss_song_place` per batch: the waveform with a raised-cosine fade of `fade_ms` on both sides of every joint, the
@@ -316,7 +334,8 @@ def main(argv=None):
     """`python -m stylesinger_amd.infer --exp-dir checkpoints/<exp> --vocoder-dir <hifigan dir> --emotion-ckpt <pt> --speaker-ckpt <pt>
     --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim]` = the reference's
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
-    sing the score on a given pitch contour instead of the predicted one. `--loud-norm`: loudness-normalise the reference audio as a model trained with
+    sing the score on a given pitch contour instead of the predicted one; `--pitch-align dtw [--pitch-align-band-s 2.0]`: the contour is a guide
+    with its own timing, warp it onto the score's notes (band in seconds around the linear fit, 0 = full) instead of scaling it linearly. `--loud-norm`: loudness-normalise the reference audio as a model trained with
     hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
     subtraction of V, e.g. 0.1) after the generator, before the loudness target and the writer.
     `--score song.json [--max-seconds 12] [--segment-batch 8] [--fade-ms 5] [--segments-out timeline.json]`: sing a score of any length (the keys of
@@ -334,6 +353,9 @@ def main(argv=None):
     ap.add_argument("--pitch-audio", help="sing on the pitch of this guide vocal (a WAV file, tracked on the device, 80-800 Hz) instead of the predicted f0")
     ap.add_argument("--pitch-npy", help="sing on this contour: a .npy file holding a 1-D array of Hz at the mel hop, 0 = unvoiced")
     ap.add_argument("--pitch-shift", type=float, help="transpose the given contour by this many semitones")
+    ap.add_argument("--pitch-align", choices=["dtw"], help="warp the given contour onto the score's notes by dynamic time warping (a guide vocal "
+                    "with a timing of its own) instead of scaling it linearly")
+    ap.add_argument("--pitch-align-band-s", type=float, help="--pitch-align: half-width of the band around the linear fit, seconds (default 2.0; 0 = full)")
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
@@ -350,6 +372,12 @@ def main(argv=None):
         ap.error("--pitch-audio and --pitch-npy exclude each other")
     if a.pitch_shift is not None and not (a.pitch_audio or a.pitch_npy):
         ap.error("--pitch-shift needs --pitch-audio or --pitch-npy")
+    if a.pitch_align is not None and not (a.pitch_audio or a.pitch_npy):
+        ap.error("--pitch-align needs --pitch-audio or --pitch-npy")
+    if a.pitch_align_band_s is not None and a.pitch_align is None:
+        ap.error("--pitch-align-band-s needs --pitch-align")
+    if a.pitch_align_band_s is not None and not a.pitch_align_band_s >= 0:
+        ap.error("--pitch-align-band-s: seconds >= 0 (0 = full)")
     pitch = {}
     if a.pitch_audio:
         pitch["pitch_audio"] = a.pitch_audio
@@ -357,6 +385,10 @@ def main(argv=None):
         pitch["pitch_hz"] = np.load(a.pitch_npy)
     if a.pitch_shift is not None:
         pitch["pitch_shift"] = a.pitch_shift
+    if a.pitch_align is not None:
+        pitch["pitch_align"] = a.pitch_align
+    if a.pitch_align_band_s is not None:
+        pitch["pitch_align_band_s"] = a.pitch_align_band_s
     score = None
     if a.score:
         with open(a.score) as fh:

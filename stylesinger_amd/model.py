@@ -307,6 +307,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             fitted on the device to each item's frame count once that is known (`ss_contour_fit`, pitch.contour_fit), normalised with
             `norm_interp_f0_device`, then used as above. An item whose fitted contour has no voiced frame is sung unvoiced, as
             `norm_interp_f0` treats an all-unvoiced contour (f0 = 0, uv = 1 on every frame).
+            `pitch_align="dtw"` (+ `pitch_align_band=<guide frames | None = full>`): the contour is a guide with a timing of its own (a sung take).
+            In place of the linear fit it is warped onto the score's per-frame notes by dynamic time warping (`ss_contour_align`,
+            pitch.contour_align: cents distance, band around the linear fit's diagonal; `pitch_shift` puts the guide into the score's key BEFORE the
+            comparison). `ret` gains `pitch_align_idx` [B, T] (guide frame per score frame, -1 beyond the item), `pitch_align_cost` [B] and
+            `pitch_align_status` [B] (1 = the item was not aligned and got the linear fit: more than `band` guide frames per score frame) as
+            device tensors, no sync. Default `None`: the linear fit, exactly as before.
         Both skip `ss_f0_bounds` and the f0 pair loop (and its hipGraph) and run `ss_pitch_given` in place of `ss_pitch_post`; everything from
         `pitch_embed` on is unchanged, and the mel loop draws the same noise as a predicted-f0 forward with the same `seed`. `ret` carries
         `pitch_pred`, `f0_denorm`, `f0_denorm_pred` (= `f0_denorm`, as stylesinger.py:241 yields for a given contour) and `pitch_coarse`, and
@@ -324,6 +330,16 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             raise ValueError("forward: pitch_shift transposes the pitch_hz contour; it needs pitch_hz")
         if pitch_hz is not None and not (isinstance(pitch_hz, (tuple, list)) and len(pitch_hz) == 2):
             raise ValueError("forward: pitch_hz = (contour_hz [B, Lc], lens_c)")
+        pitch_align, pitch_align_band = kwargs.get("pitch_align"), kwargs.get("pitch_align_band")
+        if pitch_align is not None and pitch_align != "dtw":
+            raise ValueError(f"forward: pitch_align={pitch_align!r}: None (the linear fit) or 'dtw'")
+        if pitch_align is not None and pitch_hz is None:
+            raise ValueError("forward: pitch_align warps the pitch_hz contour onto the score; it needs pitch_hz"
+                             + (" (f0 / uv are taken as they are)" if f0 is not None else ""))
+        if pitch_align_band is not None and pitch_align is None:
+            raise ValueError("forward: pitch_align_band is the band of pitch_align='dtw'; it needs pitch_align")
+        if pitch_align_band is not None and int(pitch_align_band) < 0:
+            raise ValueError(f"forward: pitch_align_band={pitch_align_band}: guide frames >= 0 (0 or None = the full matrix)")
         self._ensure_packed()
         # c: the per-call state the stages share (shapes, lengths, intermediate activations, the plan) and the result dict
         c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, noise=kwargs.get("noise"), seed=int(kwargs.get("seed", self.hp["seed"])),
@@ -482,7 +498,16 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             from .pitch import contour_fit_device, norm_interp_f0_device
             if pitch_hz[0].dim() != 2 or pitch_hz[0].shape[0] != B:
                 raise ValueError(f"forward: pitch_hz contour {tuple(pitch_hz[0].shape)} for a batch of {B}: expected [{B}, Lc]")
-            hz = contour_fit_device(pitch_hz[0].to(dev), pitch_hz[1], lens_t, T, 0.0 if pitch_shift is None else float(pitch_shift))
+            shift = 0.0 if pitch_shift is None else float(pitch_shift)
+            if c.kwargs.get("pitch_align") is None:
+                hz = contour_fit_device(pitch_hz[0].to(dev), pitch_hz[1], lens_t, T, shift)
+            else:   # "dtw": warp the guide onto the score's note per frame (the midi of _pitch_predicted)
+                from .pitch import contour_align_device
+                midi = torch.empty(B, T, device=dev, dtype=torch.int64)
+                L.check(_lib().ss_gather_expand_i64(L.ptr(c.note), L.ptr(c.mel2ph), L.ptr(midi), B, c.Tp, T, L.stream_ptr()), "midi")
+                hz, a_idx, a_cost, a_status = contour_align_device(pitch_hz[0].to(dev), pitch_hz[1], midi, lens_t, T,
+                                                                   band=c.kwargs.get("pitch_align_band"), shift=shift)
+                c.ret["pitch_align_idx"], c.ret["pitch_align_cost"], c.ret["pitch_align_status"] = a_idx, a_cost, a_status
             f0_g, uv_g = norm_interp_f0_device(hz, lens_t, self.hp)   # frames >= lens_t[b]: f0 = 0, uv = 0 - masked by mel2ph == 0 below
         else:  # bucket padding: f0 = 0, uv = 1 (mel2ph is 0 there anyway)
             f0_g = _pad_frames(f0.to(dev).float(), T).contiguous()
@@ -615,7 +640,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             raise L.StyleSingerHipError("non-finite mel after the diffusion loop")
 
     _FRAME_KEYS = ("mel2ph", "style", "pitch_pred", "f0_denorm", "f0_denorm_pred", "pitch_coarse", "f0_a", "uv_a", "f0_b", "uv_b",
-                   "decoder_inp", "decoder_out", "fs2_mel", "x_mask", "diff_cond", "mel_out")
+                   "decoder_inp", "decoder_out", "fs2_mel", "x_mask", "diff_cond", "mel_out", "pitch_align_idx")
 
     @classmethod
     def _crop_frames(cls, ret, T, T_out):

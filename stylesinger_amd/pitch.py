@@ -11,7 +11,9 @@ Two forms with the same contract:
 
 Pitch control (`StyleSingerHIP.forward(pitch_hz=...)`): a caller's contour in Hz lives on a frame grid of its own, the score's frame count is only
 known inside forward. `contour_fit` is the float64 definition of the fit between the two grids, `contour_fit_device` the kernel (`ss_contour_fit`,
-csrc/pitch_fit.hip) that runs it from device lengths.
+csrc/pitch_fit.hip) that runs it from device lengths. That fit is a linear time scaling: right for a contour that already has the score's timing.
+A guide vocal does not: `contour_align` (definition, integer arithmetic) / `contour_align_device` (`ss_contour_align`, csrc/contour_align.hip) warp
+the contour onto the score's per-frame notes by dynamic time warping (forward(pitch_align="dtw")).
 """
 import numpy as np
 import torch
@@ -120,3 +122,160 @@ def contour_fit_device(f0_hz, lens_c, lens_t, T, shift=0.0):
     L.check(L.load().ss_contour_fit(L.ptr(x), x.stride(0), Lc, L.ptr(lc), L.ptr(lt), float(shift), L.ptr(out), out.stride(0), int(T), B,
                                     L.stream_ptr()), "ss_contour_fit")
     return out
+
+
+# ---- contour alignment by dynamic time warping (forward(pitch_align="dtw")) ----------------------------------------------------------------------
+# Named here, passed to the kernel as arguments, not user options.
+ALIGN_CAP = 1200        # cents: a voiced pair further apart than an octave costs the same, everything beyond is equally wrong
+ALIGN_UV_COST = 300     # cents: a voicing mismatch costs what leaving the model's +-3 semitone window around the note costs (ss_f0_bounds)
+ALIGN_UNVOICED = -32768                    # the cents arrays' sentinel (int16) for an unvoiced guide frame / a rest
+ALIGN_CENTS_LO, ALIGN_CENTS_HI = -2000, 16000   # guide cents are clipped to this range and notes to MIDI 1..127 (100 .. 12700 cents): both ends lie
+#                                                 more than ALIGN_CAP outside the notes' range, so the clip cannot change a cost
+ALIGN_INF = 0x3FFFFFFF                     # D of a cell no path reaches
+ALIGN_MAX_T = L.ALIGN_MAX_T       # the kernel's caps (the LDS its layout needs): sizes beyond them are refused, never truncated
+ALIGN_MAX_LC = L.ALIGN_MAX_LC
+ALIGN_MAX_WORKSPACE_BYTES = 4 << 30        # contour_align_device refuses to allocate more direction bytes than this for one call
+
+
+def align_cents(f0_hz, shift=0.0):
+    """Guide frames in integer cents as the kernel computes them (fp32): 6900 + lrintf(1200 log2f(g / 440) + 100 shift) with every product and the
+    sum rounded to fp32 on its own, clipped to [ALIGN_CENTS_LO, ALIGN_CENTS_HI]; ALIGN_UNVOICED where not g > 0."""
+    g = np.asarray(f0_hz, dtype=np.float32)
+    v = g > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = np.float32(1200.0) * np.log2(np.where(v, g, np.float32(440.0)) / np.float32(440.0), dtype=np.float32) + np.float32(100.0) * np.float32(shift)
+    x = np.clip(x.astype(np.float32), np.float32(ALIGN_CENTS_LO - 6900), np.float32(ALIGN_CENTS_HI - 6900))
+    return np.where(v, 6900 + np.rint(x).astype(np.int64), ALIGN_UNVOICED).astype(np.int64)
+
+
+def align_cost_matrix(Gc, Mc, uv_cost=ALIGN_UV_COST, cap=ALIGN_CAP):
+    """c(i, j) int64 [n_t, n_c] of score cents Mc [n_t] and guide cents Gc [n_c] (ALIGN_UNVOICED = unvoiced / rest)."""
+    Gc, Mc = np.asarray(Gc, dtype=np.int64)[None, :], np.asarray(Mc, dtype=np.int64)[:, None]
+    gv, mv = Gc != ALIGN_UNVOICED, Mc != ALIGN_UNVOICED
+    return np.where(gv & mv, np.minimum(np.abs(Gc - Mc), cap), np.where(gv != mv, uv_cost, 0)).astype(np.int64)
+
+
+def align_band_centres(n_t, n_c):
+    """c_i = ((2 i + 1) n_c) // (2 n_t): the guide frame under the centre of score frame i (the frame-centre rule of contour_fit, exact integers)."""
+    i = np.arange(n_t, dtype=np.int64)
+    return ((2 * i + 1) * n_c) // (2 * n_t)
+
+
+def align_path(C, W=None):
+    """The warp of a cost matrix C [n_t, n_c] (n_t, n_c >= 1; integers) within the band |j - c_i| <= W (None: full, W = max(n_t, n_c)):
+    D[0][0] = C[0][0], D[i][j] = C[i][j] + min(D[i-1][j], D[i][j-1], D[i-1][j-1]) over the predecessors inside the band, the FIRST minimum in that
+    order (up, left, diagonal); walk back from (n_t-1, n_c-1) to (0, 0); idx[i] = the smallest j the path visits in row i.
+    -> (idx int64 [n_t], cost) or (None, None) when the end cell cannot be reached from (0, 0) inside the band."""
+    C = np.asarray(C)
+    n_t, n_c = C.shape
+    W = max(n_t, n_c) if W is None else int(W)
+    ci = align_band_centres(n_t, n_c)
+    lo, hi = np.maximum(ci - W, 0).tolist(), np.minimum(ci + W, n_c - 1).tolist()
+    rows = C.tolist()                                   # plain Python integers: the loop below is the definition, kept scalar
+    INF = ALIGN_INF
+    D, step = [], []                                    # per row: the cells lo[i] .. hi[i]
+    for i in range(n_t):
+        l, h, c = lo[i], hi[i], rows[i]
+        Di, Si = [INF] * (h - l + 1), [0] * (h - l + 1)
+        if i > 0:
+            pl, ph, Dp = lo[i - 1], hi[i - 1], D[i - 1]
+        for j in range(l, h + 1):
+            if i == 0 and j == 0:
+                Di[0] = c[0]
+                continue
+            up = Dp[j - pl] if i > 0 and pl <= j <= ph else INF
+            left = Di[j - 1 - l] if j - 1 >= l else INF
+            diag = Dp[j - 1 - pl] if i > 0 and pl <= j - 1 <= ph else INF
+            best, k = up, 0                             # the first minimum: up, left, diagonal
+            if left < best:
+                best, k = left, 1
+            if diag < best:
+                best, k = diag, 2
+            Si[j - l] = k
+            Di[j - l] = INF if best >= INF else best + c[j]
+        D.append(Di)
+        step.append(Si)
+    if lo[0] > 0 or hi[n_t - 1] < n_c - 1 or D[n_t - 1][n_c - 1 - lo[n_t - 1]] >= INF:
+        return None, None
+    idx = np.zeros(n_t, dtype=np.int64)
+    i, j = n_t - 1, n_c - 1
+    while True:
+        idx[i] = j   # j only falls along the walk: the last write of a row is its smallest j
+        if i == 0 and j == 0:
+            break
+        k = step[i][j - lo[i]]
+        i, j = (i - 1, j) if k == 0 else (i, j - 1) if k == 1 else (i - 1, j - 1)
+    return idx, int(D[n_t - 1][n_c - 1 - lo[n_t - 1]])
+
+
+def contour_align(f0_hz, midi, band=None, shift=0.0, uv_cost=ALIGN_UV_COST, cap=ALIGN_CAP):
+    """The definition of the contour alignment (one item): guide f0_hz [n_c] in Hz (0 = unvoiced) warped onto the score's per-frame notes
+    midi [n_t] (MIDI numbers, <= 0 = rest; what ss_gather_expand_i64(note, mel2ph) gives) by dynamic time warping.
+      * cents: guide `align_cents(f0_hz, shift)` (the SHIFTED guide is compared: pitch_shift is how the caller puts the guide into the score's key);
+        score 100 * min(m, 127);
+      * cost c(i, j): both voiced min(|Gc[j] - Mc[i]|, cap); exactly one voiced uv_cost; neither 0;
+      * band: cell (i, j) exists iff |j - c_i| <= W, c_i = ((2 i + 1) n_c) // (2 n_t); band None or <= 0: full, W = max(n_t, n_c);
+      * recurrence, tie order and result: `align_path`; out[i] = fl32(fl32(g[idx[i]]) * fl32(2^(shift / 12))), 0 where g[idx[i]] is unvoiced.
+    An item with n_c > W n_t (more than W guide frames per score frame: the band would be disconnected) is NOT aligned: status 1, out =
+    contour_fit(f0_hz, n_t, shift) (its float64 definition; the kernel runs the arithmetic of ss_contour_fit), idx = -1, cost = 0. Empty items
+    (n_t == 0 or n_c == 0): status 1, zeros.
+    -> (out [n_t] (fp32 when aligned), idx int32 [n_t], cost int, status int)."""
+    g = np.asarray(f0_hz, dtype=np.float32)
+    m = np.asarray(midi, dtype=np.int64)
+    n_c, n_t = len(g), len(m)
+    W = max(n_t, n_c) if band is None or int(band) <= 0 else int(band)
+    if n_t == 0 or n_c == 0:
+        return np.zeros(n_t, dtype=np.float32), np.full(n_t, -1, dtype=np.int32), 0, 1
+    if n_c > W * n_t:
+        return contour_fit(g, n_t, shift), np.full(n_t, -1, dtype=np.int32), 0, 1
+    Mc = np.where(m > 0, 100 * np.minimum(m, 127), ALIGN_UNVOICED)
+    idx, cost = align_path(align_cost_matrix(align_cents(g, shift), Mc, uv_cost, cap), W)
+    assert idx is not None, "a band with n_c <= W n_t is connected"
+    src = g[idx]
+    scale = np.float32(2.0 ** (float(shift) / 12.0))
+    out = np.where(src > 0, src * scale, np.float32(0)).astype(np.float32)
+    return out, idx.astype(np.int32), cost, 0
+
+
+@torch.no_grad()
+def contour_align_device(f0_hz, lens_c, midi, lens_t, T, band=None, shift=0.0):
+    """f0_hz fp32 [B, Lc] on the device (Hz, 0 = unvoiced), lens_c [B] valid guide frames (host ints or a device tensor; None = Lc), midi int64 [B, >= T]
+    on the device (the score's note per frame, 0 = rest), lens_t int32 [B] ON THE DEVICE (score frames per item: no host sync), band = half-width in
+    guide frames (None or <= 0: full) -> (out [B, T] fp32, idx [B, T] int32, cost [B] int32, status [B] int32): `contour_align` of every item
+    (`ss_contour_align`), frames >= lens_t[b] are out = 0, idx = -1. status 1 = not aligned (the linear fit instead): see `contour_align`.
+    The direction workspace is allocated here from the library's query; sizes beyond ALIGN_MAX_T / ALIGN_MAX_LC and a workspace above
+    ALIGN_MAX_WORKSPACE_BYTES are refused."""
+    if not torch.is_tensor(f0_hz) or f0_hz.device.type != "cuda" or not torch.is_tensor(midi) or midi.device.type != "cuda":
+        raise L.StyleSingerHipError("contour_align_device needs device tensors: there is no CPU path")
+    x = f0_hz if f0_hz.dtype == torch.float32 and f0_hz.stride(1) == 1 and f0_hz.stride(0) >= f0_hz.shape[1] else f0_hz.float().contiguous()
+    B, Lc = x.shape
+    T = int(T)
+    dev = x.device
+    if T > ALIGN_MAX_T or Lc > ALIGN_MAX_LC:
+        raise ValueError(f"contour_align_device: {T} score frames / {Lc} guide frames exceed the kernel's caps ({ALIGN_MAX_T} / {ALIGN_MAX_LC}); "
+                         "cut the score into segments (sing_score) or use the linear fit")
+    md = midi if midi.dtype == torch.int64 and midi.dim() == 2 and midi.stride(1) == 1 and midi.stride(0) >= midi.shape[1] else midi.long().contiguous()
+    if md.dim() != 2 or md.shape[0] != B or md.shape[1] < T:
+        raise ValueError(f"contour_align_device: midi {tuple(md.shape)} for {B} contours and {T} frames")
+    lc = torch.full((B,), Lc, dtype=torch.int32) if lens_c is None else torch.as_tensor(lens_c)
+    lc = lc.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    lt = lens_t.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if lc.numel() != B or lt.numel() != B:
+        raise ValueError(f"contour_align_device: {lc.numel()} source lengths and {lt.numel()} target lengths for {B} contours")
+    band = 0 if band is None or int(band) <= 0 else int(band)
+    lib = L.load()
+    ws_bytes = int(lib.ss_contour_align_workspace_bytes(B, T, Lc, band))
+    if ws_bytes <= 0:
+        raise L.StyleSingerHipError(f"ss_contour_align_workspace_bytes refused B={B} T={T} Lc={Lc} band={band}")
+    if ws_bytes > ALIGN_MAX_WORKSPACE_BYTES:
+        raise ValueError(f"contour_align_device: {ws_bytes} bytes of direction workspace for B={B} T={T} Lc={Lc} band={band or 'full'} exceed "
+                         f"ALIGN_MAX_WORKSPACE_BYTES = {ALIGN_MAX_WORKSPACE_BYTES}; narrow the band or split the batch")
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    out = torch.empty(B, T, device=dev, dtype=torch.float32)
+    idx = torch.empty(B, T, device=dev, dtype=torch.int32)
+    cost = torch.empty(B, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    L.check(lib.ss_contour_align(L.ptr(x), x.stride(0), Lc, L.ptr(lc), L.ptr(md), md.stride(0), L.ptr(lt), band, ALIGN_UV_COST, ALIGN_CAP, float(shift),
+                                 L.ptr(out), out.stride(0), L.ptr(idx), L.ptr(cost), L.ptr(status), T, B, L.ptr(ws), ws_bytes, L.stream_ptr()),
+            "ss_contour_align")
+    return out, idx, cost, status

@@ -23,6 +23,28 @@ def row(x, dtype):
     return torch.as_tensor(np.asarray(x), dtype=dtype)[None]
 
 
+ALIGN_BAND_S = 2.0   # default half-width of the pitch_align band, seconds around the linear fit
+
+
+def align_inputs(inp, has_contour, sr, hop):
+    """The alignment keys of `inp` (host only, no device): inp['pitch_align'] (None | "dtw") and inp['pitch_align_band_s'] (seconds >= 0; default
+    ALIGN_BAND_S; 0 = the full matrix) -> {} or {pitch_align: "dtw", pitch_align_band: round(s * sr / hop) guide frames (0 = full)}. Refused: another
+    mode, a band without pitch_align, either without a contour (`has_contour`: inp gave pitch_hz or pitch_audio)."""
+    mode, band_s = inp.get("pitch_align"), inp.get("pitch_align_band_s")
+    if mode is None:
+        if band_s is not None:
+            raise ValueError("preprocess_input: inp['pitch_align_band_s'] is the band of inp['pitch_align'] = 'dtw'; it needs pitch_align")
+        return {}
+    if mode != "dtw":
+        raise ValueError(f"preprocess_input: inp['pitch_align'] = {mode!r}: None (the linear fit) or 'dtw'")
+    if not has_contour:
+        raise ValueError("preprocess_input: inp['pitch_align'] warps inp['pitch_hz'] / inp['pitch_audio'] onto the score; it needs one of them")
+    band_s = ALIGN_BAND_S if band_s is None else float(band_s)
+    if not band_s >= 0:
+        raise ValueError(f"preprocess_input: inp['pitch_align_band_s'] = {band_s}: seconds >= 0 (0 = the full matrix)")
+    return dict(pitch_align="dtw", pitch_align_band=int(round(band_s * sr / hop)))
+
+
 class ReferenceProducers:
     """Mixin of StyleSingerInfer: the feature producers of `preprocess_input` on the device, batched and single-item."""
 
@@ -267,7 +289,9 @@ class ReferenceProducers:
     def _pitch_inputs(self, inp):
         """The pitch-control entries of `inp` as `infer_batch` takes them: inp['pitch_hz'] (a 1-D contour in Hz at the mel hop, 0 = unvoiced) or
         inp['pitch_audio'] (a WAV path or a (waveform, sample_rate) pair: a guide vocal, resampled like `ref_audio` and tracked on the device as
-        `preprocess_batch` tracks the reference audio, 80-800 Hz), and inp['pitch_shift'] (semitones). -> {} when `inp` has none of them."""
+        `preprocess_batch` tracks the reference audio, 80-800 Hz), and inp['pitch_shift'] (semitones). inp['pitch_align'] = "dtw" (+
+        inp['pitch_align_band_s'], seconds, default ALIGN_BAND_S, 0 = full) asks for the warp of forward(pitch_align=): -> `pitch_align` and
+        `pitch_align_band` = round(s * audio_sample_rate / hop_size) guide frames. -> {} when `inp` has none of them."""
         if inp.get("pitch_hz") is not None and inp.get("pitch_audio") is not None:
             raise ValueError("preprocess_input: give inp['pitch_hz'] or inp['pitch_audio'], not both")
         out = {}
@@ -289,6 +313,7 @@ class ReferenceProducers:
             if "pitch_hz" not in out:
                 raise ValueError("preprocess_input: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
             out["pitch_shift"] = float(inp["pitch_shift"])
+        out.update(align_inputs(inp, "pitch_hz" in out, int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])))
         return out
 
     @torch.no_grad()
