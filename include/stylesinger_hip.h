@@ -711,6 +711,30 @@ int ss_f0diff_sample(const ss_wavenet* net, float* f0, int32_t* uv, const float*
                      const int32_t* lens, int B, int T, const float* noise, const float* gumbel_u, uint64_t seed,
                      const uint64_t* seed_dev, int step_lo, int step_hi, int precompute_cond, void* ws, int64_t ws_bytes,
                      void* stream);
+/* The same joint loop over a CHOSEN list of network times (a released checkpoint's f0 schedule and step-embedding table are fixed; this trades
+ * f0 steps for time as ss_meldiff_sample_ddim does for the mel): ts[0] > ts[1] > ... (HOST array) inside [0, net->steps); the transition leaves
+ * t = ts[i] for s = ts[i+1], the last one for x_0 ("final": cumprod alpha = 1). betas = HOST table [net->steps] in DOUBLE precision (the
+ * checkpoint's f0_gen.betas widened); with a = 1 - betas, ac = cumprod(a), Lambda = cumsum(log a):
+ *   Gaussian half: the DDIM family, sigma = eta sqrt((1-ac_s)/(1-ac_t)) sqrt(1 - ac_t/ac_s), c2 = sqrt(max(1-ac_s-sigma^2, 0)/(1-ac_t)),
+ *     c1 = sqrt(ac_s) - c2 sqrt(ac_t); x' = c1 clamp(x0, lo, hi) + c2 x + sigma z (the per-frame dyn_clip clamp kept).
+ *   multinomial half: the exact posterior q(x_s | x_t, x0) ~ q(x_t | x_s) q(x_s | x0) of the uniform-transition chain over the gap: the
+ *     one-step posterior with alpha_{t|s} = ac_t/ac_s in place of alpha_t and ac_s in place of ac_{t-1} (logs: Lambda_t - Lambda_s, Lambda_s;
+ *     log(1 - exp(.) + 1e-40) as multinomial_schedule); the final transition takes no prior term, as the reference's t = 0 row.
+ *   ts = steps-1 ... 0 with eta = 1 IS the reference's step (the coefficients agree with the checkpoint's tables to fp32 rounding), which pins
+ *     this entry to ss_f0diff_sample and its goldens. eta in [0, 1]; eta = 0: the Gaussian tape is never read.
+ *   noise / gumbel_u: the tapes of ss_f0diff_sample ([steps]... , row = NETWORK TIME t) or NULL -> Philox at counter t: with ts = steps-1 ... 0
+ *     and eta = 1 the draws are ss_f0diff_sample's.
+ *   [i_lo, i_hi): the list positions this call runs (whole list: 0, n_ts) - the loop-cut contract of step_lo / step_hi: the first position's
+ *     input row comes from the state, every later one from the previous transition's launch; evaluation i uses step-embedding row ts[i].
+ * Refused before any launch (SS_ERR_ARG, ss_last_error): a null pointer, n_ts < 1, a list that is not strictly decreasing or leaves
+ * [0, steps), a bad [i_lo, i_hi), eta outside [0, 1], a beta that is not finite or not inside (0, 1). */
+int ss_f0diff_sample_strided(const ss_wavenet* net, float* f0, int32_t* uv, const float* cond, const float* lo, const float* hi,
+                             const int32_t* lens, int B, int T, const int32_t* ts, int n_ts, int i_lo, int i_hi,
+                             const double* betas /* HOST [net->steps] */, float eta, const float* noise, const float* gumbel_u,
+                             uint64_t seed, const uint64_t* seed_dev, int precompute_cond, void* ws, int64_t ws_bytes, void* stream);
+/* Host only (no device call): the nine coefficients of ONE transition t -> s of ss_f0diff_sample_strided (s = -1: final), computed in double
+ * and rounded to fp32, in the order recip, recipm1, c1, c2, sigma, log_alpha_t, log_1m_alpha_t, log_cp_tm1, log_1m_cp_tm1. betas: [steps]. */
+int ss_f0_strided_coef(const double* betas, int steps, int t, int s, float eta, float* out9);
 
 /* f0 post-processing of the two predictors (stylesinger.py:216-311, utils/pitch_utils.py:22-31,65-78):
  * midi -> clamp bounds ; merge ; denorm ; coarse. */

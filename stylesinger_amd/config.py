@@ -60,6 +60,9 @@ DEFAULT_HPARAMS = dict(
     # vocoder output denoise (egs/egs_bases/tts/base.yaml:107; hifigan_nsf.py:73-74): > 0 = spectral subtraction of this magnitude after the generator
     # (denoise.py), with the geometry keys fft_size / win_size / hop_size of the caller's hparams
     vocoder_denoise_c=0.0,
+    # not reference keys: sample the two f0 / uv diffusions at this many of their f0_timesteps network times (forward(f0_steps=); None = the
+    # reference's full ancestral loop) with this eta (0 = deterministic Gaussian half ... 1 = ancestral)
+    f0_sample_steps=None, f0_sample_eta=1.0,
 )
 
 # The released HiFi-GAN config ships only inside the un-vendored checkpoint

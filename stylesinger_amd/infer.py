@@ -361,6 +361,9 @@ def main(argv=None):
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
     ap.add_argument("--vocoder-denoise-c", type=float, help="spectral subtraction of this magnitude on the vocoder's output "
                     "(hparams['vocoder_denoise_c'], e.g. 0.1; 0 = off)")
+    ap.add_argument("--f0-steps", type=int, help="sample the two f0 / uv diffusions at this many of their f0_timesteps network times "
+                    "(hparams['f0_sample_steps']; default: every one, the reference's loop)")
+    ap.add_argument("--f0-eta", type=float, help="--f0-steps: 0 = deterministic Gaussian half ... 1 = ancestral (hparams['f0_sample_eta'], default 1)")
     ap.add_argument("--score", help="a score of any length as JSON (the keys of example_input.json, optionally ph_dur = seconds per phone): split at "
                     "its rests, rendered in batches, stitched on the device")
     ap.add_argument("--max-seconds", type=float, default=12.0, help="--score: longest merged segment")
@@ -416,6 +419,16 @@ def main(argv=None):
         hp["out_loudness_lufs"] = a.out_lufs
     if a.vocoder_denoise_c is not None:
         hp["vocoder_denoise_c"] = a.vocoder_denoise_c
+    if a.f0_steps is not None:
+        if a.f0_steps < 1:
+            ap.error("--f0-steps: at least 1")
+        hp["f0_sample_steps"] = a.f0_steps
+    if a.f0_eta is not None:
+        if a.f0_steps is None:
+            ap.error("--f0-eta belongs to --f0-steps")
+        if not 0.0 <= a.f0_eta <= 1.0:
+            ap.error("--f0-eta: inside [0, 1]")
+        hp["f0_sample_eta"] = a.f0_eta
     ctor = dict(exp_dir=a.exp_dir, vocoder_dir=a.vocoder_dir, emotion_state=emo.get("model_state", emo),
                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
     if score is not None:

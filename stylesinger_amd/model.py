@@ -294,6 +294,10 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         parity tests; default = on-device Philox), `seed` (Philox seed), `sampler="ddim", ddim_steps=n, eta=0.0` (strided
         DDIM mel sampler, BASELINE config 5; eta = 0 deterministic, eta = 1 with ddim_steps = K_step IS the reference's ancestral
         sampler; default = the reference's 100-step ancestral sampler),
+        `f0_steps=n, f0_eta=1.0` (strided sampler of the two f0 / uv diffusions: n of the f0_timesteps network times, `ss_f0diff_sample_strided`;
+        f0_eta = 0 deterministic Gaussian half ... 1 ancestral, n = f0_timesteps with f0_eta = 1 IS the reference's loop to fp32 rounding of the
+        coefficients; defaults hparams['f0_sample_steps'] = None - the reference's full loop, unchanged - and hparams['f0_sample_eta'];
+        ValueError together with a given contour),
         `sampler="plms", plms_interval=n` (the reference's PLMS sampler, hparams['pndm_speedup'],
         shallow_diffusion_tts.py:165-197), `plan_slot` (workspace/graph set to use: give concurrent forwards on different streams
         different slots), `style_cache` (the dict encode_style() returned for these references: skips
@@ -340,11 +344,13 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             raise ValueError("forward: pitch_align_band is the band of pitch_align='dtw'; it needs pitch_align")
         if pitch_align_band is not None and int(pitch_align_band) < 0:
             raise ValueError(f"forward: pitch_align_band={pitch_align_band}: guide frames >= 0 (0 or None = the full matrix)")
+        f0_ts, f0_eta = self._f0_sampler_args(kwargs, f0 is not None or pitch_hz is not None)
         self._ensure_packed()
         # c: the per-call state the stages share (shapes, lengths, intermediate activations, the plan) and the result dict
         c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, noise=kwargs.get("noise"), seed=int(kwargs.get("seed", self.hp["seed"])),
                                   kwargs=kwargs)
         c.f32 = dict(device=c.dev, dtype=torch.float32)
+        c.f0_ts, c.f0_eta = f0_ts, f0_eta
         self._encode_text(c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed)
         self._regulate_length(c, mel2ph, f0, uv)
         self._align_style(c, ref_mels, ref_f0)
@@ -359,6 +365,25 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
                 else:
                     c.ret["mel_out"] = c.coarse_mel
         return self._crop_frames(c.ret, c.T, c.T_out)
+
+    def _f0_sampler_args(self, kwargs, contour_given):
+        """(network times or None, eta) of the f0 pair loop: forward(f0_steps=, f0_eta=), else hparams['f0_sample_steps'] / ['f0_sample_eta'];
+        None = the reference's full ancestral loop (ss_f0diff_sample). Raises ValueError on a bad value; touches no device."""
+        steps, eta = kwargs.get("f0_steps"), kwargs.get("f0_eta")
+        if steps is not None and contour_given:
+            raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with a given contour (f0 / uv or pitch_hz) they do not run")
+        if contour_given:   # the hparams defaults are simply unused
+            return None, 1.0
+        if steps is None:
+            steps = self.hp.get("f0_sample_steps")
+        if eta is None:
+            eta = self.hp.get("f0_sample_eta", 1.0)
+        if steps is not None and int(steps) < 1:
+            raise ValueError(f"forward: f0_steps={steps}: at least 1 (more than f0_timesteps = {self.hp['f0_timesteps']} means all of them)")
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"forward: f0_eta={eta}: 0 (deterministic Gaussian half) ... 1 (ancestral)")
+        return (None if steps is None else self.f0_strided_timesteps(int(steps))), eta
 
     def _encode_text(self, c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed):
         """Phoneme encoder (a1) + note encoder (a2) + speaker / emotion projections -> c.enc [B,Tp,H], c.spk, c.emo [B,H]."""
@@ -530,9 +555,11 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         pl.cond_a.copy_(c.dec)  # = decoder_inp * tgt_nonpadding (the gather already wrote 0 on padding)
         L.check(lib.ss_add_bcast_mask(L.ptr(c.dec), L.ptr(c.spk), None, L.ptr(c.emo), L.ptr(c.style), L.ptr(pl.cond_b), B, T, H, L.ptr(lens_t), st()), "cond_b")
 
+        ts, eta = c.f0_ts, c.f0_eta   # None: the reference's full loop; else the strided sampler (its tapes: the same [S]... layout, row = network time)
+
         def run(noise=None):
             if noise is None:
-                return self._run_f0_pair(pl)
+                return self._run_f0_pair(pl, ts=ts, eta=eta)
             S = self._pk["f0_pair"]["net"].steps
             tape_t = lambda x: _pad_frames(x.to(dev).float(), T)  # recorded noise [..., T_out] (reference layout) -> device fp32, bucket-padded
             na, nb_ = noise["f0_a"], noise["f0_b"]
@@ -540,9 +567,10 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             pl.f0[1].copy_(tape_t(nb_["z0"]).reshape(B, T))
             zs = torch.cat([tape_t(na["z_steps"]).reshape(S, B, T), tape_t(nb_["z_steps"]).reshape(S, B, T)], 1).contiguous()
             us = torch.cat([tape_t(na["u_steps"]).reshape(S, B, 2, T), tape_t(nb_["u_steps"]).reshape(S, B, 2, T)], 1).contiguous()
-            self._run_f0_pair(pl, (zs, us))
-        # uv2 is reset outside the graph: before the capture (its warm-up and recording passes accumulate into it) and before every run
-        self._run_loop(pl, "f0", run, tape=c.noise, graphs=c.graphs, prepare=pl.uv2.zero_)
+            self._run_f0_pair(pl, (zs, us), ts=ts, eta=eta)
+        # uv2 is reset outside the graph: before the capture (its warm-up and recording passes accumulate into it) and before every run.
+        # One captured graph per sampler: "f0" = the default loop, ("f0", number of steps, eta) = a strided one
+        self._run_loop(pl, "f0" if ts is None else ("f0", len(ts), eta), run, tape=c.noise, graphs=c.graphs, prepare=pl.uv2.zero_)
         f0_a, uv_a, f0_b, uv_b = pl.f0[0].clone(), pl.uv[0].clone(), pl.f0[1].clone(), pl.uv[1].clone()
         ret["gdiff1"] = ret["mdiff1"] = ret["gdiff2"] = ret["mdiff2"] = 0.0
         pitch_pred, f0_denorm, coarse = out

@@ -39,6 +39,51 @@ def _step_emb_table(steps, dim):
     return torch.cat((e.sin(), e.cos()), dim=-1).contiguous()
 
 
+F0_COEF_NAMES = ("recip", "recipm1", "c1", "c2", "sigma", "log_alpha_t", "log_1m_alpha_t", "log_cp_tm1", "log_1m_cp_tm1")   # F0StepCoef
+F0_STRIDED_RTOL = 1e-6
+
+
+def f0_strided_coef(betas64, t, s, eta):
+    """The nine fp32 coefficients of the transition t -> s (s = -1: final) of the strided f0 / uv sampler (`ss_f0_strided_coef`: host only)."""
+    betas64 = np.ascontiguousarray(betas64, dtype=np.float64)
+    out = np.empty(9, np.float32)
+    L.check(L.load().ss_f0_strided_coef(L.hptr(betas64), len(betas64), int(t), int(s), float(eta), L.hptr(out)), "ss_f0_strided_coef")
+    return out
+
+
+def f0_table_coef(tables, t):
+    """What `ss_f0diff_sample` reads from the checkpoint's fp32 tables at network time t, under the same nine names. The two prior entries are
+    not read at t = 0 (None)."""
+    g = lambda k: float(np.asarray(tables[k], np.float32)[t])
+    p = lambda k: float(np.asarray(tables[k], np.float32)[t - 1]) if t > 0 else None
+    sigma = float(np.exp(np.float32(0.5) * np.float32(g("posterior_log_variance_clipped")))) if t > 0 else 0.0
+    return (g("sqrt_recip_alphas_cumprod"), g("sqrt_recipm1_alphas_cumprod"), g("posterior_mean_coef1"), g("posterior_mean_coef2"), sigma,
+            g("log_alpha"), g("log_1_min_alpha"), p("log_cumprod_alpha"), p("log_1_min_cumprod_alpha"))
+
+
+def f0_strided_guard(tables):
+    """Do the checkpoint's f0 schedule tables belong to its betas? The stride-1, eta = 1 coefficients of every network time, computed from
+    `betas` widened to float64, against the fp32 tables `ss_f0diff_sample` reads - all nine names, the four multinomial tables included.
+    `tables`: reference buffer name -> 1-D array. Returns (betas float64, worst relative deviation, (name, t) of the worst, error text or None):
+    a deviation above F0_STRIDED_RTOL means the strided sampler would not continue the sampler the checkpoint was trained with."""
+    betas = np.ascontiguousarray(np.asarray(tables["betas"], np.float32).astype(np.float64))
+    worst, where = 0.0, None
+    for t in range(len(betas)):
+        mine, ref = f0_strided_coef(betas, t, t - 1, 1.0), f0_table_coef(tables, t)
+        for name, a, b in zip(F0_COEF_NAMES, mine, ref):
+            if b is None:
+                continue
+            dev = abs(float(a) - b) / abs(b) if b != 0.0 else (0.0 if float(a) == 0.0 else float("inf"))
+            if not dev <= worst:   # also a NaN
+                worst, where = dev, (name, t)
+    err = None
+    if not worst <= F0_STRIDED_RTOL:
+        err = (f"the f0 schedule tables of this checkpoint do not belong to its f0_gen.betas: {where[0]} at network time {where[1]} deviates by "
+               f"{worst:.3g} (relative; limit {F0_STRIDED_RTOL:g}) from the value the betas give - strided f0 sampling (f0_steps) is refused for "
+               f"this checkpoint; the default sampler reads the tables as they are and is unaffected")
+    return betas, worst, where, err
+
+
 class Packing:
     """Mixin of StyleSingerHIP: builds `self._pk` from the registered weights (uses `self.p`, `self.hp` and the precision-mode flags)."""
     # "fp16x2": the weights' power-of-two shift. |w| 2^8 < 65504 for |w| < 255; lo = RNE16(w 2^8 - hi) stays a NORMAL fp16 number for every
@@ -291,6 +336,14 @@ class Packing:
             net.log_alpha, net.log_1m_alpha = host("log_alpha"), host("log_1_min_alpha")
             net.log_cumprod_alpha, net.log_1m_cumprod_alpha = host("log_cumprod_alpha"), host("log_1_min_cumprod_alpha")
         sched = {k: self.p(f"{gen}.{k}").detach().cpu() for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")}
+        if f0:   # the strided sampler builds its coefficients from the betas in float64 (ss_f0diff_sample_strided); refused where the tables disagree
+            names = ("betas", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
+                     "posterior_log_variance_clipped", "log_alpha", "log_1_min_alpha", "log_cumprod_alpha", "log_1_min_cumprod_alpha")
+            try:
+                sched["betas_f64"], sched["strided_dev"], _, sched["strided_error"] = f0_strided_guard(
+                    {k: self.p(f"{gen}.{k}").detach().cpu().numpy() for k in names})
+            except L.StyleSingerHipError as e:   # a beta outside (0, 1)
+                sched["betas_f64"], sched["strided_dev"], sched["strided_error"] = None, float("inf"), f"strided f0 sampling is refused: {e}"
         if not f0:
             sched["alphas_cumprod_np"] = np.ascontiguousarray(self.p(f"{gen}.alphas_cumprod").detach().cpu().numpy().astype(np.float32))
             # DDIM coefficients need 1 - alphas_cumprod at small t: rebuilt in float64 from the betas buffer as the reference builds its

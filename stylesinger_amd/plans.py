@@ -56,7 +56,7 @@ class _DiffPlan:
             wsb = lib.ss_wavenet_workspace_bytes(struct_addr(pk["mel"]["net"]), nb, T)
             self.ws_mel.append((wsb, torch.empty(wsb, device=dev, dtype=torch.uint8)))
         self.ws_prodiff = None   # full-batch workspace of the ProDiff decoder when ws_mel is split (allocated on first use, plan-owned)
-        self.graphs = {}         # captured loops: "f0" (the f0 pair), "mel" (DDPM or ProDiff), ("ddim", n_steps, eta)
+        self.graphs = {}         # captured loops: "f0" (the f0 pair), ("f0", n_steps, eta) (its strided sampler), "mel" (DDPM or ProDiff), ("ddim", n_steps, eta)
         self.plms_hist = None
         self.uses = 0   # forwards that asked for this shape (auto mode captures on the second one)
         self.recount()
@@ -102,6 +102,12 @@ def _capture(fn):
     with torch.cuda.graph(g):
         fn()
     return g
+
+
+def strided_timesteps(S, n):
+    """n network times of a schedule of S, strictly decreasing from S-1 to 0 at a uniform stride; n is clipped to [1, S] (n = S: all of them,
+    n = 1: time 0 alone - linspace's first point)."""
+    return sorted({int(round(v)) for v in np.linspace(0, S - 1, max(1, min(int(n), S)))}, reverse=True)
 
 
 class Plans:
@@ -212,25 +218,41 @@ class Plans:
     # Philox keys: the host part of every key is a CONSTANT per call site and all per-call variation comes from the device
     # word pl.seed, so that a captured graph (host arguments frozen at capture) and the eager launches draw the same noise
     # for the same `seed`, whatever was run before.
-    def _run_f0_pair(self, pl, tape=None):
-        """Both joint f0/uv samplers in ONE grouped loop (they are independent given their conditions)."""
+    def _run_f0_pair(self, pl, tape=None, ts=None, eta=1.0):
+        """Both joint f0/uv samplers in ONE grouped loop (they are independent given their conditions). `ts` (network times, strictly
+        decreasing) switches to the strided sampler `ss_f0diff_sample_strided` with `eta` = 0 deterministic Gaussian half ... 1 ancestral;
+        tapes keep the reference's [S]... layout and are indexed by network time."""
         lib, pk = _lib(), self._pk
         B, T = pl.B, pl.T
         sdp = L.ptr(pl.seed)
         net = pk["f0_pair"]["net"]
+        sched = pk["f0_pair"]["sched"]
+        if ts is not None and sched["strided_error"] is not None:   # the checkpoint's tables do not belong to its betas (packing.f0_strided_guard)
+            raise L.StyleSingerHipError(sched["strided_error"])
         zs = us = None
         if tape is not None:
             zs, us = tape  # [S][2B][T], [S][2B][2][T]
         else:
             L.check(lib.ss_fill_normal_rows(L.ptr(pl.f02), 2 * B, T, T, 11, sdp, L.stream_ptr()), "z0")
+        if ts is not None:
+            ts = np.ascontiguousarray(np.asarray(ts, dtype=np.int32))
+            L.check(lib.ss_f0diff_sample_strided(struct_addr(net), L.ptr(pl.f02), L.ptr(pl.uv2), L.ptr(pl.cond2), L.ptr(pl.lo2), L.ptr(pl.hi2),
+                                                 L.ptr(pl.lens2), 2 * B, T, L.hptr(ts), len(ts), 0, len(ts), L.hptr(sched["betas_f64"]), float(eta),
+                                                 L.ptr(zs), L.ptr(us), 17, sdp, 1, L.ptr(pl.ws_f0), pl.ws_f0_bytes, L.stream_ptr()), "f0 pair strided")
+            return
         L.check(lib.ss_f0diff_sample(struct_addr(net), L.ptr(pl.f02), L.ptr(pl.uv2), L.ptr(pl.cond2), L.ptr(pl.lo2), L.ptr(pl.hi2),
                                      L.ptr(pl.lens2), 2 * B, T, L.ptr(zs), L.ptr(us), 17, sdp, 0, net.steps, 1,
                                      L.ptr(pl.ws_f0), pl.ws_f0_bytes, L.stream_ptr()), "f0 pair")
 
     def ddim_timesteps(self, n):
         """n network times, strictly decreasing from K-1 to 0 (uniform stride)."""
-        K = self.hp["K_step"]
-        return sorted({int(round(v)) for v in np.linspace(0, K - 1, max(1, min(n, K)))}, reverse=True)
+        return strided_timesteps(self.hp["K_step"], n)
+
+    def f0_strided_timesteps(self, n):
+        """The same rule over the f0 pair's schedule: n of its f0_timesteps network times, S-1 ... 0 (n = S: every time). One point cannot be
+        both ends: n = 1 is time S-1 alone (the state IS x_{S-1}: one evaluation there and the jump to x_0), where the rule's single point is 0."""
+        S = self.hp["f0_timesteps"]
+        return [S - 1] if int(n) <= 1 else strided_timesteps(S, n)
 
     def _run_mel(self, pl, tape=None, ddim_ts=None, plms_interval=None, eta=0.0):
         """q_sample + the shallow reverse loop (batch halves on two streams); `ddim_ts` switches to the strided
