@@ -249,7 +249,10 @@ int ss_wino43_weight_transform(const float* src, float* dst, int Cout, int Cin, 
  * bf16-operand GEMM/conv for the denoisers' hidden layers (BASELINE config 4): A and W are bf16 IN HBM (rounded once where
  * they are produced: weights by ss_to_bf16 at pack time = the "bf16 weight copies", activations by the producing epilogue),
  * fp32 accumulate on v_mfma_f32_32x32x16_bf16, K chunks of 64. Same tap / zero-padding / grouped-launch semantics as
- * ss_conv_gemm. Arithmetic contract: RNE rounding of both matmul operands, everything else fp32 (net.py:58-130 otherwise).
+ * ss_conv_gemm. Zero padding is the kernels' own: a tap that lands outside [0, lens[b]) of its item (T without lens) reads 0 WHATEVER A holds
+ * there - rows [lens[b], T) of A and the neighbouring items' rows are never fetched, with mask_rows = 0 too - so a producer need not zero
+ * its tail (every kernel of the family, every tile edge: tests/test_gpu_hgemm_edges.py runs each launch on zeroed and on poisoned tails).
+ * Arithmetic contract: RNE rounding of both matmul operands, everything else fp32 (net.py:58-130 otherwise).
  * ------------------------------------------------------------------------------------------ */
 enum {
   SS_HEPI_STORE = 0, /* C fp32 = act(acc + bias), rows >= lens[b] written as 0 when mask_rows                               */
@@ -332,7 +335,8 @@ int ss_gemm_bf16(const ss_gemm_bf16_args* args, void* stream);
 /* The SS_HEPI_GATE form of ss_gemm_bf16 for many-round launches (BASELINE config 4): three taps (-d, 0, d) with d <= 8, K = 256,
  * Np a multiple of 256. 256 rows x 256 packed columns per workgroup, 8 waves, both operands by LDS-DMA, the A tile staged once per
  * channel chunk with its dilation halo. ss_gemm_bf16 dispatches here when ss_gemm_bf16_gate256_ok(args) (and the "gate256" tuning knob)
- * say so; same arithmetic contract, results equal up to the K summation order. */
+ * say so; same arithmetic contract, results equal up to the K summation order - and for split = 2 in the SAME order as the generic kernel:
+ * bit-identical outputs, so a launch does not depend on the kernel picked for its size (tests/test_gpu_hgemm_edges.py). */
 int ss_gemm_bf16_gate256(const ss_gemm_bf16_args* args, void* stream);
 int ss_gemm_bf16_gate256_ok(const ss_gemm_bf16_args* args);
 /* The same launch for split = 2 ("fp16x2") operands on 256 x 128 tiles with TWO workgroups per CU (4 waves, 80 KB of LDS each: the A image is

@@ -92,22 +92,40 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
   [[maybe_unused]] const int a_lo_dead = (W2 && st_slot >= 4) ? (int)0x80000000 : 0;   // SPLIT = 2: the A operand's second plane is never read - not fetched either (zeros)
 
   // chunk c = (tap, k0): SGPR byte offsets of the A fetch (tap row shift + channel offset) and of the W fetch
+  // SPLIT = 2 walks the chunks channel-chunk-major (c = cc * ntaps + tap) and runs the products of a chunk as H0, L0, L1, H1 (compute below): the order
+  // in which gate256_kernel<8, 2> / gate128_kernel feed every accumulator, so that a launch computes the same bits whichever kernel the dispatcher
+  // picks for its size (tests/test_gpu_hgemm_edges.py). The bf16 forms keep their tap-major order.
+  auto chunk_tap = [&](int c, int& tap, int& cc) {
+    if constexpr (W2) {
+      cc = c / a.ntaps;
+      tap = c - cc * a.ntaps;
+    } else {
+      tap = c / nchunks_tap;
+      cc = c - tap * nchunks_tap;
+    }
+  };
   auto a_soff = [&](int c) {
-    const int tap = c / nchunks_tap, cc = c - tap * nchunks_tap;
+    int tap, cc;
+    chunk_tap(c, tap, cc);
     return a.tap_off[tap] * lda2 + cc * (BKH * 2);
+  };
+  auto w_soff = [&](int c) {
+    int tap, cc;
+    chunk_tap(c, tap, cc);
+    return (tap * nchunks_tap + cc) * (BKH * 2);
   };
   u32x4 ra[2][AP], rb[2][BP];  // two register stages
   auto fetch = [&](auto st_tag, int c, int dead) {
     constexpr int ST = decltype(st_tag)::value;
     // a negative tap shift must stay in the VGPR offset (the range check has to see the row): one v_add per load, only for taps
-    const int so = a_soff(c);
+    const int so = a_soff(c), wso = w_soff(c);
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
       if constexpr (W2) ra[ST][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (a_voff[i] + so) | dead | a_lo_dead, 0, 0);
       else ra[ST][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (a_voff[i] + so) | dead, 0, 0);
     }
 #pragma unroll
-    for (int i = 0; i < BP; ++i) rb[ST][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[i] | dead, c * (BKH * 2), 0);
+    for (int i = 0; i < BP; ++i) rb[ST][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff[i] | dead, wso, 0);
   };
   auto stage = [&](auto st_tag, auto buf_tag) {
     constexpr int ST = decltype(st_tag)::value;
@@ -156,14 +174,22 @@ __global__ __launch_bounds__(256, (BM >= 128 ? 2 : 3)) void gemm_bf16_kernel(con
 #pragma unroll
             for (int n = 0; n < TN; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[m], bh[n], acc[m][n], 0, 0, 0);
         }
+        if (W2 && ks == 0) {   // fp16x2, first k-step: hi x hi before hi x lo (the order of the many-round kernels, see chunk_tap)
+#pragma unroll
+          for (int m = 0; m < TM; ++m)
+#pragma unroll
+            for (int n = 0; n < TN; ++n) acc[m][n] = ss_mfma_32x32x16<W2>(ah[m], bh[n], acc[m][n]);
+        }
 #pragma unroll
         for (int m = 0; m < TM; ++m)
 #pragma unroll
           for (int n = 0; n < TN; ++n) acc[m][n] = ss_mfma_32x32x16<W2>(ah[m], bm[n], acc[m][n]);
+        if (!(W2 && ks == 0)) {
 #pragma unroll
-        for (int m = 0; m < TM; ++m)
+          for (int m = 0; m < TM; ++m)
 #pragma unroll
-          for (int n = 0; n < TN; ++n) acc[m][n] = ss_mfma_32x32x16<W2>(ah[m], bh[n], acc[m][n]);
+            for (int n = 0; n < TN; ++n) acc[m][n] = ss_mfma_32x32x16<W2>(ah[m], bh[n], acc[m][n]);
+        }
       }
     } else {
 #pragma unroll

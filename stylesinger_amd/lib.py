@@ -484,7 +484,8 @@ def split_planes(y):
 
 def gemm_bf16(A, Wh, *, B, T, K, taps, N, Np, epi, lens=None, bias=None, act=ACT_NONE, E=None, lde=0, e_bs=None, X=None, post_scale=1.0,
               next_bias=None, Y=None, out=None, ldc=None, c_bs=None, lda=None, a_bs=None, mask_rows=True, gate_mode=0, gate256=False,
-              split=0, cur_bias=None, out_scale=1.0, q_scale=0.0, one_product=False, a_compact=False):
+              split=0, cur_bias=None, out_scale=1.0, q_scale=0.0, one_product=False, a_compact=False, group_size=0, w_gs=0, bias_gs=0, next_bias_gs=0,
+              cur_bias_gs=0):
     """ss_gemm_bf16: A, Wh = bf16 device tensors (A [B,T,lda], Wh packed [Np][len(taps)*K]); see include/stylesinger_hip.h."""
     a = GemmBf16Args()
     a.A = ptr(A); a.lda = lda if lda is not None else A.shape[-1]
@@ -509,6 +510,8 @@ def gemm_bf16(A, Wh, *, B, T, K, taps, N, Np, epi, lens=None, bias=None, act=ACT
     a.one_product = int(one_product)
     a.a_compact = int(a_compact)
     a.cur_bias = ptr(cur_bias)
+    a.group_size = group_size; a.w_group_stride = w_gs; a.bias_group_stride = bias_gs
+    a.next_bias_group_stride = next_bias_gs; a.cur_bias_group_stride = cur_bias_gs
     if gate256 and epi == HEPI_STORE and split == 3:   # the fp16q4 skip GEMM
         check(load().ss_gemm_bf16_tile256q(C.byref(a), stream_ptr()), "ss_gemm_bf16_tile256q")
         return
