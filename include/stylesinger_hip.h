@@ -853,12 +853,35 @@ int ss_normalize_volume(const float* wav, const int32_t* lens, float* out, int B
 int ss_round_f16_rows(const float* x, int64_t ldx, int Lx, const int32_t* n_in, const int32_t* n_out, float* y, int64_t ldy, int B, void* stream);
 /* trim_long_silences (data_gen/tts/emotion/audio.py:58-100; called by preprocess_wav :38) AROUND the caller's voice-activity flags: the decision
  * itself is webrtcvad's (an un-vendored C library, no published text to restate); the reference's windowing, smoothing, dilation and compaction
- * run here. wav [B][wav_stride] fp32, n_samples[b] valid samples; flags [B][flags_stride] uint8, one per window of samples_per_window samples
+ * run here. (Callers without that package may take the flags from ss_vad_lrt below: this project's own decision, on the device.) wav [B][wav_stride] fp32, n_samples[b] valid samples; flags [B][flags_stride] uint8, one per window of samples_per_window samples
  * (floor(n_samples / samples_per_window) of them are read). A window is kept iff, after a moving average of avg_width windows rounded half to even
  * (more than half of the neighbourhood voiced), any window within max_silence / 2 of it (binary_dilation with ones(max_silence + 1)) is voiced.
  * out [B][out_stride] <- the kept windows back to back, zeros behind; out_lens[b] = kept samples; win_dst [B][max_windows] int32 scratch. */
 int ss_vad_trim(const float* wav, int64_t wav_stride, const int32_t* n_samples, const uint8_t* flags, int flags_stride, int B, int max_windows,
                 int samples_per_window, int avg_width, int max_silence, float* out, int64_t out_stride, int32_t* out_lens, int32_t* win_dst, void* stream);
+/* A voice-activity decision of this project's own for ss_vad_trim's flags (opt-in: vad_flags="lrt"): a per-window likelihood-ratio test in the
+ * maximum-likelihood form of Sohn, Kim & Sung (1999) against a noise spectrum taken from the item's own quietest windows. NOT webrtcvad: parity
+ * with it is neither claimed nor wanted, and the constants are unassessed on recordings. The definition is `lrt_statistic` in
+ * stylesinger_amd/vadtrim.py (float64), which also passes the constants. Per item b with n = n_samples[b] (a DEVICE array, clamped to
+ * [0, wav_stride]; what the row holds at or beyond n is never read) and nW = min(n / samples_per_window, max_windows) windows:
+ *   p = clip(rint(wav * 32767), -32768, 32767); window w = p[w spw .. (w + 1) spw) times table's window, zero-padded to n_fft;
+ *   P[w][k] = |DFT|^2 for k = k_lo .. k_hi; E[w] = sum_k P[w][k] (ascending k);
+ *   N[k] = mean of P[w][k] over the q = max(1, ceil(nW / q_div)) windows of smallest E (ties to the smaller index), summed in ascending w;
+ *   if sum_k N[k] > thr = max_w E[w] * 10^(-peak_db / 10): every N[k] times thr / sum_k N[k]; then N[k] = max(N[k], n_min);
+ *   g = P[w][k] / N[k]; stat[w] = (sum_k (g > 1 ? g - ln g - 1 : 0)) / (k_hi - k_lo + 1); flags[w] = stat[w] > eta.
+ * flags [B][flags_stride] uint8 and stat [B][stat_stride] float64 (may be NULL): max_windows columns are written, 0 at and beyond nW.
+ * table: 2 n_fft + samples_per_window float64 on the device: n_fft complex twiddles by butterfly span, [2 (s + j)], [2 (s + j) + 1] = cos, -sin
+ * of 2 pi j / (2 s) for s = 1, 2, 4, ..., n_fft / 2 and j < s (entry 0 unused), then the window.
+ * Geometry: n_fft a power of two in [64, 1024], 1 <= samples_per_window <= n_fft, 0 <= k_lo <= k_hi <= n_fft / 2, at most 128 bins,
+ * max_windows <= 4096, q_div >= 1.
+ * Two launches, float64 throughout: (a) one wave per window quantises, windows and transforms it in LDS and writes P and E to the workspace;
+ * (b) one workgroup per item ranks E by counting, builds N in the order above and writes stat and flags. No atomics, every sum in the stated
+ * order: an item's row is bit-identical from run to run and does not depend on B, wav_stride or the other items. The workspace is the caller's
+ * (ss_vad_lrt_workspace_bytes: 129 float64 per window, 0 for B <= 0 or max_windows <= 0): no allocation, no host synchronisation. */
+int64_t ss_vad_lrt_workspace_bytes(int B, int max_windows);
+int ss_vad_lrt(const float* wav, int64_t wav_stride, const int32_t* n_samples, int B, int max_windows, int samples_per_window, int n_fft, int k_lo,
+               int k_hi, int q_div, double peak_db, double n_min, double eta, const double* table, uint8_t* flags, int flags_stride, double* stat,
+               int stat_stride, void* ws, int64_t ws_bytes, void* stream);
 /* Polyphase sample-rate conversion by up / down (reduced sr_out / sr_in): what `librosa.core.load(path, sr=audio_sample_rate)` does to a file of
  * another rate (utils/audios/__init__.py:52; resampy's `kaiser_best` windowed sinc - un-vendored: parity UNPINNED, `stylesinger_amd/resample.py`
  * holds the definition and builds the bank). Output t of item b sits at input position t * down / up = n + p / up (64-bit integers):

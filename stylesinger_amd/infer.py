@@ -9,7 +9,8 @@ embedding (resemblyzer's published algorithm on the emotion encoder's kernels, `
 the f0 contour (Praat's autocorrelation method, `f0track.py`; parity unpinned: parselmouth is un-vendored) and its normalisation.
 `trim_long_silences` runs on the device AROUND webrtcvad's per-window decisions (a fixed-point GMM whose tables are not in the reference tree):
 they are computed on the host when the package is importable, or given by the caller; skipping the trim is an explicit opt-out
-(`vad_flags=False`), never a silent default.
+(`vad_flags=False`), never a silent default. `vad_flags="lrt"` / `StyleSingerInfer(vad="lrt")` / `--vad lrt` opt into this project's own
+decision on the device instead (`vadtrim.lrt_statistic`, `ss_vad_lrt`: a likelihood-ratio test, NOT webrtcvad's; the audio then never leaves the device).
 `infer_once(inp)` = the reference's entry point (inference/StyleSinger.py:175-179) with the features kept on the device between the producers and
 the model; `python -m stylesinger_amd.infer` = `example_run` (:181-331).
 `sing_score(inp)` (`--score song.json`) sings a score of any length: split at its rests, rendered as batches, stitched on the device (`song.py`: planner and renderer).
@@ -45,13 +46,19 @@ def _instance(cls, hparams, ctor):
 
 class StyleSingerInfer(ReferenceProducers):
     def __init__(self, hparams=None, device=None, model_state=None, vocoder_state=None, vocoder_config=None, dictionary=None,
-                 emotion_state=None, speaker_state=None, phone_set=None, loudness=None):
+                 emotion_state=None, speaker_state=None, phone_set=None, loudness=None, vad=None):
         """`loudness`: "bs1770" = honour hparams['loud_norm'] with this project's BS.1770 meter (`loudness.py`; parity with pyloudnorm UNPINNED, so
         the bare flag stays refused: `loudness.resolve_loudness`).
+        `vad`: what `vad_flags=None` resolves to in `preprocess_input` / `infer_once` / `sing_score` (`_resolve_vad`): None = the reference's
+        webrtcvad decision on the host (ImportError where the package is missing), "webrtc" = the same, asked for by name, "lrt" = this
+        project's own likelihood-ratio decision on the device (`vadtrim.py`; NOT webrtcvad's, constants unassessed on recordings).
         `emotion_state`: state_dict of the reference's emotion encoder checkpoint (`EmotionEncoder.load_model`,
         inference/StyleSinger.py:101) - enables the emotion branch of `preprocess_batch`.
         `speaker_state`: `model_state` of resemblyzer's `pretrained.pt` (`VoiceEncoder()`, inference/StyleSinger.py:100) - enables the
         speaker branch."""
+        if vad not in (None, "webrtc", "lrt"):
+            raise ValueError(f"vad={vad!r}: expected None, 'webrtc' or 'lrt'")
+        self.vad = vad
         self.hparams = make_hparams(hparams)
         self._front_hparams = hparams
         # inference/StyleSinger.py:27-28: ph_encoder = build_token_encoder(f"{processed_data_dir}/phone_set.json"); `phone_set` overrides the path
@@ -332,7 +339,7 @@ def _score_run(score, hparams, out_path, segments_out=None, vad_flags=None, max_
 
 def main(argv=None):
     """`python -m stylesinger_amd.infer --exp-dir checkpoints/<exp> --vocoder-dir <hifigan dir> --emotion-ckpt <pt> --speaker-ckpt <pt>
-    --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim]` = the reference's
+    --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim | --vad {webrtc,lrt}]` = the reference's
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
     sing the score on a given pitch contour instead of the predicted one; `--pitch-align dtw [--pitch-align-band-s 2.0]`: the contour is a guide
     with its own timing, warp it onto the score's notes (band in seconds around the linear fit, 0 = full) instead of scaling it linearly. `--loud-norm`: loudness-normalise the reference audio as a model trained with
@@ -350,6 +357,9 @@ def main(argv=None):
     ap.add_argument("--ref-audio", help="the reference voice (default: the score file's ref_audio, else test/test.wav)")
     ap.add_argument("--out", default="infer_out/test.wav")
     ap.add_argument("--no-vad-trim", action="store_true", help="explicit opt-out of trim_long_silences (webrtcvad missing)")
+    ap.add_argument("--vad", choices=["webrtc", "lrt"], help="the voice-activity decision inside trim_long_silences: webrtc = the reference's (the "
+                    "webrtcvad package on the host; the default), lrt = this project's own likelihood-ratio decision on the device (not webrtcvad's; "
+                    "constants unassessed on recordings)")
     ap.add_argument("--pitch-audio", help="sing on the pitch of this guide vocal (a WAV file, tracked on the device, 80-800 Hz) instead of the predicted f0")
     ap.add_argument("--pitch-npy", help="sing on this contour: a .npy file holding a 1-D array of Hz at the mel hop, 0 = unvoiced")
     ap.add_argument("--pitch-shift", type=float, help="transpose the given contour by this many semitones")
@@ -371,6 +381,8 @@ def main(argv=None):
     ap.add_argument("--fade-ms", type=float, default=5.0, help="--score: raised-cosine fade on both sides of every joint")
     ap.add_argument("--segments-out", help="--score: write the timeline (phone ranges and start samples per segment) to this JSON file")
     a = ap.parse_args(argv)
+    if a.vad and a.no_vad_trim:
+        ap.error("--vad and --no-vad-trim exclude each other")
     if a.pitch_audio and a.pitch_npy:
         ap.error("--pitch-audio and --pitch-npy exclude each other")
     if a.pitch_shift is not None and not (a.pitch_audio or a.pitch_npy):
@@ -432,10 +444,10 @@ def main(argv=None):
     ctor = dict(exp_dir=a.exp_dir, vocoder_dir=a.vocoder_dir, emotion_state=emo.get("model_state", emo),
                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
     if score is not None:
-        _score_run(score, hp or None, a.out, segments_out=a.segments_out, vad_flags=False if a.no_vad_trim else None, max_seconds=a.max_seconds,
+        _score_run(score, hp or None, a.out, segments_out=a.segments_out, vad_flags=False if a.no_vad_trim else a.vad, max_seconds=a.max_seconds,
                    segment_batch=a.segment_batch, fade_ms=a.fade_ms, **ctor)
         return
-    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else None, pitch=pitch, **ctor)
+    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch=pitch, **ctor)
 
 
 if __name__ == "__main__":

@@ -194,7 +194,9 @@ class ReferenceProducers:
                    device AROUND the caller's decisions: pass `emo_vad_flags` [B, nW] = webrtcvad's `is_speech` per 30 ms window of the
                    volume-normalised 16-bit PCM (the decision itself is an un-vendored fixed-point GMM: `vadtrim.py`); without flags the
                    audio goes untrimmed; `emo_vad_flags="webrtc"` computes them on the host with the webrtcvad package from the device-normalised
-                   audio (`vadtrim.webrtc_flags`: the reference's own call). Pass `emo_embed` [B, 256] instead to skip this branch.
+                   audio (`vadtrim.webrtc_flags`: the reference's own call); `emo_vad_flags="lrt"` computes them on the device with this
+                   project's own likelihood-ratio decision (`vadtrim.lrt_flags_device`, `ss_vad_lrt`: opt-in, NOT webrtcvad's decision, constants
+                   unassessed on recordings), the audio never leaving the device. Pass `emo_embed` [B, 256] instead to skip this branch.
         The returned dict also carries `ref_f0_hz` [B, Tr] (the tracker's contour on the mel grid, before normalisation) for callers that mirror
         `preprocess_input`'s `inp['f0']`.
           spk_embed [B, 256], or None -> `VoiceEncoder().embed_utterance(wav)` (:100,104) on the device (`embed_speaker_batch`;
@@ -228,10 +230,11 @@ class ReferenceProducers:
                 emo_wavs = self._emo_front().normalize_volume(raw_wavs, torch.tensor(ref_lens_h))
                 emo_lens = ref_lens_h
                 if isinstance(emo_vad_flags, str):
-                    if emo_vad_flags != "webrtc":
-                        raise ValueError(f"emo_vad_flags={emo_vad_flags!r}: expected flags, None or 'webrtc'")
-                    from .vadtrim import webrtc_flags
-                    emo_vad_flags = webrtc_flags(emo_wavs, emo_lens)
+                    if emo_vad_flags not in ("webrtc", "lrt"):
+                        raise ValueError(f"emo_vad_flags={emo_vad_flags!r}: expected flags, None, 'webrtc' or 'lrt'")
+                    from .vadtrim import lrt_flags_device, webrtc_flags
+                    # "lrt": the audio stays on the device between normalize_volume and ss_vad_trim
+                    emo_vad_flags = webrtc_flags(emo_wavs, emo_lens) if emo_vad_flags == "webrtc" else lrt_flags_device(emo_wavs, emo_lens)[0]
                 if emo_vad_flags is not None:   # preprocess_wav's second step (audio.py:38), around the VAD flags
                     from .vadtrim import trim_long_silences_device
                     emo_wavs, kept = trim_long_silences_device(emo_wavs, emo_lens, emo_vad_flags)
@@ -251,14 +254,23 @@ class ReferenceProducers:
         """`preprocess_wav` ALWAYS trims long silences (data_gen/tts/emotion/audio.py:36-38). None = do as the reference does: webrtcvad's decisions,
         computed on the host - an ImportError where the package is missing (it is un-vendored), never a silent skip. False = explicit opt-out
         (untrimmed audio; warns once: the emotion embedding of a recording with long pauses then differs from the reference's). Otherwise the
-        caller's flags [nW]."""
+        caller's flags [nW], or a decision by name: "webrtc" (as None, asked for explicitly) or "lrt" (this project's own likelihood-ratio decision
+        on the device, `vadtrim.lrt_flags_device`: opt-in, not webrtcvad's). None resolves to the instance's `vad` (StyleSingerInfer(vad=...)) when
+        that is set."""
+        if vad_flags is None:
+            vad_flags = getattr(self, "vad", None)   # (an instance made with __new__ has no attribute: the reference's behaviour)
         if vad_flags is None:
             from .vadtrim import have_webrtcvad
             if not have_webrtcvad():
                 raise ImportError("preprocess_input: the reference trims long silences with webrtcvad before the emotion encoder, and the package is "
                                   "not importable here. Pass vad_flags=<webrtcvad's is_speech per 30 ms window> or vad_flags=False to skip the trim "
-                                  "explicitly (the emotion embedding then differs from the reference's for audio with long pauses).")
+                                  "explicitly (the emotion embedding then differs from the reference's for audio with long pauses), or "
+                                  "vad_flags=\"lrt\" for this project's own on-device decision (not webrtcvad's).")
             return "webrtc"
+        if isinstance(vad_flags, str):
+            if vad_flags not in ("webrtc", "lrt"):
+                raise ValueError(f"vad_flags={vad_flags!r}: expected flags, None, False, 'webrtc' or 'lrt'")
+            return vad_flags
         if vad_flags is False:
             if not type(self)._warned_untrimmed:   # on the instance's own class: that is where callers reset it
                 type(self)._warned_untrimmed = True
@@ -323,7 +335,8 @@ class ReferenceProducers:
         `inp['ref_audio']`: the path of a WAV file (`audiofile.load_audio`: PCM or float, any channel count, any sample rate), a float waveform at
         `inp['ref_sr']` Hz (default: the model's sample rate) or a `(waveform, sample_rate)` pair; audio of another rate is resampled on the device as
         `librosa.core.load(wav_path, sr=audio_sample_rate)` does (`resample.py`; parity with librosa UNPINNED). Needs `emotion_state` and
-        `speaker_state` (the two encoders' checkpoints). `vad_flags`: see `_resolve_vad` (None = webrtcvad on the host, False = opt out).
+        `speaker_state` (the two encoders' checkpoints). `vad_flags`: see `_resolve_vad` (None = webrtcvad on the host unless the instance was made with `vad=`,
+        False = opt out, "lrt" = this project's own decision on the device).
         Pitch control (`_pitch_inputs`): `inp['pitch_hz']` / `inp['pitch_shift']` pass through; `inp['pitch_audio']` (a guide vocal) is tracked
         on the device and replaced by its contour in `inp['pitch_hz']`."""
         batch = self._device_batch(inp, vad_flags)
