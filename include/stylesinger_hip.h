@@ -920,6 +920,30 @@ int ss_loudness_measure(const float* x, int64_t ldx, int Lx, const int32_t* n, c
 int ss_loudness_apply(const float* x, int64_t ldx, int Lx, const int32_t* n, const float* gain, const float* peak, float* y, int64_t ldy, int Ly,
                       int B, void* stream);
 
+/* Look-ahead true-peak limiter of the output (hparams['out_true_peak_db']; `stylesinger_amd/limiter.py` holds the definition and builds the bank -
+ * this project's own 4x peak estimate on the resampler's windowed-sinc bank, NOT a standard-conformant true-peak meter). Per item b with
+ * G = gain[b] (NULL: 1; what ss_loudness_measure writes: ss_loudness_apply and its peak rule are then bypassed), x'[t] = fl32(G x[b][t]) inside
+ * [0, n[b]) and zero outside (what the buffer holds past n[b] <= min(Lx, Ly) is padding and never read into a result):
+ *   e[t] = max(|x'[t]|, max over p < 4 of |sum_{k < taps} bank[p][k] x'[t + k - left]|)   bank [4][taps] fp32, fp32 FMA over k in ascending order
+ *   r[t] = fl32(c / e[t]) where e[t] > c, else 1; 1 outside [0, n)
+ *   m[t] = min of r over [t, t + W - 1]
+ *   g[t] = min(r[t], fl32(s / W)), s = the fp32 sum of m[t - W + 1 .. t] in ascending order (IEEE division: W ones give exactly 1)
+ *   y[b][t] = fl32(g[t] x'[t]) for t < n[b], exact zeros for n[b] <= t < Ly.
+ *   min_gain[b] = min over t < n[b] of g[t] (1 for an empty item), n_limited[b] = #{t < n[b] : g[t] < 1}; g_out (may be NULL) [B][ldy]: g[t] for
+ *   t < n[b], 1 up to Ly.
+ * 0 < c <= 1, 1 <= W <= SS_LIMIT_MAX_W, taps <= 256, 0 <= left < taps. One workgroup owns a tile of 1856 consecutive samples of one item: it
+ * stages x' for the tile plus left + W - 1 samples before and taps - 1 - left + W - 1 after it in LDS, computes e and r over the tile plus W - 1
+ * samples on both sides, takes the sliding minimum there by doubling, then the W-term sum, the outer min and the product. min_gain / n_limited are
+ * reduced from per-tile partials in the workspace (ss_limit_workspace_bytes, 64-byte aligned; < 0 for bad dims; it also holds a tap-major copy
+ * of the bank that a first small launch writes) by a last launch. No atomics, every
+ * sum in a fixed order: bit-identical from run to run, independent of B, Lx, Ly, ldx, ldy and the other items. No allocation: graph-capturable.
+ * y (and g_out) must not alias x: the ranges [x, x + (B - 1) ldx + Lx) and [y, y + (B - 1) ldy + Ly) must be disjoint (checked). */
+#define SS_LIMIT_MAX_W 512
+int64_t ss_limit_workspace_bytes(int B, int Ly);
+int ss_limit_true_peak(const float* x, int64_t ldx, int Lx, const int32_t* n, const float* gain, const float* bank, int taps, int left, float c, int W,
+                       float* y, int64_t ldy, int Ly, float* min_gain, int32_t* n_limited, float* g_out, int B, void* ws, int64_t ws_bytes,
+                       void* stream);
+
 /* Vocoder output denoise: what `denoise(wav_out, v=hparams['vocoder_denoise_c'])` does at the end of HifiGAN.spec2wav
  * (tasks/tts/vocoder_infer/hifigan_nsf.py:14-22, 73-74): a spectral subtraction between librosa 0.8's stft(center=True, pad_mode='constant') and
  * istft(center=True) - librosa is un-vendored: parity UNPINNED, `stylesinger_amd/denoise.py` holds the definition and builds the table. With

@@ -57,6 +57,9 @@ DEFAULT_HPARAMS = dict(
     t_bucket=64,
     # not a reference key: write the result at this BS.1770 integrated loudness in LUFS (loudness.py; None = as synthesised). Excludes out_wav_norm.
     out_loudness_lufs=None,
+    # not reference keys: true-peak ceiling of the result in dBFS (<= 0; limiter.py: a look-ahead limiter on the device after the loudness gain, which
+    # is then applied in full - no peak rule; None = off, the result as before) and its look-ahead / release window in ms. Excludes out_wav_norm.
+    out_true_peak_db=None, out_limiter_lookahead_ms=2.0,
     # vocoder output denoise (egs/egs_bases/tts/base.yaml:107; hifigan_nsf.py:73-74): > 0 = spectral subtraction of this magnitude after the generator
     # (denoise.py), with the geometry keys fft_size / win_size / hop_size of the caller's hparams
     vocoder_denoise_c=0.0,

@@ -78,6 +78,12 @@ class StyleSingerInfer(ReferenceProducers):
         resolve_denoise(self.hparams)   # hparams['vocoder_denoise_c'] > 0: a geometry the kernel does not compute is refused here (the vocoder plugin applies it)
         if self.hparams.get("out_loudness_lufs") is not None and (self.hparams.get("out_wav_norm") or (hparams or {}).get("out_wav_norm")):
             raise ValueError("hparams: out_loudness_lufs and out_wav_norm exclude each other (a loudness target or peak normalisation, not both)")
+        if self.hparams.get("out_true_peak_db") is not None:
+            if self.hparams.get("out_wav_norm") or (hparams or {}).get("out_wav_norm"):
+                raise ValueError("hparams: out_true_peak_db and out_wav_norm exclude each other (a true-peak ceiling or peak normalisation, not both)")
+            from .limiter import ceiling_f32, window_samples   # a ceiling above 0 dBFS or a window beyond LIMIT_MAX_W: refused before a device is touched
+            ceiling_f32(self.hparams["out_true_peak_db"])
+            window_samples(self.hparams["audio_sample_rate"], self.hparams["out_limiter_lookahead_ms"])
         if device is None:
             if not torch.cuda.is_available():
                 raise L.StyleSingerHipError("StyleSingerInfer (HIP) needs a GPU: there is no CPU path")
@@ -121,7 +127,7 @@ class StyleSingerInfer(ReferenceProducers):
 
     # ---- batched, device resident -------------------------------------------------------------
     @torch.no_grad()
-    def infer_batch(self, batch, noise=None, vocoder_noise=None, seed=None, vocode=True, plan_slot=0, out_lufs=None):
+    def infer_batch(self, batch, noise=None, vocoder_noise=None, seed=None, vocode=True, plan_slot=0, out_lufs=None, out_true_peak_db=None):
         """batch: dict of device tensors (txt_tokens, note, note_dur, note_type, spk_embed, emo_embed, ref_mels,
         ref_f0, optional mel2ph).  Returns dict(mel [B,T,80], f0 [B,T], lens int32 [B], wav [B,T*hop]).
         Pitch control (StyleSingerHIP.forward): optional `f0` + `uv` [B, T] (the normalised contour, the reference's use_gt_f0 form), or
@@ -130,6 +136,9 @@ class StyleSingerInfer(ReferenceProducers):
         being scaled linearly; items the aligner left to the linear fit (`model_out['pitch_align_status']` != 0) are named in a warning where
         this method reads the lengths on the host anyway (`out_lufs`), never through a sync of its own.
         `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain).
+        `out_true_peak_db`: hold every item of `wav` under this true-peak ceiling with the look-ahead limiter (`_finish_wav`, `limiter.py`; adds
+        res['limiter'] = {min_gain, n_limited} as device tensors); with `out_lufs` too the loudness gain is applied in full (res['loudness_gain'])
+        and the limiter takes the place of the peak rule.
         Optional `style_cache`: what `model.encode_style` returned for the batch's references; the style encoder is then skipped."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
@@ -143,8 +152,9 @@ class StyleSingerInfer(ReferenceProducers):
         res = dict(mel=out["mel_out"], f0=out["f0_denorm"], lens=out["lens"], model_out=out)
         if vocode:
             res["wav"] = self.vocode(out["mel_out"], out["f0_denorm"], out["lens"], noise=vocoder_noise, seed=seed + 101)
-            if out_lufs is not None:
-                res["wav"], res["lufs"] = self._to_lufs(res["wav"], [int(v) * self.vocoder.model.hop for v in out["lens"].cpu()], out_lufs)
+            if out_lufs is not None or out_true_peak_db is not None:
+                res["wav"], info = self._finish_wav(res["wav"], [int(v) * self.vocoder.model.hop for v in out["lens"].cpu()], out_lufs, out_true_peak_db)
+                res.update(info)
                 self._warn_unaligned(out)   # (the copy above synchronised)
         return res
 
@@ -168,6 +178,29 @@ class StyleSingerInfer(ReferenceProducers):
         if 0 in m["n_blocks"]:
             warnings.warn(f"out_loudness_lufs: {m['n_blocks'].count(0)} item(s) shorter than one 0.4 s gating block left at their own level")
         return y, m["lufs"]
+
+    def _finish_wav(self, wav, lens, out_lufs=None, true_peak_db=None):
+        """The end of the output chain for wav [B, L] on the device (lens host ints) -> (wav, what it adds to a result dict). Without a
+        ceiling: `_to_lufs` (or nothing). With `true_peak_db` (hparams['out_true_peak_db']): the look-ahead true-peak limiter (`limiter.py`);
+        a loudness target then becomes `ss_loudness_measure` + `ss_limit_true_peak(gain=...)` - the gain in full ('loudness_gain', fp32 [B]), no
+        division by the peak - and 'limiter' = {min_gain, n_limited} stay on the device."""
+        if true_peak_db is None:
+            if out_lufs is None:
+                return wav, {}
+            y, lufs = self._to_lufs(wav, lens, out_lufs)
+            return y, dict(lufs=lufs)
+        from .limiter import limit_batch
+        sr, info, gain = int(self.hparams["audio_sample_rate"]), {}, None
+        if out_lufs is not None:
+            from .loudness import measure_batch
+            m = measure_batch(wav, lens, sr, target=float(out_lufs), short="skip")
+            if 0 in m["n_blocks"]:
+                warnings.warn(f"out_loudness_lufs: {m['n_blocks'].count(0)} item(s) shorter than one 0.4 s gating block left at their own level")
+            gain = m["gain"]
+            info.update(lufs=m["lufs"], loudness_gain=gain)
+        y, rep = limit_batch(wav, lens, sr, true_peak_db, lookahead_ms=self.hparams["out_limiter_lookahead_ms"], gain=gain)
+        info["limiter"] = rep
+        return y, info
 
     @torch.no_grad()
     def infer_batches(self, batches, in_flight=3, seed=None, vocode=True):
@@ -239,7 +272,7 @@ class StyleSingerInfer(ReferenceProducers):
         from .writer import wav_to_pcm16
         if not (self.hparams.get("use_gt_f0") and batch.get("f0") is not None and batch.get("uv") is not None):
             batch = {k: v for k, v in batch.items() if k not in ("f0", "uv")}
-        res = self.infer_batch(batch, seed=seed, out_lufs=self.hparams.get("out_loudness_lufs"))
+        res = self.infer_batch(batch, seed=seed, out_lufs=self.hparams.get("out_loudness_lufs"), out_true_peak_db=self.hparams.get("out_true_peak_db"))
         self.model.check_finite(res["model_out"])
         hop = self.vocoder.model.hop
         pcm = wav_to_pcm16(res["wav"], res["lens"], hop, norm=bool(self.hparams.get("out_wav_norm", False)))
@@ -287,7 +320,8 @@ class StyleSingerInfer(ReferenceProducers):
         res = self.infer_batch({k: v for k, v in batch.items() if k not in ("n_mel", "wav_fn", "ref_f0_hz")}, noise=noise, vocode=False)
         return self.postprocess_output(self._wav_from_result(res, vocoder_noise))
 
-    def sing_score(self, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None):
+    def sing_score(self, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None,
+                   out_true_peak_db=None):
         """Sing a score of any length in the reference's voice: `inp` = the reference's input dict (`ph` | `ph_token`, `note`, `note_dur`, `note_type`,
         optionally `ph_dur` = seconds per phone, `pitch_hz` | `pitch_audio`, `pitch_shift`, `pitch_align` (+ `pitch_align_band_s`): every segment
         then warps ITS slice of the contour onto its own notes, the slice's ends pinned; the planner's cut of the contour stays linear;
@@ -296,12 +330,13 @@ class StyleSingerInfer(ReferenceProducers):
         plan's batches run through `infer_batches` (batch i with seed + i), and the segments are put on one timeline on the device
         (`ss_song_offsets` + three `ss_song_place` per batch: the waveform with a raised-cosine fade of `fade_ms` on both sides of every joint, the
         mel and the f0 as they are). Segments never overlap: the song is their concatenation. ONE host sync at the end learns the length. Loudness
-        (`out_lufs`, else hparams['out_loudness_lufs']) is applied to the WHOLE song, never per segment: that would flatten its dynamics.
+        (`out_lufs`, else hparams['out_loudness_lufs']) is applied to the WHOLE song, never per segment: that would flatten its dynamics. So is the
+        true-peak limiter (`out_true_peak_db`, else hparams['out_true_peak_db']; `_finish_wav`), once, after the stitch: adds 'limiter' (one entry).
         -> dict(wav [N], mel [F, 80], f0 [F] on the device, segments = [{first, last, start_frame, n_frames, batch, row}] (phones [first, last)),
         plan (the SongPlan; its batches in their device form), lufs (float, the loudness before the gain) when a target is set)."""
         from . import song
         return song.sing_score(self, inp, max_seconds=max_seconds, segment_batch=segment_batch, fade_ms=fade_ms, in_flight=in_flight, seed=seed,
-                               out_lufs=out_lufs, vad_flags=vad_flags)
+                               out_lufs=out_lufs, vad_flags=vad_flags, out_true_peak_db=out_true_peak_db)
 
     @classmethod
     def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, pitch=None, **ctor):
@@ -315,8 +350,9 @@ class StyleSingerInfer(ReferenceProducers):
         inp.update(pitch or {})   # pitch control: pitch_hz | pitch_audio, pitch_shift (`_pitch_inputs`)
         ins = _instance(cls, hparams, ctor)
         out = ins.infer_once(inp, vad_flags=vad_flags)
-        if ins.hparams.get("out_loudness_lufs") is not None:
-            y, _ = ins._to_lufs(torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32))[None].to(ins.device), [len(out)], ins.hparams["out_loudness_lufs"])
+        if ins.hparams.get("out_loudness_lufs") is not None or ins.hparams.get("out_true_peak_db") is not None:
+            y, _ = ins._finish_wav(torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32))[None].to(ins.device), [len(out)],
+                                   ins.hparams.get("out_loudness_lufs"), ins.hparams.get("out_true_peak_db"))
             out = y[0].cpu().numpy()
         _write_wav(ins, out, out_path)
         return out
@@ -343,7 +379,8 @@ def main(argv=None):
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
     sing the score on a given pitch contour instead of the predicted one; `--pitch-align dtw [--pitch-align-band-s 2.0]`: the contour is a guide
     with its own timing, warp it onto the score's notes (band in seconds around the linear fit, 0 = full) instead of scaling it linearly. `--loud-norm`: loudness-normalise the reference audio as a model trained with
-    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
+    hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--out-true-peak DB [--out-lookahead-ms 2]`: hold the result under DB dBFS
+    true peak with the look-ahead limiter (with --out-lufs the loudness gain is then applied in full instead of being divided by the peak); `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
     subtraction of V, e.g. 0.1) after the generator, before the loudness target and the writer.
     `--score song.json [--max-seconds 12] [--segment-batch 8] [--fade-ms 5] [--segments-out timeline.json]`: sing a score of any length (the keys of
     example_input.json, optionally `ph_dur`; its `ref_audio` unless --ref-audio is given) with `sing_score`; pitch flags then need `ph_dur` in the score."""
@@ -369,6 +406,10 @@ def main(argv=None):
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
+    ap.add_argument("--out-true-peak", type=float, metavar="DB", help="hold the result under this true-peak ceiling in dBFS (<= 0, e.g. -1) with the "
+                    "look-ahead limiter on the device (hparams['out_true_peak_db']; this project's own 4x peak estimate, not a standard-conformant meter)")
+    ap.add_argument("--out-lookahead-ms", type=float, metavar="MS", help="--out-true-peak: look-ahead and release window (hparams['out_limiter_lookahead_ms'], "
+                    "default 2)")
     ap.add_argument("--vocoder-denoise-c", type=float, help="spectral subtraction of this magnitude on the vocoder's output "
                     "(hparams['vocoder_denoise_c'], e.g. 0.1; 0 = off)")
     ap.add_argument("--f0-steps", type=int, help="sample the two f0 / uv diffusions at this many of their f0_timesteps network times "
@@ -429,6 +470,17 @@ def main(argv=None):
         hp["loud_norm"] = True
     if a.out_lufs is not None:
         hp["out_loudness_lufs"] = a.out_lufs
+    if a.out_lookahead_ms is not None and a.out_true_peak is None:
+        ap.error("--out-lookahead-ms belongs to --out-true-peak")
+    if a.out_true_peak is not None:
+        from .limiter import ceiling_f32
+        try:
+            ceiling_f32(a.out_true_peak)   # (the window is checked against the model's sample rate by the constructor)
+        except ValueError as e:
+            ap.error(str(e))
+        hp["out_true_peak_db"] = a.out_true_peak
+        if a.out_lookahead_ms is not None:
+            hp["out_limiter_lookahead_ms"] = a.out_lookahead_ms
     if a.vocoder_denoise_c is not None:
         hp["vocoder_denoise_c"] = a.vocoder_denoise_c
     if a.f0_steps is not None:

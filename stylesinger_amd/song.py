@@ -253,7 +253,8 @@ def _song_reference(ins, inp, vad_flags):
 
 
 @torch.no_grad()
-def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None):
+def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flight=3, seed=None, out_lufs=None, vad_flags=None,
+               out_true_peak_db=None):
     """The body of `StyleSingerInfer.sing_score` (arguments and result: its docstring); `ins` = the infer object. The flow is the module docstring's:
     reference once, plan, batches through `infer_batches`, stitch on the device, loudness over the whole song."""
     hp, d = ins.hparams, ins.device
@@ -314,7 +315,12 @@ def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flig
                       f"[{plan.segments[long_[0]]['first']}, {plan.segments[long_[0]]['last']}), {plan.segments[long_[0]]['n_frames']} frames); lower "
                       "max_seconds or add rests")
     target = out_lufs if out_lufs is not None else hp.get("out_loudness_lufs")
-    if target is not None:
-        y, lufs = ins._to_lufs(out["wav"][None], [F * hop], target)
-        out["wav"], out["lufs"] = y[0], float(lufs[0])
+    ceiling = out_true_peak_db if out_true_peak_db is not None else hp.get("out_true_peak_db")
+    if target is not None or ceiling is not None:   # the WHOLE song, once, after the stitch
+        y, info = ins._finish_wav(out["wav"][None], [F * hop], target, ceiling)
+        out["wav"] = y[0]
+        if target is not None:
+            out["lufs"] = float(info["lufs"][0])
+        if ceiling is not None:
+            out["limiter"] = info["limiter"]
     return out
