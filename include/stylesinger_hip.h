@@ -162,7 +162,9 @@ int ss_conv_gemm(const ss_conv_gemm_args* args, void* stream);
 
 /* Small-K GEMM on 16x16x4 fp32 MFMA tiles for the residual half of the denoisers' output projection (net.py:75-77, deferred-skip
  * form):  C = (R + A . W^T + bias) * post_scale,  K = Cin = Kp in {192, 256}, one tap. A workgroup is 16*mt rows x 64 columns
- * (mt = 4 | 6 | 8, 0 = ss_gemm16_pick); the wave's whole weight slice is register-resident, the A tile arrives by LDS-DMA.
+ * (mt = 2 | 4 | 6 | 8, 0 = ss_gemm16_pick; the 32-row tile mt = 2 exists for this kernel only - the pick returns it for launches whose
+ * 64-row grid leaves half the CUs idle - ss_gemm16_store and its forms take 4 | 6 | 8); the wave's whole weight slice is
+ * register-resident, the A tile arrives by LDS-DMA.
  * Uses A, lda, Cin, Kp, lens, B, T, W, N, Np, bias, R, ldr, C, ldc, post_scale, mask_rows, batch strides and the group fields of
  * ss_conv_gemm_args; C may alias R (in-place residual update). Same result as ss_conv_gemm(epi STORE + R) up to the K order. */
 int ss_gemm16_res(const ss_conv_gemm_args* args, int mt, void* stream);
@@ -228,8 +230,9 @@ int ss_wino_weight_transform(const float* src, float* dst, int Cout, int Cin, vo
  * equal the direct form to fp32 rounding (single-layer error about 2x that of F(2,3); tests/test_gpu_kernels.py). */
 int ss_wino43_gate(const ss_conv_gemm_args* args, int dilation, void* stream);
 /* The same layer on 16x16x4 fp32 MFMA tiles: a wave tile is 16*mt quads x 16 packed columns (8 channels, both gate operands), a
- * workgroup 16*mt quads x 64 packed columns; mt = 2 | 3, or 0 = ss_wino43_gate16_pick decides per launch and falls back to
- * ss_wino43_gate when the 32x32x2 tiles fit better (many rounds of workgroups per launch). For single-round launches: at BASELINE
+ * workgroup 16*mt quads x 64 packed columns; mt = 1 | 2 | 3 (1 exists only in the K-staged form: Kp >= 64 and the gate16_ks knob on,
+ * refused otherwise), or 0 = ss_wino43_gate16_pick decides per launch and falls back to ss_wino43_gate when the 32x32x2 tiles fit
+ * better (many rounds of workgroups per launch). For single-round launches: at BASELINE
  * config 2 the mel launch is 512 workgroups (2 per CU) and the f0-pair launch 768 (3 per CU) instead of 384 / 564 uneven ones.
  * Same arguments, same weights (ss_wino43_weight_transform + ss_pack_conv_weight(k=6, interleave_half=C)), same arithmetic up to
  * the summation order over K (tests/test_gpu_round3.py). */
@@ -239,7 +242,7 @@ int ss_wino43_gate16(const ss_conv_gemm_args* args, int dilation, int mt, void* 
  * Frames >= T of the last tile of an item are written as 0. */
 int ss_gate16_tile_addend(const float* E, int lde, int64_t e_batch_stride, float* E16, int B, int T, int Np, int dilation, int mt, void* stream);
 int64_t ss_gate16_tiled_floats(int B, int T, int Np, int dilation, int mt);
-/* the tiling ss_wino43_gate16(mt = 0) uses for a launch of B items x T frames x Np packed columns: 2 | 3, or 0 = the 32x32x2 kernel */
+/* the tiling ss_wino43_gate16(mt = 0) uses for a launch of B items x T frames x Np packed columns: 1 | 2 | 3, or 0 = the 32x32x2 kernel */
 int ss_wino43_gate16_pick(int B, int T, int Np, int dilation);
 /* src [Cout][Cin][3] -> dst [Cout][Cin][6]: g0=w0/4, g1=-(w0+w1+w2)/6, g2=-(w0-w1+w2)/6, g3=w0/24+w1/12+w2/6,
  * g4=w0/24-w1/12+w2/6, g5=w2 */

@@ -171,8 +171,10 @@ def pack_gate16_weights(Wp, Kp):
 
 
 def wino43_gate16(A, Wt, out, *, dilation, mt=0, W16=None, **kw):
-    """The F(4,3) gate on 16x16x4 MFMA tiles (ss_wino43_gate16); mt = 0 lets the library pick, 2 / 3 force the row-tile count.
-    W16 = pack_gate16_weights(Wt): the weights in the kernel's fetch order (ss_wino43_gate16w)."""
+    """The F(4,3) gate on 16x16x4 MFMA tiles (ss_wino43_gate16); mt = 0 lets the library pick, 1 / 2 / 3 force the row-tile count (16 * mt
+    quads per workgroup). mt = 1 exists only in the K-staged form: it needs Kp >= 64 and the gate16_ks knob on, and is refused otherwise.
+    W16 = pack_gate16_weights(Wt): the weights in the kernel's fetch order (ss_wino43_gate16w). e_tiled=True (E from gate16_tile_addend
+    with the same dilation and mt) needs an explicit mt."""
     kw.setdefault("epi", EPI_GATE)
     a = _fill_args(A, Wt, out, **kw)
     if W16 is not None:
@@ -183,7 +185,8 @@ def wino43_gate16(A, Wt, out, *, dilation, mt=0, W16=None, **kw):
 
 def gemm16_res(A, W, out, *, mt=0, W16=None, **kw):
     """Residual projection C = (R + A.W^T + bias) * post_scale on 16x16x4 tiles (ss_gemm16_res); same keyword arguments as conv_gemm.
-    W16 = pack_gemm16_weights(first N rows of W): the weights in the kernel's fetch order (ss_gemm16_resw)."""
+    mt = 0 lets the library pick, 2 / 4 / 6 / 8 force 16 * mt rows per workgroup (the 32-row tile, mt = 2, exists for this kernel only).
+    W16 = pack_gemm16_weights(first N rows of W): the weights in the kernel's fetch order (ss_gemm16_resw; N % 64 == 0)."""
     a = _fill_args(A, W, out, **kw)
     if W16 is not None:
         check(load().ss_gemm16_resw(C.byref(a), ptr(W16), int(mt), stream_ptr()), "ss_gemm16_resw")
