@@ -1002,6 +1002,49 @@ int ss_contour_align(const float* f0_hz, int64_t ldc, int Lc, const int32_t* len
                      int band, int uv_cost, int cap, float shift_semitones, float* out, int64_t ldo, int32_t* idx, int32_t* cost, int32_t* status,
                      int T, int B, void* ws, int64_t ws_bytes, void* stream);
 
+/* Objective metrics of a rendered item a (rows i, n_a = lens_a[b] <= Ta frames) against a target b (columns j, n_b = lens_b[b] <= Tb frames), both
+ * on the mel hop grid (csrc/evaluate.hip; definitions: `mcep_q`, `dtw_path`, `path_metrics` in stylesinger_amd/evaluate.py). A log-mel cepstral
+ * distortion of this project's OWN definition - not SPTK / WORLD mcep MCD - next to the F0 frame error and the cents RMSE along the same path. All
+ * lens are DEVICE arrays; no entry allocates or synchronises (graph-capturable), none uses atomics, an item's result does not depend on B, the padded
+ * sizes, the strides or the other items, and rows at or past lens are never read into a result.
+ * ss_eval_mcep: mel [B][T] rows of n_mels log10 values (row stride ldm, item stride mel_bs floats) -> q int16 [B][T][Kp], Kp = K rounded up to even:
+ *   m = min(max(mel, vmin), vmax); c_k = 0, then for n = 0 .. n_mels - 1 IN THAT ORDER c_k = fl(c_k + fl(m[n] * tab[k - 1][n])) (no contraction);
+ *   q[k - 1] = (int16) rint(fl(c_k * s)) for k = 1 .. K; frames >= lens[b] (lens NULL: T) and the pad column are 0. tab [K][n_mels] fp32 is an INPUT,
+ *   by convention fl32(sqrt(2 / N) cos(pi k (n + 0.5) / N)) computed in float64 (evaluate.mcep_table: the orthonormal DCT-II without c0).
+ *   Refused, never truncated: a range whose bound s sqrt(N) max(vmax - vmin, |vmin|, |vmax|) (x sqrt(2) when K >= n_mels) + 1 exceeds 32767, or, for
+ *   K >= n_mels, K bound^2 >= 2^31. Inside it every q, every difference of two q fits int16 and S = sum_k (qa_k - qb_k)^2 < 2^31.
+ * ss_eval_cost_band: qa [B][Ta][Kp], qb [B][Tb][Kp] (dense, Kp even, 4-byte aligned; what ss_eval_mcep wrote, or any int16 whose differences fit
+ *   int16 and whose S stays below 2^31) -> c(i, j) = floor(sqrt(S(i, j))) as uint16 for every band cell, at ws_cost[(d mod Wd) * Ta + i] of the
+ *   item's plane, d = i + j, Wd = min(Tb, 2 band + 1). 64 x 64 tiles over all CUs, both operand tiles in LDS, packed int16 dot products.
+ * ss_eval_dtw: the warp over those costs. Band (centres c_i = ((2 i + 1) n_b) / (2 n_a), W, band <= 0 = full), the rule for an item that is not
+ *   aligned (n_b > W n_a, or an empty item: status 1) and INF are those of ss_contour_align, with a the score side and b the guide side.
+ *   D[0][0] = c(0, 0), D[i][j] = c(i, j) + min over existing cells, the FIRST minimum in the order DIAGONAL, UP, LEFT (not ss_contour_align's: with
+ *   up first, two stretches of identical frames give a path along the matrix edge and a path length that inflates the means taken over it).
+ *   path [B][Ta + Tb][2] int32: the (i, j) pairs from (0, 0) to (n_a - 1, n_b - 1) in forward order, plen[b] = P of them (what follows is
+ *   unspecified); cost[b] = D[n_a-1][n_b-1]; status[b] = 0. status 1: the identity (p, p) over min(n_a, n_b) frames, cost 0. One workgroup per
+ *   item, three rolling diagonals of D in LDS (14 Ta bytes), one direction byte per band cell in the workspace.
+ *   Workspace of both entries, the same pointer: 2 B Ta Wd bytes of costs, then B Ta Wd bytes of directions (ss_eval_dtw_workspace_bytes =
+ *   3 B Ta Wd; 0 for dims the entries refuse). Ta, Tb <= SS_EVAL_MAX_T; larger sizes are refused, never truncated.
+ * ss_eval_reduce: along path / plen (both NULL: the identity over min(n_a, n_b) frames), with f0 in Hz on the same grid (0 = unvoiced; row strides
+ *   ldfa, ldfb): counts [B][4] int64 = P, n_both (both voiced), n_vde (exactly one voiced), n_gpe (both voiced and fabsf(fa - fb) > 0.2f * fb, fp32,
+ *   no contraction); sums [B][2] float64 = sum sqrt((double) S), sum over the both-voiced cells of (1200 log2((double) fa / (double) fb))^2. S is
+ *   recomputed from q. One workgroup per item: thread t adds the cells p = t (mod 256) in ascending order, then a fixed tree: bit-identical
+ *   from run to run.
+ * ss_cosine_rows: out[r] = <a_r, b_r> / (|a_r| |b_r|) of rows of C floats, sums in float64 in a fixed order, 0 where a row is all zero. */
+#define SS_EVAL_MAX_T 8192
+#define SS_EVAL_MAX_K 64
+int ss_eval_mcep(const float* mel, int64_t ldm, int64_t mel_bs, const int32_t* lens, const float* tab, int16_t* q, int B, int T, int n_mels, int K,
+                 float s, float vmin, float vmax, void* stream);
+int64_t ss_eval_dtw_workspace_bytes(int B, int Ta, int Tb, int band);
+int ss_eval_cost_band(const int16_t* qa, const int32_t* lens_a, const int16_t* qb, const int32_t* lens_b, int Kp, int band, int Ta, int Tb, int B,
+                      void* ws, int64_t ws_bytes, void* stream);
+int ss_eval_dtw(const int32_t* lens_a, const int32_t* lens_b, int band, int32_t* path, int32_t* plen, int32_t* cost, int32_t* status, int Ta, int Tb,
+                int B, void* ws, int64_t ws_bytes, void* stream);
+int ss_eval_reduce(const int16_t* qa, const float* f0a, int64_t ldfa, const int32_t* lens_a, const int16_t* qb, const float* f0b, int64_t ldfb,
+                   const int32_t* lens_b, int Kp, const int32_t* path, const int32_t* plen, int Ta, int Tb, int B, int64_t* counts, double* sums,
+                   void* stream);
+int ss_cosine_rows(const float* a, const float* b, float* out, int rows, int C, void* stream);
+
 /* A song from separately rendered segments (StyleSingerInfer.sing_score; csrc/song.hip, restated on the host in tests/song_ref.py). The S segments
  * of a score are rows of ordinary batches, in an order chosen for batching; their frame counts are device values. Neither entry allocates or
  * synchronises: both are graph-capturable.

@@ -338,6 +338,24 @@ class StyleSingerInfer(ReferenceProducers):
         return song.sing_score(self, inp, max_seconds=max_seconds, segment_batch=segment_batch, fade_ms=fade_ms, in_flight=in_flight, seed=seed,
                                out_lufs=out_lufs, vad_flags=vad_flags, out_true_peak_db=out_true_peak_db)
 
+    @torch.no_grad()
+    def evaluate(self, res, target_wavs, target_lens, target_srs=None, align="dtw", band_s=2.0):
+        """Score what `infer_batch` (wav [B, L], lens = frames per item) or `sing_score` (wav [N]: one item) returned against target recordings
+        target_wavs [B, Lt] (target_lens valid samples, host ints; at the model's rate or at `target_srs`): `evaluate.score_wavs` on the rendered
+        waveform - the F0 frame error, the f0 RMSE in cents, the log-mel cepstral distortion along the DTW path (`align`, `band_s`; this project's
+        own definition, not SPTK / WORLD MCD) and, with a speaker encoder loaded, `singer_cos`. Reads `res['lens']` on the host (one sync)."""
+        from .evaluate import score_wavs
+        if res.get("wav") is None:
+            raise ValueError("evaluate: the result carries no 'wav' (infer_batch(vocode=False)?); score mels with evaluate.score_pairs")
+        wav = res["wav"]
+        if wav.dim() == 1:                               # sing_score: the song is one item
+            wav, lens = wav[None], [int(wav.numel())]
+        else:
+            hop = int(self.vocoder.model.hop)
+            lens = [min(int(v) * hop, int(wav.shape[1])) for v in res["lens"].cpu()]
+        tw = torch.as_tensor(target_wavs)
+        return score_wavs(self, wav, lens, tw[None] if tw.dim() == 1 else tw, target_lens, srs_b=target_srs, align=align, band_s=band_s)
+
     @classmethod
     def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, pitch=None, **ctor):
         """inference/StyleSinger.py:181-331: the example score (stylesinger_amd/example_input.json = that method's input dict, extracted by
