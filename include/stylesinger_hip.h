@@ -216,6 +216,16 @@ int64_t ss_split3_gemm16_elems(int Np, int Kp);
 int ss_wino43_conv(const ss_conv_gemm_args* args, int k, int dilation, void* stream);
 int ss_wino43_conv_ok(int C, int k, int dilation);
 int ss_wino43_conv_ok4(int Cin, int Cout, int k, int dilation);
+/* Grouped Winograd F(4,4) form of the same square conv for k = 7 | 11 (additive exports, ABI 20): the taps are split into ceil(k/4) groups of
+ * four (the last group zero padded at its end), each an F(4,4) product on the points {0, 1, -1, 2, -2, 1/2, inf}, seven accumulators over
+ * all groups: 14 / 21 matrix products per four output frames instead of the 18 / 24 of ss_wino43_conv. Same arguments, epilogue forms,
+ * input leaky-relu and zero-padding rule as ss_wino43_conv (no GELU epilogue), with W = ss_pack_conv_weight of the transformed taps
+ * [C][C][7*ceil(k/4)] (the 7 x 4 filter matrix per group, applied in float64 and rounded once: wino44_group_weight of the Python binding).
+ * Needs Cin == N == Np == Kp. ss_wino44_conv_ok: 1 where 7*ceil(k/4) < 6*ceil(k/3) (k = 7 | 11), dilation 1 | 3 | 5 and C a multiple of 32
+ * (multiples of 64 run 64-column tiles, the others - the C = 32 stage - 32-column tiles). The vocoder packs and runs F(4,4) exactly where
+ * this says 1. */
+int ss_wino44_conv(const ss_conv_gemm_args* args, int k, int dilation, void* stream);
+int ss_wino44_conv_ok(int C, int k, int dilation);
 /* Winograd F(2,3) form of the 3-tap dilated conv + SS_EPI_GATE epilogue (net.py:66-73): same arguments as the
  * direct call except that W is the TRANSFORMED weight packed as a 4-"tap" tensor (ss_wino_weight_transform then
  * ss_pack_conv_weight(k=4, interleave_half=C)) and the dilation is passed explicitly (power of two). 1.5x fewer
@@ -782,11 +792,13 @@ typedef struct ss_hifigan {
   const float* src_b; /* [1] */
   /* 1 = bf16-operand MFMA for conv_pre, the transposed convs and the residual blocks (conv_post and the NSF source stay fp32) */
   int32_t mfma_bf16;
-  /* 1 = ResBlock convs with a Winograd pack below run as grouped F(4,3) (ss_wino43_conv; fp32 mode, C a multiple of 32, k in {3,7,11},
-   * dilation in {1,3,5}); 0 / NULL pack = direct ss_conv_gemm. Same results to fp32 rounding (wav max error 1.3e-7 vs 0.9e-7 on the
-   * reference's golden cases, oracle/wino_vocoder_numerics.py) */
+  /* 1 = ResBlock convs with a Winograd pack below run as grouped F(4,4) where ss_wino44_conv_ok(C, k, d) says 1 (ss_wino44_conv: k in
+   * {7,11}) and as grouped F(4,3) otherwise (ss_wino43_conv: k = 3); fp32 mode, C a multiple of 32, dilation in {1,3,5}; 0 / NULL pack =
+   * direct ss_conv_gemm. Same results to fp32 rounding (F(4,3) form: wav max error 1.3e-7 vs 0.9e-7 on the reference's golden cases,
+   * oracle/wino_vocoder_numerics.py) */
   int32_t wino;
-  const float* w_rb1_wino[SS_HG_MAX_UPS][SS_HG_MAX_KERNELS][3]; /* ss_pack_conv_weight of the [C][C][6*ceil(k/3)] transformed taps */
+  /* ss_pack_conv_weight of the transformed taps: [C][C][7*ceil(k/4)] where ss_wino44_conv_ok says 1, else [C][C][6*ceil(k/3)] */
+  const float* w_rb1_wino[SS_HG_MAX_UPS][SS_HG_MAX_KERNELS][3];
   const float* w_rb2_wino[SS_HG_MAX_UPS][SS_HG_MAX_KERNELS][3];
 } ss_hifigan;
 

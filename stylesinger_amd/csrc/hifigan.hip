@@ -360,7 +360,8 @@ inline ss_conv_gemm_args base_args(int B, int T, const int32_t* lens) {
   return a;
 }
 
-// W_wino != NULL: the grouped Winograd F(4,3) kernel (fp32 mode; the caller checked ss_wino43_conv_ok). act_out = 1: leaky-relu(0.1)
+// W_wino != NULL: the grouped Winograd kernel (fp32 mode; the caller checked ss_wino43_conv_ok): F(4,4) groups where ss_wino44_conv_ok
+// covers the shape (k = 7 | 11), F(4,3) groups otherwise. act_out = 1: leaky-relu(0.1)
 // of the OUTPUT in the epilogue - the value is only ever read through the next conv's input leaky-relu, which then passes lrelu = 1.
 int conv_same(const float* A, int B, int Trows, int C, const int32_t* lens, const float* W, const float* W_wino, const float* bias, int k,
               int d, float lrelu, int act_out, const float* R, float post_scale, int accumulate, float* out, int bf16, hipStream_t stream) {
@@ -394,6 +395,8 @@ int conv_same(const float* A, int B, int Trows, int C, const int32_t* lens, cons
   // 32-bit byte offsets inside an item: longer items take the direct kernel ("voc_wino_max_mb" knob, default 2048 MiB = the real limit)
   if (W_wino && ((int64_t)Trows + 1024) * C * 4 < ((int64_t)g_ss_tuning.voc_wino_max_mb << 20)) {
     a.W = W_wino;
+    // the pack (vocoder.py) holds F(4,4) tap groups exactly where ss_wino44_conv_ok says 1, F(4,3) groups elsewhere: one rule on both sides
+    if (ss_wino44_conv_ok(C, k, d)) return ss_wino44_conv(&a, k, d, stream);
     return ss_wino43_conv(&a, k, d, stream);
   }
   return ss_conv_gemm(&a, stream);

@@ -234,6 +234,43 @@ def wino43_conv(A, W, out, *, k, dilation, **kw):
     return out
 
 
+# F(4,4) on the points {0, 1, -1, 2, -2, 1/2, inf}: the 7 x 4 filter matrix (row j = p_j^i / prod_{l != j} (p_j - p_l); last row = the point at
+# infinity). Its partners are the input transform of csrc/wino44_conv.hip and the power-of-two output transform in its header comment.
+WINO44_G = (
+    (-1 / 2, 0.0, 0.0, 0.0),
+    (-1 / 3, -1 / 3, -1 / 3, -1 / 3),
+    (1 / 9, -1 / 9, 1 / 9, -1 / 9),
+    (1 / 36, 1 / 18, 1 / 9, 2 / 9),
+    (-1 / 60, 1 / 30, -1 / 15, 2 / 15),
+    (32 / 45, 16 / 45, 8 / 45, 4 / 45),
+    (0.0, 0.0, 0.0, 1.0),
+)
+
+
+def wino44_conv_ok(C, k, dilation):
+    """1 where the square ResBlock conv (C, k, dilation) runs as F(4,4) tap groups (ss_wino44_conv_ok): the one rule of pack and forward."""
+    return int(load().ss_wino44_conv_ok(int(C), int(k), int(dilation)))
+
+
+def wino44_group_weight(w):
+    """conv weight [Cout][Cin][k] (device) -> [Cout][Cin][7 * ceil(k/4)]: the taps in groups of four (zero padded at the end), every group
+    F(4,4)-transformed in float64 and rounded once - the B operand of ss_wino44_conv after ss_pack_conv_weight."""
+    Cout, Cin, k = w.shape
+    G = (k + 3) // 4
+    wp = torch.zeros(Cout, Cin, G, 4, device=w.device, dtype=torch.float64)
+    wp.view(Cout, Cin, 4 * G)[..., :k] = w.double()
+    g = torch.tensor(WINO44_G, device=w.device, dtype=torch.float64)
+    return torch.einsum("jt,oigt->oigj", g, wp).reshape(Cout, Cin, 7 * G).float().contiguous()
+
+
+def wino44_conv(A, W, out, *, k, dilation, **kw):
+    """Grouped Winograd F(4,4) conv (ss_wino44_conv, k = 7 | 11); keyword arguments as conv_gemm (taps are implied by k and dilation)."""
+    taps = [(j - (k - 1) // 2) * dilation for j in range(k)]
+    a = _fill_args(A, W, out, taps=taps, **kw)
+    check(load().ss_wino44_conv(C.byref(a), k, dilation, stream_ptr()), "ss_wino44_conv")
+    return out
+
+
 def split3_weights(Wp, Kp):
     """packed F(4,3) weights [Np][6 * Kp] fp32 -> Np * 18 * Kp bf16: every element as its three bf16 terms, in the fetch order of
     ss_wino43_gate16x ([n tile][wave][K chunk][component][plane][lane][8])."""

@@ -137,7 +137,7 @@ class HifiGanGeneratorHIP(torch.nn.Module):
         hg.sr, hg.harmonics = h["audio_sample_rate"], h["harmonic_num"]
         import os
         hg.mfma_bf16 = 1 if os.environ.get("SS_PRECISION", h.get("mfma_precision", "fp32")) == "bf16" else 0
-        # grouped Winograd F(4,3) ResBlock convs (fp32 mode; SS_VOC_WINO=0 keeps the direct convs)
+        # grouped Winograd ResBlock convs: F(4,4) for k = 7 / 11, F(4,3) for k = 3 (fp32 mode; SS_VOC_WINO=0 keeps the direct convs)
         hg.wino = 1 if (not hg.mfma_bf16 and os.environ.get("SS_VOC_WINO", str(h.get("vocoder_wino", 1))) != "0") else 0
         lib = L.load()
         for i, (u, k) in enumerate(zip(rates, ks)):
@@ -152,6 +152,9 @@ class HifiGanGeneratorHIP(torch.nn.Module):
         def hold(t):
             keep.append(t)
             return t.data_ptr()
+
+        def wino_group(c, k, d):   # F(4,4) tap groups where ss_wino44_conv_ok says so (the rule conv_same of hifigan.hip runs by), else F(4,3)
+            return L.wino44_group_weight if L.wino44_conv_ok(c, k, d) else L.wino43_group_weight
 
         v, s0 = self._wn("conv_pre")
         hg.w_pre = hold(L.pack_conv_weight(v, scale0=s0))
@@ -172,13 +175,13 @@ class HifiGanGeneratorHIP(torch.nn.Module):
                     v, s0 = self._wn(f"{pfx}.convs1.{m}")
                     hg.w_rb1[i][j][m] = hold(L.pack_conv_weight(v, scale0=s0))
                     hg.b_rb1[i][j][m] = hold(L.pack_bias(self.p(f"{pfx}.convs1.{m}.bias")))
-                    if hg.wino and lib.ss_wino43_conv_ok(cout, k, d):   # grouped F(4,3) pack of the folded weight
-                        hg.w_rb1_wino[i][j][m] = hold(L.pack_conv_weight(L.wino43_group_weight(v * s0.view(-1, 1, 1))))
+                    if hg.wino and lib.ss_wino43_conv_ok(cout, k, d):   # grouped Winograd pack of the folded weight
+                        hg.w_rb1_wino[i][j][m] = hold(L.pack_conv_weight(wino_group(cout, k, d)(v * s0.view(-1, 1, 1))))
                     v, s0 = self._wn(f"{pfx}.convs2.{m}")
                     hg.w_rb2[i][j][m] = hold(L.pack_conv_weight(v, scale0=s0))
                     hg.b_rb2[i][j][m] = hold(L.pack_bias(self.p(f"{pfx}.convs2.{m}.bias")))
                     if hg.wino and lib.ss_wino43_conv_ok(cout, k, 1):
-                        hg.w_rb2_wino[i][j][m] = hold(L.pack_conv_weight(L.wino43_group_weight(v * s0.view(-1, 1, 1))))
+                        hg.w_rb2_wino[i][j][m] = hold(L.pack_conv_weight(wino_group(cout, k, 1)(v * s0.view(-1, 1, 1))))
         v, s0 = self._wn("conv_post")
         hg.w_post = hold((v * s0.view(-1, 1, 1)).contiguous())  # 1 x c_last x 7 filter, consumed raw by conv_post_kernel
         hg.b_post = hold(self.p("conv_post.bias").contiguous())

@@ -186,6 +186,12 @@ def main():
                                            R=X, ldr=C)
                 s = timeit(fw, max(3, a.iters // 5))
                 res.append((f"voc C={C} rows={rows} k={k} grouped F(4,3)", s, 2.0 * B * rows * C * C * k))
+            if L.wino44_conv_ok(C, k, 3):          # and as grouped F(4,4): what the vocoder runs for k = 7 / 11
+                W4 = L.pack_conv_weight(L.wino44_group_weight(w))
+                f4 = lambda: L.wino44_conv(X, W4, Y, k=k, dilation=3, B=B, T=rows, Cin=C, N=C, Np=C, Kp=C, lens=ln, a_lrelu=0.1, bias=bias,
+                                           R=X, ldr=C)
+                s = timeit(f4, max(3, a.iters // 5))
+                res.append((f"voc C={C} rows={rows} k={k} grouped F(4,4)", s, 2.0 * B * rows * C * C * k))
     for name, s, fl in res:
         print(f"{name:52s} {s * 1e6:9.1f} us  {fl / s / 1e12:7.2f} TF/s  ({fl / s / 157.3e12 * 100:5.1f}% of fp32 MFMA peak)")
 
