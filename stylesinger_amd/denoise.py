@@ -118,6 +118,6 @@ def denoise_batch(wav, lens_samples, n_fft, hop, win, v):
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8) if ws_bytes else None
     y = torch.empty(B, Ly, device=dev, dtype=torch.float32)
     n_out = torch.empty(B, device=dev, dtype=torch.int32)
-    L.check(lib.ss_wav_denoise(L.ptr(x), x.stride(0), Lx, L.ptr(n), L.ptr(y), Ly, Ly, L.ptr(n_out), B, n_fft, hop, v,
-                               L.ptr(device_table(n_fft, dev)), L.ptr(ws), ws_bytes, L.stream_ptr()), "ss_wav_denoise")
+    table = L.ptr(device_table(n_fft, dev))   # a byte buffer (float64 table, then its float32 copy) behind the `const double*`: by address, the cache owns it
+    L.ops.ss_wav_denoise(x, x.stride(0), Lx, n, y, Ly, Ly, n_out, B, n_fft, hop, v, table, ws, ws_bytes)
     return (y if Lx >= hop else y[:, :0]), n_out

@@ -85,7 +85,6 @@ class EmotionEncoderHIP:
     def embed_frames_batch(self, frames):
         """frames [P, n_frames, 40] (device or host) -> partial embeddings [P, 256] = final hidden state of the last layer
         (EmotionEncoder.inference, model.py:62-78, as inference.embed_frames_batch :39-53 calls it)."""
-        lib = L.load()
         x = torch.as_tensor(frames, dtype=torch.float32).to(self.device).contiguous()
         P, n, _ = x.shape
         H = self.H
@@ -95,8 +94,7 @@ class EmotionEncoderHIP:
             L.conv_gemm(x, pk["W"], xproj, B=P, T=n, Cin=pk["cin"], N=4 * H, Np=pk["Np"], Kp=pk["Kp"], bias=pk["bias"], mask_rows=False)
             last = l + 1 == self.layers
             h_seq = None if last else torch.empty(P, n, H, device=self.device)
-            L.check(lib.ss_lstm_layer(L.ptr(xproj), L.ptr(pk["whh"]), L.ptr(h_seq), L.ptr(h_last) if last else None, P, n, H,
-                                      L.stream_ptr()), "ss_lstm_layer")
+            L.ops.ss_lstm_layer(xproj, pk["whh"], h_seq, h_last if last else None, P, n, H)
             x = h_seq
         return h_last
 
@@ -105,7 +103,7 @@ class EmotionEncoderHIP:
         """-> (embed [256], partial_embeds [P,256]): embed_utterance's tail (inference.py:139-151)."""
         part = self.embed_frames_batch(frames)
         out = torch.empty(self.H, device=self.device)
-        L.check(L.load().ss_mean_l2norm(L.ptr(part), L.ptr(out), part.shape[0], self.H, L.stream_ptr()), "ss_mean_l2norm")
+        L.ops.ss_mean_l2norm(part, out, part.shape[0], self.H)
         return out, part
 
     @torch.no_grad()
@@ -125,14 +123,13 @@ class EmotionEncoderHIP:
     @torch.no_grad()
     def forward(self, frames):
         """EmotionEncoder.forward (model.py:40-60): relu(linear(h_last)) L2-normalised per row."""
-        lib = L.load()
         h = self.embed_frames_batch(frames)
         P = h.shape[0]
         e = torch.empty(P, self.E, device=self.device)
         L.conv_gemm(h, self._lin["W"], e, B=1, T=P, Cin=self.H, N=self.E, Np=self._lin["Np"], Kp=self._lin["Kp"], bias=self._lin["bias"],
                     act=L.ACT_RELU, mask_rows=False)
         out = torch.empty_like(e)
-        L.check(lib.ss_l2norm_rows(L.ptr(e), L.ptr(out), P, self.E, L.stream_ptr()), "ss_l2norm_rows")
+        L.ops.ss_l2norm_rows(e, out, P, self.E)
         return out
 
     __call__ = forward

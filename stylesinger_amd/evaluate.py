@@ -269,8 +269,7 @@ def mcep_q_device(mel, frames=None, hparams=None, K=EVAL_K):
     if B * T == 0:
         return q
     n = None if frames is None else _lens(frames, B, T, x.device)
-    L.check(L.load().ss_eval_mcep(L.ptr(x), x.stride(1), x.stride(0), L.ptr(n), L.ptr(_table(N, K, x.device)), L.ptr(q), B, T, N, int(K), EVAL_SCALE,
-                                  vmin, vmax, L.stream_ptr()), "ss_eval_mcep")
+    L.ops.ss_eval_mcep(x, x.stride(1), x.stride(0), n, _table(N, K, x.device), q, B, T, N, int(K), EVAL_SCALE, vmin, vmax)
     if n is not None:
         n.record_stream(torch.cuda.current_stream(x.device))
     return q
@@ -303,9 +302,8 @@ def align_device(qa, lens_a, qb, lens_b, band=None):
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
     path = torch.empty(B, Ta + Tb, 2, device=dev, dtype=torch.int32)
     plen, cost, status = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
-    L.check(lib.ss_eval_cost_band(L.ptr(qa), L.ptr(la), L.ptr(qb), L.ptr(lb), Kp, band, Ta, Tb, B, L.ptr(ws), ws_bytes, L.stream_ptr()), "ss_eval_cost_band")
-    L.check(lib.ss_eval_dtw(L.ptr(la), L.ptr(lb), band, L.ptr(path), L.ptr(plen), L.ptr(cost), L.ptr(status), Ta, Tb, B, L.ptr(ws), ws_bytes,
-                            L.stream_ptr()), "ss_eval_dtw")
+    L.ops.ss_eval_cost_band(qa, la, qb, lb, Kp, band, Ta, Tb, B, ws, ws_bytes)
+    L.ops.ss_eval_dtw(la, lb, band, path, plen, cost, status, Ta, Tb, B, ws, ws_bytes)
     ws.record_stream(torch.cuda.current_stream(dev))
     return dict(path=path, plen=plen, cost=cost, status=status, lens_a=la, lens_b=lb)
 
@@ -327,8 +325,7 @@ def reduce_device(qa, f0_a, lens_a, qb, f0_b, lens_b, path=None, plen=None):
     la, lb = _lens(lens_a, B, Ta, dev), _lens(lens_b, B, Tb, dev)
     counts = torch.empty(B, 4, device=dev, dtype=torch.int64)
     sums = torch.empty(B, 2, device=dev, dtype=torch.float64)
-    L.check(L.load().ss_eval_reduce(L.ptr(qa), L.ptr(fa), fa.stride(0), L.ptr(la), L.ptr(qb), L.ptr(fb), fb.stride(0), L.ptr(lb), Kp, L.ptr(path),
-                                    L.ptr(plen), Ta, Tb, B, L.ptr(counts), L.ptr(sums), L.stream_ptr()), "ss_eval_reduce")
+    L.ops.ss_eval_reduce(qa, fa, fa.stride(0), la, qb, fb, fb.stride(0), lb, Kp, path, plen, Ta, Tb, B, counts, sums)
     for t in (la, lb):
         t.record_stream(torch.cuda.current_stream(dev))
     return counts, sums
@@ -342,7 +339,7 @@ def cosine_rows_device(a, b):
     if a.dim() != 2 or a.shape != b.shape:
         raise ValueError(f"cosine_rows_device: {tuple(a.shape)} against {tuple(b.shape)}")
     out = torch.empty(a.shape[0], device=a.device, dtype=torch.float32)
-    L.check(L.load().ss_cosine_rows(L.ptr(a), L.ptr(b), L.ptr(out), a.shape[0], a.shape[1], L.stream_ptr()), "ss_cosine_rows")
+    L.ops.ss_cosine_rows(a, b, out, a.shape[0], a.shape[1])
     return out
 
 

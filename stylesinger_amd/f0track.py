@@ -125,7 +125,6 @@ def track_f0_device(wavs, n_samples, n_out, sr=48000, hop_size=256, pitch_floor=
     # the next one - before the kernels read them)
     meta = torch.tensor([ns, [nf for nf, _ in grid], [lf for _, lf in grid]], dtype=torch.int32).to(dev)
     out = torch.empty(B, int(n_out), device=dev, dtype=torch.float32)
-    import ctypes
     # The workspace holds the float64 autocorrelation of every frame (max_frames x (nlag + 1) x 8 B per item: 40 MB for a 30 s item). A batch is
     # tracked in groups of items whose workspace stays below WS_CAP_BYTES - 32 x 30 s would otherwise ask for 1.3 GB at once; items are independent,
     # so the grouping changes nothing but the peak allocation (the same kernels, the same per-item arithmetic).
@@ -134,8 +133,7 @@ def track_f0_device(wavs, n_samples, n_out, sr=48000, hop_size=256, pitch_floor=
     ws = torch.empty(lib.ss_f0track_workspace_bytes(group, max_frames, g["nlag"]), device=dev, dtype=torch.uint8)
     for b0 in range(0, B, group):
         nb = min(group, B - b0)
-        L.check(lib.ss_f0track(L.ptr(wavs[b0:]), wavs.shape[1], L.ptr(meta[0, b0:]), L.ptr(meta[1, b0:]), L.ptr(meta[2, b0:]), nb,
-                               max_frames, ctypes.byref(prm), L.ptr(win), L.ptr(win_r), L.ptr(out[b0:]), int(n_out), lpad, L.ptr(ws), ws.numel(),
-                               L.stream_ptr()), "ss_f0track")
+        L.ops.ss_f0track(wavs[b0:], wavs.shape[1], meta[0, b0:], meta[1, b0:], meta[2, b0:], nb, max_frames, prm, win, win_r, out[b0:], int(n_out),
+                         lpad, ws, ws.numel())
     meta.record_stream(torch.cuda.current_stream(dev))
     return out

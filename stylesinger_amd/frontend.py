@@ -96,11 +96,10 @@ class MelFrontendHIP:
             wav = torch.nn.functional.pad(wav, (0, R * hop - Ls))
         wav = wav.contiguous()
         n = torch.full((B,), Ls, device=self.device, dtype=torch.int64) if lens is None else lens.to(self.device).to(torch.int64)
-        lib = L.load()
         if lens is not None:  # samples past an item's length are not part of it: zeroed (the row-mask kernel on the [B][R * hop][1] view)
             n32 = n.to(torch.int32).contiguous()
             masked = torch.empty_like(wav)
-            L.check(lib.ss_add_bcast_mask(L.ptr(wav), None, None, None, None, L.ptr(masked), B, R * hop, 1, L.ptr(n32), L.stream_ptr()), "wav mask")
+            L.ops.ss_add_bcast_mask(wav, None, None, None, None, masked, B, R * hop, 1, n32)
             wav = masked
         rows = ((n + hop - 1) // hop).to(torch.int32)
         frames = (n // hop + 1).to(torch.int32)
@@ -109,13 +108,13 @@ class MelFrontendHIP:
         L.conv_gemm(wav, self.W_dft, S, B=B, T=T, Cin=hop, N=2 * self.nb_pad, Np=self.W_dft.shape[0], Kp=self.W_dft.shape[1] // taps,
                     lda=hop, a_bs=R * hop, taps=tuple(j - taps // 2 for j in range(taps)), lens=rows, mask_rows=False)
         P = torch.empty(B, T, self.nb_pad, device=self.device, dtype=torch.float32)
-        L.check(lib.ss_spec_magnitude(L.ptr(S), L.ptr(P), B * T, 2 * self.nb_pad, self.nb_pad, self.nbins, self.nb_pad, L.stream_ptr()), "mag")
+        L.ops.ss_spec_magnitude(S, P, B * T, 2 * self.nb_pad, self.nb_pad, self.nbins, self.nb_pad)
         mel = torch.empty(B, T, self.n_mels, device=self.device, dtype=torch.float32)
         L.conv_gemm(P, self.W_mel, mel, B=B, T=T, Cin=self.nb_pad, N=self.n_mels, Np=self.W_mel.shape[0], Kp=self.W_mel.shape[1],
                     mask_rows=False)
-        L.check(lib.ss_log10_floor(L.ptr(mel), L.ptr(mel), mel.numel(), self.eps, L.stream_ptr()), "log10")
+        L.ops.ss_log10_floor(mel, mel, mel.numel(), self.eps)
         frames = frames.contiguous()
-        L.check(lib.ss_add_bcast_mask(L.ptr(mel), None, None, None, None, L.ptr(mel), B, T, self.n_mels, L.ptr(frames), L.stream_ptr()), "mel mask")
+        L.ops.ss_add_bcast_mask(mel, None, None, None, None, mel, B, T, self.n_mels, frames)
         return mel, frames
 
 
@@ -158,8 +157,7 @@ class EmotionMelFrontendHIP:
         wav = wav.to(self.device).float().contiguous()
         out = torch.empty_like(wav)
         n = torch.as_tensor(lens).to(device=self.device, dtype=torch.int32).contiguous()
-        L.check(L.load().ss_normalize_volume(L.ptr(wav), L.ptr(n), L.ptr(out), wav.shape[0], wav.shape[1], float(target_dbfs), L.stream_ptr()),
-                "ss_normalize_volume")
+        L.ops.ss_normalize_volume(wav, n, out, wav.shape[0], wav.shape[1], float(target_dbfs))
         n.record_stream(torch.cuda.current_stream(self.device))
         return out
 
@@ -177,15 +175,14 @@ class EmotionMelFrontendHIP:
         T = 1 + max(lens_h) // hop
         rows = T + taps - 1
         Ly = rows * hop
-        lib = L.load()
         yp = torch.empty(B, Ly, device=self.device, dtype=torch.float32)
-        L.check(lib.ss_reflect_pad(L.ptr(wav), L.ptr(lens_d), L.ptr(yp), B, Lx, Ly, n_fft // 2, L.stream_ptr()), "ss_reflect_pad")
+        L.ops.ss_reflect_pad(wav, lens_d, yp, B, Lx, Ly, n_fft // 2)
         S = torch.empty(B, T, 2 * self.nb_pad, device=self.device, dtype=torch.float32)
         L.conv_gemm(yp, self.W_dft, S, B=B, T=T, Cin=hop, N=2 * self.nb_pad, Np=self.W_dft.shape[0], Kp=self.W_dft.shape[1] // taps,
                     lda=hop, a_bs=Ly, taps=tuple(range(taps)), lens=torch.full((B,), rows, device=self.device, dtype=torch.int32),
                     mask_rows=False)
         P = torch.empty(B, T, self.nb_pad, device=self.device, dtype=torch.float32)
-        L.check(lib.ss_spec_power(L.ptr(S), L.ptr(P), B * T, 2 * self.nb_pad, self.nb_pad, self.nbins, self.nb_pad, L.stream_ptr()), "ss_spec_power")
+        L.ops.ss_spec_power(S, P, B * T, 2 * self.nb_pad, self.nb_pad, self.nbins, self.nb_pad)
         mel = torch.empty(B, T, self.N_MELS, device=self.device, dtype=torch.float32)
         L.conv_gemm(P, self.W_mel, mel, B=B, T=T, Cin=self.nb_pad, N=self.N_MELS, Np=self.W_mel.shape[0], Kp=self.W_mel.shape[1],
                     mask_rows=False)

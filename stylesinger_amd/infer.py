@@ -260,7 +260,7 @@ class StyleSingerInfer(ReferenceProducers):
         the song then holds what single `spec2wav` calls would return."""
         hp = self.hparams
         mel_c = torch.empty_like(mel)
-        L.check(L.load().ss_clip(L.ptr(mel), L.ptr(mel_c), mel.numel(), float(hp["mel_vmin"]), float(hp["mel_vmax"]), L.stream_ptr()), "ss_clip")
+        L.ops.ss_clip(mel, mel_c, mel.numel(), float(hp["mel_vmin"]), float(hp["mel_vmax"]))
         return self.vocoder.spec2wav_batch(mel_c, f0, lens=lens, noise=noise, seed=seed)
 
     @torch.no_grad()

@@ -3,10 +3,18 @@
 The product path has NO fallback: if the shared library is missing or a symbol cannot be resolved this
 module raises, and every op raises `StyleSingerHipError` on a non-zero status.  PyTorch is used only
 for device memory (`tensor.data_ptr()`) and streams.
+
+Two paths lead to the library. `ops.ss_x(...)`, one callable per prototype that ends in the stream (everything that launches):
+tensors, host arrays and argument structs are passed as they are and checked against the pointee the header declares, so a
+wrong dtype, a host tensor or a wrong argument count is an exception naming function and parameter BEFORE any launch; the
+current stream is supplied when left out; a plain int is a raw address and the one explicit way to reinterpret memory.
+`load().ss_x(...)` is raw ctypes, for the functions that answer queries and launch nothing (`_ok` / `_pick` rules,
+`*_workspace_bytes`, `ss_set_tuning`, host tables), and for tests and tools that pin the raw ABI.
 """
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import abi
@@ -60,6 +68,9 @@ def load():
         if C.sizeof(abi.STRUCTURES[name]) != c_size:
             raise StyleSingerHipError(f"{name}: {C.sizeof(abi.STRUCTURES[name])} bytes as read from include/stylesinger_hip.h, {c_size} in libstylesinger_hip.so: rebuild it")
     _lib = lib
+    for name, proto in abi.PROTOTYPES.items():
+        if proto.launch:
+            setattr(ops, name, _op(proto))
     for env, key in (("SS_GATE16", b"gate16"), ("SS_GATE16_KS", b"gate16_ks"), ("SS_GATE256", b"gate256"), ("SS_MEL_TAIL", b"mel_tail"), ("SS_GATE128", b"gate128"),
                      ("SS_Q4_FORCE", b"q4_force"), ("SS_SKIP_DENSE", b"skip_dense"), ("SS_LAYER512", b"layer512"), ("SS_LAYER512_TAIL", b"layer512_tail")):
         val = os.environ.get(env)
@@ -82,7 +93,8 @@ def ptr(t):
     """Device pointer of a torch tensor (or None) as a plain int."""
     if t is None:
         return None
-    assert t.is_cuda, "HIP path needs device tensors"
+    if not t.is_cuda:
+        raise StyleSingerHipError("HIP path needs device tensors")
     return t.data_ptr()
 
 
@@ -91,8 +103,101 @@ def hptr(a):
     return a.ctypes.data
 
 
-def _f(x):
-    return float(x)
+# ---------------------------------------------------------------------------------------------
+# checked marshalling: what a pointer of the header may be handed (ops.* and the pointer members of the argument structs)
+# ---------------------------------------------------------------------------------------------
+_ANY = None   # void*: every dtype
+_TORCH_DTYPES = {"float": {torch.float32}, "double": {torch.float64}, "int32_t": {torch.int32}, "int": {torch.int32}, "int64_t": {torch.int64},
+                 "int16_t": {torch.int16}, "uint8_t": {torch.uint8}, "char": {torch.uint8, torch.int8},
+                 "uint16_t": {torch.bfloat16, torch.float16, torch.int16, torch.uint16},
+                 "uint64_t": {torch.int64, torch.uint64},   # the plans' `seed` word is int64
+                 "void": _ANY}
+_NUMPY_DTYPES = {k: v if v is _ANY else {str(d).split(".")[1] for d in v} for k, v in _TORCH_DTYPES.items()}
+_Tensor = torch.Tensor
+
+
+def _refuse(fn, param, pointee, got):
+    return TypeError(f"{fn}: parameter '{param}' is a `{pointee}*` and cannot take {got}")
+
+
+def _address(a, pointee, fn, param):
+    """What ctypes is handed for the `pointee*` parameter (or struct member) `param` of `fn`; everything the pointee rules out raises here."""
+    if a is None or type(a) is int:   # NULL; a raw address (address arithmetic, deliberate reinterpretation) goes through untouched
+        return a
+    if type(a) is _Tensor or isinstance(a, _Tensor):
+        ok = _TORCH_DTYPES.get(pointee, ())
+        if ok is not _ANY and a.dtype not in ok:
+            raise _refuse(fn, param, pointee, f"a {a.dtype} tensor")
+        if not a.is_cuda:
+            raise StyleSingerHipError(f"{fn}: parameter '{param}' needs device tensors")
+        return a.data_ptr()
+    if isinstance(a, np.ndarray):   # a host pointer
+        ok = _NUMPY_DTYPES.get(pointee, ())
+        if ok is not _ANY and a.dtype.name not in ok:
+            raise _refuse(fn, param, pointee, f"a {a.dtype.name} array")
+        if not a.flags.c_contiguous:
+            raise _refuse(fn, param, pointee, "an array that is not C-contiguous")
+        return a.ctypes.data
+    if isinstance(a, C.Structure):
+        if type(a) is not abi.STRUCTURES.get(pointee):
+            raise _refuse(fn, param, pointee, f"a {type(a).__name__} struct")
+        return C.byref(a)
+    if type(a) is bytes and pointee == "char":
+        return a
+    raise _refuse(fn, param, pointee, f"{type(a).__name__} {a!r}")
+
+
+def member_address(struct, field, v):
+    """The checked address of tensor `v` for pointer member `field` of the ctypes struct `struct` (the caller keeps `v` alive)."""
+    name = type(struct).__name__
+    return _address(v, abi.STRUCT_POINTEES[name][field], name, field)
+
+
+def set_members(struct, **members):
+    """struct.field = tensor | None | raw address for pointer members, each checked against the member's declaration in the header."""
+    for field, v in members.items():
+        setattr(struct, field, member_address(struct, field, v))
+
+
+def _op(proto, fn=None):
+    """The checked callable of one launch prototype: pointers marshalled by _address, the stream supplied where it is left out, status raised.
+    The entry point is looked up on load() at every call, like every other use of the library (fn: a stand-in, for tests)."""
+    name, n = proto.name, len(proto.params)
+    pointers = tuple((i, p.pointee, p.name) for i, p in enumerate(proto.params) if p.pointee)
+
+    def op(*args):
+        if not n - 1 <= len(args) <= n:
+            raise TypeError(f"{name} takes {n - 1} arguments and, optionally, the stream ({len(args)} given): {proto.text}")
+        a = list(args)
+        if len(a) < n:   # None holds the stream's place until every other argument has passed
+            a.append(None)
+        for i, pointee, param in pointers:
+            v = a[i]
+            if v is not None:
+                a[i] = _address(v, pointee, name, param)
+        if len(args) < n:
+            a[-1] = stream_ptr()
+        rc = (fn or getattr(load(), name))(*a)
+        if rc != 0:
+            raise StyleSingerHipError(f"{name} failed ({rc}): {load().ss_last_error().decode(errors='replace')}")
+    op.__name__ = op.__qualname__ = name
+    op.__doc__ = proto.text
+    return op
+
+
+class _Ops:
+    """One checked callable per prototype that ends in the stream; filled by load()."""
+
+    def __getattr__(self, name):   # reached only for what load() has not put here
+        if _lib is None:
+            load()
+            return getattr(self, name)
+        if name in abi.PROTOTYPES:
+            raise AttributeError(f"{name} takes no stream, so it launches nothing and is not in ops: call it as load().{name}(...)")
+        raise AttributeError(f"include/stylesinger_hip.h declares no {name}")
+
+
+ops = _Ops()
 
 
 def round_up(x, m):
@@ -100,11 +205,11 @@ def round_up(x, m):
 
 
 # ---------------------------------------------------------------------------------------------
-# thin op wrappers (argument marshalling only)
+# thin op wrappers (defaults and argument structs; the marshalling is ops' and set_members')
 # ---------------------------------------------------------------------------------------------
 def conv_gemm(A, W, out, **kw):
     a = _fill_args(A, W, out, **kw)
-    check(load().ss_conv_gemm(C.byref(a), stream_ptr()), "ss_conv_gemm")
+    ops.ss_conv_gemm(a)
 
 
 def _fill_args(A, W, out, *, B, T, Cin, N, Np, Kp, lda=None, a_bs=None, taps=(0,), lens=None, a_bias=None, a_scale=1.0,
@@ -112,20 +217,21 @@ def _fill_args(A, W, out, *, B, T, Cin, N, Np, Kp, lda=None, a_bs=None, taps=(0,
                gate_mode=0, R=None, ldr=0, r_bs=None, post_scale=1.0, accumulate=False, mask_rows=True, ldc=None, c_bs=None,
                C2=None, ldc2=0, c2_bs=0, Nh=0, tile=0, group_size=0, w_gs=0, bias_gs=0, a_bias_gs=0, bf16=False, e_tiled=False):
     a = ConvGemmArgs()
-    a.A = ptr(A); a.lda = lda if lda is not None else Cin
+    set_members(a, A=A, lens=lens, a_bias=a_bias, W=W, bias=bias, E=E, R=R, C=out, C2=C2)
+    a.lda = lda if lda is not None else Cin
     a.a_batch_stride = a_bs if a_bs is not None else T * a.lda
     a.Cin = Cin; a.ntaps = len(taps)
     for i, o in enumerate(taps):
         a.tap_off[i] = int(o)
-    a.lens = ptr(lens); a.B = B; a.T = T; a.a_bias = ptr(a_bias); a.a_scale = a_scale; a.a_lrelu = a_lrelu
-    a.W = ptr(W); a.N = N; a.Np = Np; a.Kp = Kp
-    a.epi = epi; a.bias = ptr(bias); a.pre_scale = pre_scale; a.act = act; a.act_slope = act_slope
-    a.E = ptr(E); a.lde = lde; a.e_batch_stride = e_bs; a.gate_mode = gate_mode
-    a.R = ptr(R); a.ldr = ldr; a.r_batch_stride = r_bs if r_bs is not None else T * ldr
+    a.B = B; a.T = T; a.a_scale = a_scale; a.a_lrelu = a_lrelu
+    a.N = N; a.Np = Np; a.Kp = Kp
+    a.epi = epi; a.pre_scale = pre_scale; a.act = act; a.act_slope = act_slope
+    a.lde = lde; a.e_batch_stride = e_bs; a.gate_mode = gate_mode
+    a.ldr = ldr; a.r_batch_stride = r_bs if r_bs is not None else T * ldr
     a.post_scale = post_scale; a.accumulate = int(accumulate); a.mask_rows = int(mask_rows)
-    a.C = ptr(out); a.ldc = ldc if ldc is not None else N
+    a.ldc = ldc if ldc is not None else N
     a.c_batch_stride = c_bs if c_bs is not None else T * a.ldc
-    a.C2 = ptr(C2); a.ldc2 = ldc2; a.c2_batch_stride = c2_bs; a.Nh = Nh; a.tile = tile
+    a.ldc2 = ldc2; a.c2_batch_stride = c2_bs; a.Nh = Nh; a.tile = tile
     a.group_size = group_size; a.w_group_stride = w_gs; a.bias_group_stride = bias_gs; a.a_bias_group_stride = a_bias_gs
     a.mfma_bf16 = 1 if bf16 else 0
     a.e_tiled = 1 if e_tiled else 0
@@ -136,7 +242,7 @@ def gate16_tile_addend(E, *, B, T, Np, lde, e_bs, dilation, mt):
     """E (this layer's Np packed columns, row stride lde) -> the addend in the 16x16x4 gate kernel's fetch order (ss_gate16_tile_addend)."""
     n = load().ss_gate16_tiled_floats(B, T, Np, int(dilation), int(mt))
     out = torch.empty(n, device=E.device, dtype=torch.float32)
-    check(load().ss_gate16_tile_addend(ptr(E), lde, e_bs, ptr(out), B, T, Np, int(dilation), int(mt), stream_ptr()), "ss_gate16_tile_addend")
+    ops.ss_gate16_tile_addend(E, lde, e_bs, out, B, T, Np, int(dilation), int(mt))
     return out
 
 
@@ -144,21 +250,21 @@ def wino_gate(A, Wt, out, *, dilation, **kw):
     """Winograd F(2,3) dilated conv + gate (ss_wino_gate); Wt = packed transformed weights (4 'taps')."""
     kw.setdefault("epi", EPI_GATE)
     a = _fill_args(A, Wt, out, **kw)
-    check(load().ss_wino_gate(C.byref(a), int(dilation), stream_ptr()), "ss_wino_gate")
+    ops.ss_wino_gate(a, int(dilation))
 
 
 def wino43_gate(A, Wt, out, *, dilation, **kw):
     """Winograd F(4,3) dilated conv + gate (ss_wino43_gate); Wt = packed transformed weights (6 'taps')."""
     kw.setdefault("epi", EPI_GATE)
     a = _fill_args(A, Wt, out, **kw)
-    check(load().ss_wino43_gate(C.byref(a), int(dilation), stream_ptr()), "ss_wino43_gate")
+    ops.ss_wino43_gate(a, int(dilation))
 
 
 def pack_gemm16_weights(Wp, Kp):
     """packed weight rows [Np][Kp] (Np % 64 == 0) -> the same floats in the fetch order of ss_gemm16_res (ss_pack_gemm16_weights)."""
     Wp = Wp.contiguous().float()
     out = torch.empty_like(Wp)
-    check(load().ss_pack_gemm16_weights(ptr(Wp), ptr(out), Wp.shape[0], Kp, stream_ptr()), "ss_pack_gemm16_weights")
+    ops.ss_pack_gemm16_weights(Wp, out, Wp.shape[0], Kp)
     return out
 
 
@@ -166,7 +272,7 @@ def pack_gate16_weights(Wp, Kp):
     """packed F(4,3) weights [Np][6 * Kp] -> the same floats in the fetch order of the 16x16x4 gate kernel (ss_pack_gate16_weights)."""
     Wp = Wp.contiguous().float()
     out = torch.empty_like(Wp)
-    check(load().ss_pack_gate16_weights(ptr(Wp), ptr(out), Wp.shape[0], Kp, stream_ptr()), "ss_pack_gate16_weights")
+    ops.ss_pack_gate16_weights(Wp, out, Wp.shape[0], Kp)
     return out
 
 
@@ -178,9 +284,9 @@ def wino43_gate16(A, Wt, out, *, dilation, mt=0, W16=None, **kw):
     kw.setdefault("epi", EPI_GATE)
     a = _fill_args(A, Wt, out, **kw)
     if W16 is not None:
-        check(load().ss_wino43_gate16w(C.byref(a), ptr(W16), int(dilation), int(mt), stream_ptr()), "ss_wino43_gate16w")
+        ops.ss_wino43_gate16w(a, W16, int(dilation), int(mt))
         return
-    check(load().ss_wino43_gate16(C.byref(a), int(dilation), int(mt), stream_ptr()), "ss_wino43_gate16")
+    ops.ss_wino43_gate16(a, int(dilation), int(mt))
 
 
 def gemm16_res(A, W, out, *, mt=0, W16=None, **kw):
@@ -189,29 +295,29 @@ def gemm16_res(A, W, out, *, mt=0, W16=None, **kw):
     W16 = pack_gemm16_weights(first N rows of W): the weights in the kernel's fetch order (ss_gemm16_resw; N % 64 == 0)."""
     a = _fill_args(A, W, out, **kw)
     if W16 is not None:
-        check(load().ss_gemm16_resw(C.byref(a), ptr(W16), int(mt), stream_ptr()), "ss_gemm16_resw")
+        ops.ss_gemm16_resw(a, W16, int(mt))
         return
-    check(load().ss_gemm16_res(C.byref(a), int(mt), stream_ptr()), "ss_gemm16_res")
+    ops.ss_gemm16_res(a, int(mt))
 
 
 def gemm16_store(A, W, out, *, mt=0, **kw):
     """C = act(A.W^T + bias) on 16x16x4 tiles with both operands streamed by LDS-DMA (ss_gemm16_store)."""
     a = _fill_args(A, W, out, **kw)
-    check(load().ss_gemm16_store(C.byref(a), int(mt), stream_ptr()), "ss_gemm16_store")
+    ops.ss_gemm16_store(a, int(mt))
 
 
 def gemm16_store_splitk(A, W, out, *, ksplit, mt=0, **kw):
     """ss_gemm16_store_splitk: the long-K GEMM with K split over `ksplit` workgroup slices + a fixed-order reduction (small launches)."""
     a = _fill_args(A, W, out, **kw)
     part = torch.empty(max(1, ksplit) * a.B * a.T * a.N, device=out.device, dtype=torch.float32)
-    check(load().ss_gemm16_store_splitk(C.byref(a), int(mt), int(ksplit), ptr(part), stream_ptr()), "ss_gemm16_store_splitk")
+    ops.ss_gemm16_store_splitk(a, int(mt), int(ksplit), part)
 
 
 def wino43_weight(w):
     """conv weight [Cout][Cin][3] (device) -> F(4,3)-transformed [Cout][Cin][6]."""
     w = w.contiguous().float()
     out = torch.empty(w.shape[0], w.shape[1], 6, device=w.device, dtype=torch.float32)
-    check(load().ss_wino43_weight_transform(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "ss_wino43_weight_transform")
+    ops.ss_wino43_weight_transform(w, out, w.shape[0], w.shape[1])
     return out
 
 
@@ -230,7 +336,7 @@ def wino43_conv(A, W, out, *, k, dilation, **kw):
     """Grouped Winograd F(4,3) conv (ss_wino43_conv); keyword arguments as conv_gemm (taps are implied by k and dilation)."""
     taps = [(j - (k - 1) // 2) * dilation for j in range(k)]
     a = _fill_args(A, W, out, taps=taps, **kw)
-    check(load().ss_wino43_conv(C.byref(a), k, dilation, stream_ptr()), "ss_wino43_conv")
+    ops.ss_wino43_conv(a, k, dilation)
     return out
 
 
@@ -267,7 +373,7 @@ def wino44_conv(A, W, out, *, k, dilation, **kw):
     """Grouped Winograd F(4,4) conv (ss_wino44_conv, k = 7 | 11); keyword arguments as conv_gemm (taps are implied by k and dilation)."""
     taps = [(j - (k - 1) // 2) * dilation for j in range(k)]
     a = _fill_args(A, W, out, taps=taps, **kw)
-    check(load().ss_wino44_conv(C.byref(a), k, dilation, stream_ptr()), "ss_wino44_conv")
+    ops.ss_wino44_conv(a, k, dilation)
     return out
 
 
@@ -277,7 +383,7 @@ def split3_weights(Wp, Kp):
     Wp = Wp.contiguous().float()
     Np = Wp.shape[0]
     out = torch.empty(Np, 3 * Wp.shape[1], device=Wp.device, dtype=torch.bfloat16)
-    check(load().ss_split3_weights(ptr(Wp), ptr(out), Np, Kp, stream_ptr()), "ss_split3_weights")
+    ops.ss_split3_weights(Wp, out, Np, Kp)
     return out
 
 
@@ -286,22 +392,22 @@ def split3_gemm16_weights(Wp, Kp):
     Wp = Wp.contiguous().float()
     Np = Wp.shape[0]
     out = torch.empty(int(load().ss_split3_gemm16_elems(Np, Kp)), device=Wp.device, dtype=torch.bfloat16)
-    check(load().ss_split3_gemm16_weights(ptr(Wp), ptr(out), Np, Kp, stream_ptr()), "ss_split3_gemm16_weights")
+    ops.ss_split3_gemm16_weights(Wp, out, Np, Kp)
     return out
 
 
 def gemm16x_store(A, W, Wx, out, *, mt=0, **kw):
     """bf16x3 form of gemm16_store (ss_gemm16x_store); W only supplies Np / Kp for the argument struct."""
     a = _fill_args(A, W, out, **kw)
-    check(load().ss_gemm16x_store(C.byref(a), ptr(Wx), int(mt), stream_ptr()), "ss_gemm16x_store")
+    ops.ss_gemm16x_store(a, Wx, int(mt))
 
 
 def wino43_gate16x(A, Wx, out, *, dilation, mt=0, **kw):
     """bf16x3 form of the F(4,3) gate (ss_wino43_gate16x); Wx = split3_weights(packed F(4,3) weight); keyword arguments as wino43_gate16
     (w_gs, if given, in bf16 elements)."""
     kw.setdefault("epi", EPI_GATE)
-    a = _fill_args(A, Wx, out, **kw)
-    check(load().ss_wino43_gate16x(C.byref(a), ptr(Wx), dilation, mt, stream_ptr()), "ss_wino43_gate16x")
+    a = _fill_args(A, ptr(Wx), out, **kw)   # the bf16 terms also stand in the struct's `const float* W`, as before: reinterpreted on purpose, so by address
+    ops.ss_wino43_gate16x(a, Wx, dilation, mt)
     return out
 
 
@@ -309,7 +415,7 @@ def wino_weight(w):
     """conv weight [Cout][Cin][3] (device) -> transformed [Cout][Cin][4]."""
     w = w.contiguous().float()
     out = torch.empty(w.shape[0], w.shape[1], 4, device=w.device, dtype=torch.float32)
-    check(load().ss_wino_weight_transform(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "ss_wino_weight_transform")
+    ops.ss_wino_weight_transform(w, out, w.shape[0], w.shape[1])
     return out
 
 
@@ -322,8 +428,7 @@ def pack_conv_weight(w, *, scale0=None, interleave_half=0, row_scale=1.0):
     Kp = round_up(Cin, 32)
     Np = 2 * round_up(interleave_half, 32) if interleave_half else round_up(Cout, 32)
     dst = torch.empty(Np, k * Kp, device=w.device, dtype=torch.float32)
-    check(load().ss_pack_conv_weight(ptr(w), ptr(scale0), ptr(dst), Cout, Cin, k, Np, Kp, interleave_half, _f(row_scale),
-                                     stream_ptr()), "ss_pack_conv_weight")
+    ops.ss_pack_conv_weight(w, scale0, dst, Cout, Cin, k, Np, Kp, interleave_half, float(row_scale))
     return dst
 
 
@@ -332,7 +437,7 @@ def weight_norm_scale(v, g):
     g = g.contiguous().float().reshape(-1)
     rows = v.shape[0]
     out = torch.empty(rows, device=v.device, dtype=torch.float32)
-    check(load().ss_weight_norm_scale(ptr(v), ptr(g), ptr(out), rows, v.numel() // rows, stream_ptr()), "ss_weight_norm_scale")
+    ops.ss_weight_norm_scale(v, g, out, rows, v.numel() // rows)
     return out
 
 
@@ -344,8 +449,7 @@ def pack_convtr_weight(w, scale0, u, group):
     Np = round_up(nph * Cout, 32)
     Kp = round_up(Cin, 32)
     dst = torch.empty(Np, 2 * Kp, device=w.device, dtype=torch.float32)
-    check(load().ss_pack_convtr_weight(ptr(w), ptr(scale0), ptr(dst), Cin, Cout, k, u, group, Np, Kp, stream_ptr()),
-          "ss_pack_convtr_weight")
+    ops.ss_pack_convtr_weight(w, scale0, dst, Cin, Cout, k, u, group, Np, Kp)
     return dst
 
 
@@ -355,7 +459,7 @@ def pack_bias(b, *, b2=None, Np=None, interleave_half=0, repeat=1):
     if Np is None:
         Np = 2 * round_up(interleave_half, 32) if interleave_half else round_up(n * repeat, 32)
     dst = torch.empty(Np, device=b.device, dtype=torch.float32)
-    check(load().ss_pack_bias(ptr(b), ptr(b2), ptr(dst), n, Np, interleave_half, repeat, stream_ptr()), "ss_pack_bias")
+    ops.ss_pack_bias(b, b2, dst, n, Np, interleave_half, repeat)
     return dst
 
 
@@ -365,7 +469,7 @@ def to_bf16(x, bias=None, lens=None):
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    check(load().ss_to_bf16(ptr(x), ptr(bias), ptr(y), 1, rows, Cc, Cc, Cc, ptr(lens), 0, 0, stream_ptr()), "ss_to_bf16")
+    ops.ss_to_bf16(x, bias, y, 1, rows, Cc, Cc, Cc, lens, 0, 0)
     return y
 
 
@@ -376,7 +480,7 @@ def split_bf16(x, bias=None, lens=None):
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     y = torch.empty(tuple(x.shape[:-1]) + (2 * Cc,), device=x.device, dtype=torch.bfloat16)
-    check(load().ss_split_bf16(ptr(x), ptr(bias), ptr(y), 1, rows, Cc, Cc, 2 * Cc, ptr(lens), 0, 0, stream_ptr()), "ss_split_bf16")
+    ops.ss_split_bf16(x, bias, y, 1, rows, Cc, Cc, 2 * Cc, lens, 0, 0)
     return y
 
 
@@ -387,7 +491,7 @@ def split_f16(x, bias=None, lens=None, scale=1.0):
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     y = torch.empty(tuple(x.shape[:-1]) + (2 * Cc,), device=x.device, dtype=torch.float16)
-    check(load().ss_split_f16(ptr(x), ptr(bias), _f(scale), ptr(y), 1, rows, Cc, Cc, 2 * Cc, ptr(lens), 0, 0, stream_ptr()), "ss_split_f16")
+    ops.ss_split_f16(x, bias, float(scale), y, 1, rows, Cc, Cc, 2 * Cc, lens, 0, 0)
     return y
 
 
@@ -528,20 +632,20 @@ def gemm_bf16(A, Wh, *, B, T, K, taps, N, Np, epi, lens=None, bias=None, act=ACT
               cur_bias_gs=0):
     """ss_gemm_bf16: A, Wh = bf16 device tensors (A [B,T,lda], Wh packed [Np][len(taps)*K]); see include/stylesinger_hip.h."""
     a = GemmBf16Args()
-    a.A = ptr(A); a.lda = lda if lda is not None else A.shape[-1]
+    set_members(a, A=A, lens=lens, W=Wh, bias=bias, E=E, X=X, next_bias=next_bias, Y=Y, C=out, cur_bias=cur_bias)
+    a.lda = lda if lda is not None else A.shape[-1]
     a.a_batch_stride = a_bs if a_bs is not None else T * a.lda
     a.K = K; a.ntaps = len(taps)
     for i, o in enumerate(taps):
         a.tap_off[i] = int(o)
-    a.lens = ptr(lens); a.B = B; a.T = T; a.W = ptr(Wh); a.N = N; a.Np = Np; a.epi = epi; a.act = act
-    a.bias = ptr(bias); a.E = ptr(E); a.lde = lde; a.e_batch_stride = e_bs if e_bs is not None else T * lde; a.gate_mode = gate_mode
-    a.X = ptr(X)
+    a.B = B; a.T = T; a.N = N; a.Np = Np; a.epi = epi; a.act = act
+    a.lde = lde; a.e_batch_stride = e_bs if e_bs is not None else T * lde; a.gate_mode = gate_mode
     if X is not None:
         a.ldx = X.shape[-1]; a.x_batch_stride = T * a.ldx
-    a.post_scale = post_scale; a.next_bias = ptr(next_bias); a.Y = ptr(Y)
+    a.post_scale = post_scale
     if Y is not None:
         a.ldy = Y.shape[-1]; a.y_batch_stride = T * a.ldy
-    a.C = ptr(out); a.ldc = ldc if ldc is not None else (out.shape[-1] if out is not None else 0)
+    a.ldc = ldc if ldc is not None else (out.shape[-1] if out is not None else 0)
     a.c_batch_stride = c_bs if c_bs is not None else T * a.ldc
     a.mask_rows = int(mask_rows)
     a.split = split
@@ -549,25 +653,24 @@ def gemm_bf16(A, Wh, *, B, T, K, taps, N, Np, epi, lens=None, bias=None, act=ACT
     a.q_scale = q_scale
     a.one_product = int(one_product)
     a.a_compact = int(a_compact)
-    a.cur_bias = ptr(cur_bias)
     a.group_size = group_size; a.w_group_stride = w_gs; a.bias_group_stride = bias_gs
     a.next_bias_group_stride = next_bias_gs; a.cur_bias_group_stride = cur_bias_gs
     if gate256 and epi == HEPI_STORE and split == 3:   # the fp16q4 skip GEMM
-        check(load().ss_gemm_bf16_tile256q(C.byref(a), stream_ptr()), "ss_gemm_bf16_tile256q")
+        ops.ss_gemm_bf16_tile256q(a)
         return
     if gate256 == 128 and epi == HEPI_GATE and split == 3:   # ... with the second product on the block-scaled fp4 instruction
-        check(load().ss_gemm_bf16_gate128q(C.byref(a), stream_ptr()), "ss_gemm_bf16_gate128q")
+        ops.ss_gemm_bf16_gate128q(a)
         return
     if gate256 == 128 and epi == HEPI_GATE:   # the fp16x2 gate on 256 x 128 tiles, two workgroups per CU
-        check(load().ss_gemm_bf16_gate128(C.byref(a), stream_ptr()), "ss_gemm_bf16_gate128")
+        ops.ss_gemm_bf16_gate128(a)
         return
     if gate256:   # the 256-row LDS-DMA kernels directly (ss_gemm_bf16 picks them by itself for many-round launches)
         if epi == HEPI_GATE:
-            check(load().ss_gemm_bf16_gate256(C.byref(a), stream_ptr()), "ss_gemm_bf16_gate256")
+            ops.ss_gemm_bf16_gate256(a)
         else:
-            check(load().ss_gemm_bf16_tile256(C.byref(a), stream_ptr()), "ss_gemm_bf16_tile256")
+            ops.ss_gemm_bf16_tile256(a)
         return
-    check(load().ss_gemm_bf16(C.byref(a), stream_ptr()), "ss_gemm_bf16")
+    ops.ss_gemm_bf16(a)
 
 
 def layer512_pack_gate(w_pairs, n_products=2):
@@ -575,7 +678,7 @@ def layer512_pack_gate(w_pairs, n_products=2):
     n_products = 1: the hi terms only, [393216])."""
     assert w_pairs.dtype == torch.float16 and tuple(w_pairs.shape) == (512, 3 * 256 * 2) and w_pairs.is_contiguous(), tuple(w_pairs.shape)
     out = torch.empty(8 * 48 * 2 * n_products * 64 * 8, device=w_pairs.device, dtype=torch.float16)
-    check(load().ss_layer512_pack_gate(ptr(w_pairs), ptr(out), n_products, stream_ptr()), "ss_layer512_pack_gate")
+    ops.ss_layer512_pack_gate(w_pairs, out, n_products)
     return out
 
 
@@ -583,7 +686,7 @@ def layer512_pack_res(w_pairs, n_products=2):
     """ss_split_f16 pack [>= 256][256*2] of the output projection (first 256 rows = residual half) -> fragment order (fp16 [131072]; n_products = 1: [65536])."""
     assert w_pairs.dtype == torch.float16 and w_pairs.shape[0] >= 256 and w_pairs.shape[1] == 512 and w_pairs.is_contiguous(), tuple(w_pairs.shape)
     out = torch.empty(8 * 16 * n_products * 64 * 8, device=w_pairs.device, dtype=torch.float16)
-    check(load().ss_layer512_pack_res(ptr(w_pairs), ptr(out), n_products, stream_ptr()), "ss_layer512_pack_res")
+    ops.ss_layer512_pack_res(w_pairs, out, n_products)
     return out
 
 
@@ -592,7 +695,7 @@ def layer512_tile_addend(E, *, B, T, lde=None, e_bs=None, out=None):
     lde = lde if lde is not None else E.shape[-1]
     n = load().ss_layer512_addend_floats(B, T)
     out = torch.empty(n, device=E.device, dtype=torch.float32) if out is None else out
-    check(load().ss_layer512_tile_addend(ptr(E), lde, e_bs if e_bs is not None else T * lde, ptr(out), B, T, stream_ptr()), "ss_layer512_tile_addend")
+    ops.ss_layer512_tile_addend(E, lde, e_bs if e_bs is not None else T * lde, out, B, T)
     return out
 
 
@@ -601,7 +704,7 @@ def layer512_tile_addend_f16(E, n_sets, *, B, T, lde=None, e_bs=None):
     lde = lde if lde is not None else E.shape[-1]
     n = load().ss_layer512_addend_halfs(B, T)
     out = torch.empty(n_sets, n, device=E.device, dtype=torch.float16)
-    check(load().ss_layer512_tile_addend_f16(ptr(E), lde, e_bs if e_bs is not None else T * lde, ptr(out), n_sets, n, B, T, stream_ptr()), "ss_layer512_tile_addend_f16")
+    ops.ss_layer512_tile_addend_f16(E, lde, e_bs if e_bs is not None else T * lde, out, n_sets, n, B, T)
     return out
 
 
@@ -621,7 +724,7 @@ def layer512_entry(X, bias=None, *, B, T, lens=None):
     """ss_layer512_entry: X fp32 [B][T][256] -> (H = fp16(X + bias) in slot-major tiles (fp16 [elems]), P = X in accumulator order (uint8 buffer of fp32))"""
     H = torch.empty(load().ss_layer512_h_elems(B, T), device=X.device, dtype=torch.float16)
     P = torch.empty(load().ss_layer512_stream_bytes(B, T), device=X.device, dtype=torch.uint8)
-    check(load().ss_layer512_entry(ptr(X), X.shape[-1], T * X.shape[-1], ptr(bias), ptr(lens), ptr(H), ptr(P), B, T, stream_ptr()), "ss_layer512_entry")
+    ops.ss_layer512_entry(X, X.shape[-1], T * X.shape[-1], bias, lens, H, P, B, T)
     return H, P
 
 
@@ -648,23 +751,22 @@ def layer512(Hin, Wg, E512, G, *, B, T, d, lens=None, Hout=None, P=None, Wr=None
              post_scale=0.70710678118654752440, ldg=None, g_bs=None, mask_rows=True, n_products=2, g_compact=False, e_f16=False, cur_bias=None):
     """ss_layer512: one launch per residual layer (gate + residual projection) of the fp16x2 mel denoiser; see include/stylesinger_hip.h."""
     a = Layer512Args()
-    a.Hin = ptr(Hin); a.d = d; a.n_products = n_products; a.g_compact = int(g_compact); a.e_f16 = int(e_f16)
-    a.Hout = ptr(Hout); a.P = ptr(P)
-    a.lens = ptr(lens); a.B = B; a.T = T; a.Wg = ptr(Wg); a.Wr = ptr(Wr); a.E512 = ptr(E512)
-    a.G = ptr(G); a.ldg = ldg if ldg is not None else G.shape[-1]; a.g_batch_stride = g_bs if g_bs is not None else T * a.ldg
-    a.mask_rows = int(mask_rows); a.bias_r = ptr(bias_r); a.next_bias = ptr(next_bias)
-    a.out_scale = out_scale; a.post_scale = post_scale; a.cur_bias = ptr(cur_bias)
-    check(load().ss_layer512(C.byref(a), stream_ptr()), "ss_layer512")
+    if e_f16 and E512 is not None:   # the fp16 sigma-delta sets travel in the `const float* E512` member: reinterpreted on purpose, so by address
+        E512 = ptr(E512)
+    set_members(a, Hin=Hin, Hout=Hout, P=P, lens=lens, Wg=Wg, Wr=Wr, E512=E512, G=G, bias_r=bias_r, next_bias=next_bias, cur_bias=cur_bias)
+    a.d = d; a.n_products = n_products; a.g_compact = int(g_compact); a.e_f16 = int(e_f16)
+    a.B = B; a.T = T
+    a.ldg = ldg if ldg is not None else G.shape[-1]; a.g_batch_stride = g_bs if g_bs is not None else T * a.ldg
+    a.mask_rows = int(mask_rows)
+    a.out_scale = out_scale; a.post_scale = post_scale
+    ops.ss_layer512(a)
 
 
 def layernorm(x, gamma, beta, *, B, T, C_, out=None, lens=None, mask_rows=False, eps=1e-5):
     out = x if out is None else out
-    check(load().ss_layernorm(ptr(x), ptr(out), ptr(gamma), ptr(beta), B, T, C_, C_, C_, T * C_,
-                              T * C_, _f(eps), ptr(lens), int(mask_rows), stream_ptr()), "ss_layernorm")
+    ops.ss_layernorm(x, out, gamma, beta, B, T, C_, C_, C_, T * C_, T * C_, float(eps), lens, int(mask_rows))
     return out
 
 
 def attention(Q, K, V, O, *, B, H, D, Tq, Tk, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, qlens=None, klens=None, scale):
-    check(load().ss_attention(ptr(Q), ptr(K), ptr(V), ptr(O), B, H, D, Tq, Tk, ldq, ldk, ldv, ldo, q_bs,
-                              k_bs, v_bs, o_bs, ptr(qlens), ptr(klens), _f(scale),
-                              stream_ptr()), "ss_attention")
+    ops.ss_attention(Q, K, V, O, B, H, D, Tq, Tk, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, qlens, klens, float(scale))

@@ -137,9 +137,8 @@ def limit_batch(wav, lens, sr, ceiling_db, lookahead_ms=DEFAULT_LOOKAHEAD_MS, ga
     rep = dict(min_gain=torch.empty(B, device=dev, dtype=torch.float32), n_limited=torch.empty(B, device=dev, dtype=torch.int32))
     nbytes = int(lib.ss_limit_workspace_bytes(B, Lx))
     ws = torch.empty(max(1, nbytes // 8), device=dev, dtype=torch.float64)
-    L.check(lib.ss_limit_true_peak(L.ptr(x), x.stride(0), Lx, L.ptr(n_d), None if gain is None else L.ptr(gain), L.ptr(bank_d), taps, left, float(c), W_,
-                                   L.ptr(y), Lx, Lx, L.ptr(rep["min_gain"]), L.ptr(rep["n_limited"]), None if g is None else L.ptr(g), B, L.ptr(ws),
-                                   nbytes, L.stream_ptr()), "ss_limit_true_peak")
+    L.ops.ss_limit_true_peak(x, x.stride(0), Lx, n_d, gain, bank_d, taps, left, float(c), W_, y, Lx, Lx,
+                             rep["min_gain"], rep["n_limited"], g, B, ws, nbytes)
     if g is not None:
         rep["g"] = g
     return y, rep

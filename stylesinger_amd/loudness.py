@@ -276,9 +276,8 @@ def _measure(x, rate, C, target, tab, n_d, nb_d, edges_d, nbs, lde):
                peak=torch.empty(B, device=dev, dtype=torch.float32), z=torch.empty(B, ldz, device=dev, dtype=torch.float64), n_blocks=list(nbs))
     nbytes = int(lib.ss_loudness_workspace_bytes(B, Lx, C))
     ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
-    L.check(lib.ss_loudness_measure(L.ptr(x), x.stride(0), Lx, L.ptr(n_d), L.ptr(nb_d), L.ptr(edges_d), lde, B, L.ptr(tab), C, float(target),
-                                    L.ptr(out["lufs"]), L.ptr(out["gain"]), L.ptr(out["peak"]), L.ptr(out["z"]), ldz, L.ptr(ws), nbytes, L.stream_ptr()),
-            "ss_loudness_measure")
+    L.ops.ss_loudness_measure(x, x.stride(0), Lx, n_d, nb_d, edges_d, lde, B, tab, C, float(target), out["lufs"], out["gain"], out["peak"], out["z"],
+                              ldz, ws, nbytes)
     return out
 
 
@@ -300,6 +299,5 @@ def normalize_batch(wavs, lens, rate, target=DEFAULT_TARGET, chunk=None, short="
     m = _measure(x, rate, C, target, tab, n_d, nb_d, edges_d, nbs, lde)
     B, Lx = x.shape
     y = torch.empty(B, Lx, device=x.device, dtype=torch.float32)
-    L.check(L.load().ss_loudness_apply(L.ptr(x), x.stride(0), Lx, L.ptr(n_d), L.ptr(m["gain"]), L.ptr(m["peak"]), L.ptr(y), Lx, Lx, B, L.stream_ptr()),
-            "ss_loudness_apply")
+    L.ops.ss_loudness_apply(x, x.stride(0), Lx, n_d, m["gain"], m["peak"], y, Lx, Lx, B)
     return y, dict(lufs=m["lufs"], gain=m["gain"], peak=m["peak"], n_blocks=m["n_blocks"])

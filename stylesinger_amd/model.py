@@ -18,9 +18,7 @@ from . import lib as L
 from . import spec as _spec
 from .config import make_hparams
 from .packing import Packing, _sin_table
-from .plans import Plans, struct_addr
-
-_lib = L.load
+from .plans import Plans
 
 
 def _pad_frames(x, T, dim=-1):
@@ -213,7 +211,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         """The shallow mel diffusion alone (a11 output -> a12): coarse mel [B,T,80] + condition [B,T,256] -> mel [B,T,80].
         z_q [B,1,80,T] / z_steps [K,B,1,80,T]: optional recorded noise (reference layout); default device Philox."""
         self._ensure_packed()
-        lib, pk, hp = _lib(), self._pk, self.hp
+        pk, hp = self._pk, self.hp
         dev = coarse_mel.device
         B, T, M = coarse_mel.shape
         K = hp["K_step"]
@@ -227,8 +225,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         self._run_mel(pl, (zq_n, zs_n), ddim_ts=self.ddim_timesteps(ddim_steps) if sampler == "ddim" else None,
                       plms_interval=plms_interval if sampler == "plms" else None, eta=eta)
         mel_out = torch.empty(B, T, M, device=dev, dtype=torch.float32)
-        L.check(lib.ss_mel_denorm(L.ptr(pl.xm), L.ptr(pk["spec_min"]), L.ptr(pk["spec_max"]), L.ptr(mel_out), B, T, M, L.ptr(pl.lens), None,
-                                  L.stream_ptr()), "denorm")
+        L.ops.ss_mel_denorm(pl.xm, pk["spec_min"], pk["spec_max"], mel_out, B, T, M, pl.lens, None)
         return mel_out
 
     # ---- forward ----------------------------------------------------------------------------------
@@ -238,8 +235,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         stylesinger.py:189-196) for a batch of references. The result depends on the reference only, so a style-transfer
         sweep (BASELINE config 5) computes it once per reference and passes it to forward(style_cache=...)."""
         self._ensure_packed()
-        lib, hp, pk = _lib(), self.hp, self._pk
-        st = L.stream_ptr
+        hp, pk = self.hp, self._pk
         H = hp["hidden_size"]
         dev = ref_mels.device
         B = ref_mels.shape[0]
@@ -250,7 +246,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             ref_f0 = ref_f0[None]
         ref_f0 = ref_f0.contiguous().float()
         lens_r = torch.empty(B, device=dev, dtype=torch.int32)
-        L.check(lib.ss_ref_lens(L.ptr(ref_mels), B, Tr, 80, L.ptr(lens_r), st()), "ref_lens")
+        L.ops.ss_ref_lens(ref_mels, B, Tr, 80, lens_r)
         xr = ref_mels.clone()
         acts = torch.empty(B, Tr, 80, **f32)
         wn_out = torch.zeros(B, Tr, 80, **f32)
@@ -261,7 +257,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             if w["res"] is not None:
                 self._gemm(acts, w["res"], xr, B, Tr, lens=lens_r, R=xr)
             self._gemm(acts, w["skip"], wn_out, B, Tr, lens=lens_r, accumulate=True)
-        L.check(lib.ss_add_rowscalar(L.ptr(wn_out), L.ptr(ref_f0), B, Tr, 80, L.ptr(lens_r), st()), "add f0")
+        L.ops.ss_add_rowscalar(wn_out, ref_f0, B, Tr, 80, lens_r)
         h80 = torch.empty(B, Tr, 80, **f32)
         h160 = torch.empty(B, Tr, 160, **f32)
         for blk in pk["cb"]:
@@ -273,13 +269,13 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         self._gemm(h80, pk["cb_post"], pre_rq, B, Tr, lens=lens_r)
         zq = torch.empty(B, Tr, H, **f32)
         codes = torch.empty(B, Tr, hp["rq_depth"], device=dev, dtype=torch.int64)
-        L.check(lib.ss_rq_lookup(L.ptr(pre_rq), L.ptr(pk["codebooks"]), L.ptr(zq), L.ptr(codes), B * Tr, H, hp["nRQ"], hp["rq_depth"], st()), "rq")
+        L.ops.ss_rq_lookup(pre_rq, pk["codebooks"], zq, codes, B * Tr, H, hp["nRQ"], hp["rq_depth"])
         cat = torch.empty(B, Tr, 2 * H, **f32)
         cat[:, :, :H].copy_(zq)
         pos_r = torch.empty(B, Tr, device=dev, dtype=torch.int32)
         tabr = self._pos(Tr + 2, dev)
-        L.check(lib.ss_make_positions(None, L.ptr(zq), H, Tr * H, L.ptr(pos_r), B, Tr, st()), "pos style")
-        L.check(lib.ss_table_add(L.ptr(pos_r), L.ptr(tabr), tabr.shape[0], L.ptr(cat) + 4 * H, 2 * H, Tr * 2 * H, B, Tr, H, None, 1.0, 0, st()), "pos add")
+        L.ops.ss_make_positions(None, zq, H, Tr * H, pos_r, B, Tr)
+        L.ops.ss_table_add(pos_r, tabr, tabr.shape[0], L.ptr(cat) + 4 * H, 2 * H, Tr * 2 * H, B, Tr, H, None, 1.0, 0)
         sty = torch.empty(B, Tr, H, **f32)
         self._gemm(cat, pk["l1"], sty, B, Tr, mask_rows=False)
         return dict(sty=sty, lens_r=lens_r, ref_f0=ref_f0, style_pre_rq=pre_rq, rq_codes=codes, style_rq=zq)
@@ -387,30 +383,29 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
 
     def _encode_text(self, c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed):
         """Phoneme encoder (a1) + note encoder (a2) + speaker / emotion projections -> c.enc [B,Tp,H], c.spk, c.emo [B,H]."""
-        lib, hp, pk, st, ret = _lib(), self.hp, self._pk, L.stream_ptr, c.ret
+        hp, pk, ret = self.hp, self._pk, c.ret
         H, dev, f32 = hp["hidden_size"], c.dev, c.f32
         B, Tp = c.B, c.Tp = txt_tokens.shape
         c.txt_tokens = txt_tokens = txt_tokens.contiguous()
         c.lens_p = lens_p = torch.empty(B, device=dev, dtype=torch.int32)
-        L.check(lib.ss_count_nonzero_i64(L.ptr(txt_tokens), L.ptr(lens_p), B, Tp, st()), "count_nonzero")
+        L.ops.ss_count_nonzero_i64(txt_tokens, lens_p, B, Tp)
         x = torch.empty(B, Tp, H, **f32)
         pos_p = torch.empty(B, Tp, device=dev, dtype=torch.int32)
         tab = self._pos(max(Tp, 8) + 2, dev)
-        L.check(lib.ss_embedding(L.ptr(txt_tokens), L.ptr(self.p("encoder.embed_tokens.weight")), L.ptr(x), B * Tp, H,
-                                 hp["vocab_size"], math.sqrt(H), 0, st()), "embedding")
-        L.check(lib.ss_make_positions(L.ptr(txt_tokens), None, 0, 0, L.ptr(pos_p), B, Tp, st()), "make_positions")
-        L.check(lib.ss_table_add(L.ptr(pos_p), L.ptr(tab), tab.shape[0], L.ptr(x), H, Tp * H, B, Tp, H, None, 1.0, 1, st()), "table_add")
-        L.check(lib.ss_add_bcast_mask(L.ptr(x), None, None, None, None, L.ptr(x), B, Tp, H, L.ptr(lens_p), st()), "mask")
+        L.ops.ss_embedding(txt_tokens, self.p("encoder.embed_tokens.weight"), x, B * Tp, H, hp["vocab_size"], math.sqrt(H), 0)
+        L.ops.ss_make_positions(txt_tokens, None, 0, 0, pos_p, B, Tp)
+        L.ops.ss_table_add(pos_p, tab, tab.shape[0], x, H, Tp * H, B, Tp, H, None, 1.0, 1)
+        L.ops.ss_add_bcast_mask(x, None, None, None, None, x, B, Tp, H, lens_p)
         c.enc = enc = self._fft_blocks(pk["enc"], x, B, Tp, lens_p)
         ret["encoder_out_text"] = enc.clone()
         note_out = torch.empty(B, Tp, H, **f32)
         c.note = note = note.contiguous()
         note_type, note_dur = note_type.contiguous(), note_dur.contiguous().float()
-        L.check(lib.ss_embedding(L.ptr(note), L.ptr(self.p("note_encoder.emb.weight")), L.ptr(note_out), B * Tp, H, 100, math.sqrt(H), 0, st()), "note emb")
-        L.check(lib.ss_note_dur_add(L.ptr(note_dur), L.ptr(self.p("note_encoder.dur_ln.weight").reshape(-1).contiguous()),
-                                    L.ptr(self.p("note_encoder.dur_ln.bias")), L.ptr(note_out), B * Tp, H, st()), "note dur")
-        L.check(lib.ss_embedding(L.ptr(note_type), L.ptr(self.p("note_encoder.type_emb.weight")), L.ptr(note_out), B * Tp, H, 5, math.sqrt(H), 1, st()), "type emb")
-        L.check(lib.ss_add_bcast_mask(L.ptr(enc), None, L.ptr(note_out), None, None, L.ptr(enc), B, Tp, H, None, st()), "enc+note")
+        L.ops.ss_embedding(note, self.p("note_encoder.emb.weight"), note_out, B * Tp, H, 100, math.sqrt(H), 0)
+        L.ops.ss_note_dur_add(note_dur, self.p("note_encoder.dur_ln.weight").reshape(-1).contiguous(), self.p("note_encoder.dur_ln.bias"), note_out,
+                              B * Tp, H)
+        L.ops.ss_embedding(note_type, self.p("note_encoder.type_emb.weight"), note_out, B * Tp, H, 5, math.sqrt(H), 1)
+        L.ops.ss_add_bcast_mask(enc, None, note_out, None, None, enc, B, Tp, H, None)
         c.spk = spk = torch.empty(B, H, **f32)
         c.emo = emo = torch.empty(B, H, **f32)
         self._gemm(spk_embed.contiguous().float(), pk["spk"], spk, 1, B, mask_rows=False)
@@ -419,11 +414,11 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
 
     def _regulate_length(self, c, mel2ph, f0, uv):
         """Duration predictor + length regulator (a3) -> c.mel2ph [B,T], c.T (bucket), c.T_out (the caller's frames), c.lens_t, c.dec [B,T,H]."""
-        lib, pk, st, ret = _lib(), self._pk, L.stream_ptr, c.ret
+        pk, ret = self._pk, c.ret
         H, dev, f32 = self.hp["hidden_size"], c.dev, c.f32
         B, Tp, enc, lens_p, txt_tokens = c.B, c.Tp, c.enc, c.lens_p, c.txt_tokens
         dur_inp = torch.empty(B, Tp, H, **f32)
-        L.check(lib.ss_add_bcast_mask(L.ptr(enc), L.ptr(c.spk), None, L.ptr(c.emo), None, L.ptr(dur_inp), B, Tp, H, L.ptr(lens_p), st()), "dur_inp")
+        L.ops.ss_add_bcast_mask(enc, c.spk, None, c.emo, None, dur_inp, B, Tp, H, lens_p)
         hbuf = torch.empty(B, Tp, H, **f32)
         cur = dur_inp
         for lyr in pk["dur"]:
@@ -436,12 +431,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c.lens_t = lens_t = torch.empty(B, device=dev, dtype=torch.int32)
         if mel2ph is None:
             dur = torch.empty(B, Tp, device=dev, dtype=torch.int64)
-            L.check(lib.ss_length_regulate(L.ptr(logdur), L.ptr(txt_tokens), L.ptr(dur), None, L.ptr(lens_t), B, Tp, 0, st()), "dur")
+            L.ops.ss_length_regulate(logdur, txt_tokens, dur, None, lens_t, B, Tp, 0)
             T = int(lens_t.max().item())  # host sync: the frame count is data dependent
             if T <= 0:
                 raise L.StyleSingerHipError("predicted durations are all zero")
             mel2ph = torch.empty(B, T, device=dev, dtype=torch.int64)
-            L.check(lib.ss_length_regulate(L.ptr(logdur), L.ptr(txt_tokens), L.ptr(dur), L.ptr(mel2ph), L.ptr(lens_t), B, Tp, T, st()), "lr")
+            L.ops.ss_length_regulate(logdur, txt_tokens, dur, mel2ph, lens_t, B, Tp, T)
             ret["dur"], ret["dur_choice"] = logdur[:, :, None], dur
         else:
             mel2ph = mel2ph.contiguous()
@@ -456,10 +451,10 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c.T = T = self.bucket_frames(T_out)
         if T != T_out:
             mel2ph = _pad_frames(mel2ph, T).contiguous()
-        L.check(lib.ss_count_nonzero_i64(L.ptr(mel2ph), L.ptr(lens_t), B, T, st()), "lens_t")
+        L.ops.ss_count_nonzero_i64(mel2ph, lens_t, B, T)
         ret["mel2ph"] = c.mel2ph = mel2ph
         c.dec = torch.empty(B, T, H, **f32)
-        L.check(lib.ss_gather_expand(L.ptr(enc), L.ptr(mel2ph), L.ptr(c.dec), B, Tp, T, H, st()), "expand")
+        L.ops.ss_gather_expand(enc, mel2ph, c.dec, B, Tp, T, H)
         # UMLN (a4): DistributionUncertainty returns x unchanged when not training (umln.py:48-50)
 
     def _align_style(self, c, ref_mels, ref_f0):
@@ -493,7 +488,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
     def _pitch(self, c, f0, uv, pitch_hz, pitch_shift):
         """Pitch: a given contour, or the two joint Gaussian/multinomial diffusions (a8) + post-processing (a9); then the pitch
         embedding and decoder_inp -> c.dec_inp [B,T,H]. Opens the call's diffusion plan (c.pl, c.graphs)."""
-        lib, st, ret = _lib(), L.stream_ptr, c.ret
+        ret = c.ret
         B, T, H, dev, f32 = c.B, c.T, self.hp["hidden_size"], c.dev, c.f32
         c.pl = pl = self._plan(B, T, dev, int(c.kwargs.get("plan_slot", 0)))
         pl.uses += 1
@@ -509,10 +504,9 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         ret["pitch_pred"], ret["f0_denorm"], ret["f0_denorm_pred"] = pitch_pred, f0_denorm, f0_denorm
         ret["pitch_coarse"] = coarse
         pitch_emb = torch.empty(B, T, H, **f32)
-        L.check(lib.ss_embedding(L.ptr(coarse), L.ptr(self.p("pitch_embed.weight")), L.ptr(pitch_emb), B * T, H, 300, 1.0, 0, st()), "pitch emb")
+        L.ops.ss_embedding(coarse, self.p("pitch_embed.weight"), pitch_emb, B * T, H, 300, 1.0, 0)
         c.dec_inp = dec_inp = torch.empty(B, T, H, **f32)
-        L.check(lib.ss_add_bcast_mask(L.ptr(c.dec), L.ptr(c.spk), L.ptr(pitch_emb), L.ptr(c.emo), L.ptr(c.style), L.ptr(dec_inp), B, T, H,
-                                      L.ptr(c.lens_t), st()), "dec_inp")
+        L.ops.ss_add_bcast_mask(c.dec, c.spk, pitch_emb, c.emo, c.style, dec_inp, B, T, H, c.lens_t)
         ret["decoder_inp"] = dec_inp
 
     def _pitch_given(self, c, f0, uv, pitch_hz, pitch_shift, out):
@@ -529,7 +523,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             else:   # "dtw": warp the guide onto the score's note per frame (the midi of _pitch_predicted)
                 from .pitch import contour_align_device
                 midi = torch.empty(B, T, device=dev, dtype=torch.int64)
-                L.check(_lib().ss_gather_expand_i64(L.ptr(c.note), L.ptr(c.mel2ph), L.ptr(midi), B, c.Tp, T, L.stream_ptr()), "midi")
+                L.ops.ss_gather_expand_i64(c.note, c.mel2ph, midi, B, c.Tp, T)
                 hz, a_idx, a_cost, a_status = contour_align_device(pitch_hz[0].to(dev), pitch_hz[1], midi, lens_t, T,
                                                                    band=c.kwargs.get("pitch_align_band"), shift=shift)
                 c.ret["pitch_align_idx"], c.ret["pitch_align_cost"], c.ret["pitch_align_status"] = a_idx, a_cost, a_status
@@ -539,21 +533,20 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             uv_g = uv.to(dev).float()
             uv_g = uv_g.contiguous() if T == T_out else torch.nn.functional.pad(uv_g, (0, T - T_out), value=1.0)
         pitch_pred, f0_denorm, coarse = out
-        L.check(_lib().ss_pitch_given(L.ptr(f0_g), L.ptr(uv_g), L.ptr(c.mel2ph), L.ptr(pitch_pred), L.ptr(f0_denorm), L.ptr(coarse), B * T,
-                                      L.stream_ptr()), "pitch_given")
+        L.ops.ss_pitch_given(f0_g, uv_g, c.mel2ph, pitch_pred, f0_denorm, coarse, B * T)
 
     def _pitch_predicted(self, c, out):
         """The f0 pair loop (a8: agnostic + specific denoiser, one grouped loop) and ss_pitch_post (a9)."""
-        lib, st, ret, pl = _lib(), L.stream_ptr, c.ret, c.pl
+        ret, pl = c.ret, c.pl
         B, T, Tp, H, dev, lens_t, mel2ph = c.B, c.T, c.Tp, self.hp["hidden_size"], c.dev, c.lens_t, c.mel2ph
         midi = torch.empty(B, T, device=dev, dtype=torch.int64)
-        L.check(lib.ss_gather_expand_i64(L.ptr(c.note), L.ptr(mel2ph), L.ptr(midi), B, Tp, T, st()), "midi")
+        L.ops.ss_gather_expand_i64(c.note, mel2ph, midi, B, Tp, T)
         pl.lens2[B:].copy_(lens_t)
-        L.check(lib.ss_f0_bounds(L.ptr(midi), L.ptr(pl.lo2), L.ptr(pl.hi2), B * T, st()), "bounds")
+        L.ops.ss_f0_bounds(midi, pl.lo2, pl.hi2, B * T)
         pl.lo2[B:].copy_(pl.lo2[:B])
         pl.hi2[B:].copy_(pl.hi2[:B])
         pl.cond_a.copy_(c.dec)  # = decoder_inp * tgt_nonpadding (the gather already wrote 0 on padding)
-        L.check(lib.ss_add_bcast_mask(L.ptr(c.dec), L.ptr(c.spk), None, L.ptr(c.emo), L.ptr(c.style), L.ptr(pl.cond_b), B, T, H, L.ptr(lens_t), st()), "cond_b")
+        L.ops.ss_add_bcast_mask(c.dec, c.spk, None, c.emo, c.style, pl.cond_b, B, T, H, lens_t)
 
         ts, eta = c.f0_ts, c.f0_eta   # None: the reference's full loop; else the strided sampler (its tapes: the same [S]... layout, row = network time)
 
@@ -574,13 +567,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         f0_a, uv_a, f0_b, uv_b = pl.f0[0].clone(), pl.uv[0].clone(), pl.f0[1].clone(), pl.uv[1].clone()
         ret["gdiff1"] = ret["mdiff1"] = ret["gdiff2"] = ret["mdiff2"] = 0.0
         pitch_pred, f0_denorm, coarse = out
-        L.check(lib.ss_pitch_post(L.ptr(f0_a), L.ptr(uv_a), L.ptr(f0_b), L.ptr(uv_b), L.ptr(midi), L.ptr(mel2ph), L.ptr(pitch_pred),
-                                  L.ptr(f0_denorm), L.ptr(coarse), B * T, st()), "pitch_post")
+        L.ops.ss_pitch_post(f0_a, uv_a, f0_b, uv_b, midi, mel2ph, pitch_pred, f0_denorm, coarse, B * T)
         ret["f0_a"], ret["uv_a"], ret["f0_b"], ret["uv_b"] = f0_a, uv_a, f0_b, uv_b
 
     def _decode_prodiff(self, c):
         """ProDiff teacher decoder (stylesinger.py:175-177, modules/diff/prodiff.py:205-221): decoder_inp is the condition."""
-        lib, hp, pk, st, pl = _lib(), self.hp, self._pk, L.stream_ptr, c.pl
+        hp, pk, pl = self.hp, self._pk, c.pl
         B, T, M, S = c.B, c.T, hp["audio_num_mel_bins"], int(hp["timesteps"])
         pl.cond_mel.copy_(c.dec_inp)
         sch = pk["prodiff_sched"]
@@ -589,30 +581,28 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         def run(noise=None):
             zs = None
             if noise is None:
-                L.check(lib.ss_fill_normal_rows(L.ptr(pl.xm), B, T * M, T * M, 31, L.ptr(pl.seed), st()), "x_T")
+                L.ops.ss_fill_normal_rows(pl.xm, B, T * M, T * M, 31, pl.seed)
             else:
                 pl.xm.copy_(_noise_btm(noise["mel"]["z_q"], c.dev, (B, M, c.T_out), T))
                 zs = _noise_btm(noise["mel"]["z_steps"], c.dev, (S, B, M, c.T_out), T)
-            L.check(lib.ss_prodiff_sample(struct_addr(pk["mel"]["net"]), L.ptr(pl.xm), L.ptr(pl.cond_mel), L.ptr(pl.lens), B, T, L.ptr(zs),
-                                          37, L.ptr(pl.seed), S, L.hptr(sch["c1"]), L.hptr(sch["c2"]), L.hptr(sch["sigma"]), 1,
-                                          L.ptr(wsp), wsb, st()), "prodiff")
+            L.ops.ss_prodiff_sample(pk["mel"]["net"], pl.xm, pl.cond_mel, pl.lens, B, T, zs, 37, pl.seed, S, sch["c1"], sch["c2"], sch["sigma"], 1,
+                                    wsp, wsb)
         self._run_loop(pl, "mel", run, tape=c.noise, graphs=c.graphs)
         mel_out = torch.empty(B, T, M, **c.f32)
         # the reference leaves padded frames unmasked (prodiff.py:219-220); frames past lens[b] are written as 0 here
-        L.check(lib.ss_add_bcast_mask(L.ptr(pl.xm), None, None, None, None, L.ptr(mel_out), B, T, M, L.ptr(c.lens_t), st()), "mel mask")
+        L.ops.ss_add_bcast_mask(pl.xm, None, None, None, None, mel_out, B, T, M, c.lens_t)
         c.ret["mel_out"] = mel_out
         c.ret["lens"] = c.lens_t
 
     def _decode_fft(self, c):
         """FFT decoder -> coarse mel (a10) -> c.coarse_mel [B,T,M]."""
-        lib, hp, pk, st, ret = _lib(), self.hp, self._pk, L.stream_ptr, c.ret
+        hp, pk, ret = self.hp, self._pk, c.ret
         B, T, H, dev, dec_inp = c.B, c.T, hp["hidden_size"], c.dev, c.dec_inp
         xd = dec_inp.clone()
         pos_t = torch.empty(B, T, device=dev, dtype=torch.int32)
         tabt = self._pos(T + 2, dev)
-        L.check(lib.ss_make_positions(None, L.ptr(dec_inp), H, T * H, L.ptr(pos_t), B, T, st()), "pos dec")
-        L.check(lib.ss_table_add(L.ptr(pos_t), L.ptr(tabt), tabt.shape[0], L.ptr(xd), H, T * H, B, T, H,
-                                 L.ptr(self.p("decoder.pos_embed_alpha")), 1.0, 1, st()), "pos add dec")
+        L.ops.ss_make_positions(None, dec_inp, H, T * H, pos_t, B, T)
+        L.ops.ss_table_add(pos_t, tabt, tabt.shape[0], xd, H, T * H, B, T, H, self.p("decoder.pos_embed_alpha"), 1.0, 1)
         xd = self._fft_blocks(pk["dec"], xd, B, T, c.lens_t, ffn_wino=True)
         ret["decoder_out"] = xd
         c.coarse_mel = torch.empty(B, T, hp["audio_num_mel_bins"], **c.f32)
@@ -622,7 +612,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
 
     def _refine_mel(self, c):
         """Condition projection (a11) + shallow mel diffusion (a12): DDPM by default, `sampler="ddim"` / `"plms"` on request."""
-        lib, hp, pk, st, ret, pl, kwargs = _lib(), self.hp, self._pk, L.stream_ptr, c.ret, c.pl, c.kwargs
+        hp, pk, ret, pl, kwargs = self.hp, self._pk, c.ret, c.pl, c.kwargs
         B, T, M, K, dev, noise = c.B, c.T, hp["audio_num_mel_bins"], hp["K_step"], c.dev, c.noise
         gcat = torch.cat([c.coarse_mel, c.dec_inp, c.spk[:, None, :].expand(-1, T, -1), c.emo[:, None, :].expand(-1, T, -1), c.style], -1).contiguous()
         self._gemm(gcat, pk["ln_proj"], pl.cond_mel, B, T, mask_rows=False)
@@ -646,8 +636,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         # the reference does not mask padded frames here (shallow_diffusion_tts.py:305-306); with per-item
         # lengths the frames past lens[b] are not part of the utterance, so they are written as 0.
         pl.nonfinite.zero_()
-        L.check(lib.ss_mel_denorm(L.ptr(pl.xm), L.ptr(pk["spec_min"]), L.ptr(pk["spec_max"]), L.ptr(mel_out), B, T, M, L.ptr(c.lens_t),
-                                  L.ptr(pl.nonfinite), st()), "denorm")
+        L.ops.ss_mel_denorm(pl.xm, pk["spec_min"], pk["spec_max"], mel_out, B, T, M, c.lens_t, pl.nonfinite)
         # fp16 terms carry the residual stream x + dstep and the gate outputs inside the stack: unlike the bf16 modes they overflow beyond 65504.
         # The denorm kernel flags a non-finite valid frame on EVERY forward (ret["nonfinite"], a device word: `check_finite(ret)` wherever the
         # caller synchronises anyway - infer.py does); the first forward of every plan checks it here (one host sync).

@@ -250,8 +250,8 @@ class Packing:
             else:
                 tt = torch.stack([pk_[key] for pk_ in packs]).contiguous()
                 gs = packs[0][key].numel()
-            keep.append(tt)
-            return tt.data_ptr(), gs
+            keep.append(tt)   # the descriptor holds the address, `keep` the tensor
+            return L.member_address(net, key.split(".")[0], tt), gs
 
         for key in ("w_in", "b_in", "dstep", "w_cond", "b_cond", "w_skip", "b_skip", "w_final", "b_final") + (("uv_embed",) if f0 else ()) \
                 + (("w_skipall", "b_skipall") if self.defer_skip else ()):

@@ -70,7 +70,7 @@ def norm_interp_f0_device(f0_hz, lens=None, hparams=None):
     out = torch.empty_like(x)
     uv = torch.empty_like(x)
     lp = None if lens is None else lens.to(device=x.device, dtype=torch.int32).contiguous()
-    L.check(L.load().ss_norm_interp_f0(L.ptr(x), L.ptr(lp), L.ptr(out), L.ptr(uv), B, T, L.stream_ptr()), "ss_norm_interp_f0")
+    L.ops.ss_norm_interp_f0(x, lp, out, uv, B, T)
     return out, uv
 
 
@@ -119,8 +119,7 @@ def contour_fit_device(f0_hz, lens_c, lens_t, T, shift=0.0):
     if lc.numel() != B or lt.numel() != B:
         raise ValueError(f"contour_fit_device: {lc.numel()} source lengths and {lt.numel()} target lengths for {B} contours")
     out = torch.empty(B, int(T), device=dev, dtype=torch.float32)
-    L.check(L.load().ss_contour_fit(L.ptr(x), x.stride(0), Lc, L.ptr(lc), L.ptr(lt), float(shift), L.ptr(out), out.stride(0), int(T), B,
-                                    L.stream_ptr()), "ss_contour_fit")
+    L.ops.ss_contour_fit(x, x.stride(0), Lc, lc, lt, float(shift), out, out.stride(0), int(T), B)
     return out
 
 
@@ -275,7 +274,6 @@ def contour_align_device(f0_hz, lens_c, midi, lens_t, T, band=None, shift=0.0):
     idx = torch.empty(B, T, device=dev, dtype=torch.int32)
     cost = torch.empty(B, device=dev, dtype=torch.int32)
     status = torch.empty(B, device=dev, dtype=torch.int32)
-    L.check(lib.ss_contour_align(L.ptr(x), x.stride(0), Lc, L.ptr(lc), L.ptr(md), md.stride(0), L.ptr(lt), band, ALIGN_UV_COST, ALIGN_CAP, float(shift),
-                                 L.ptr(out), out.stride(0), L.ptr(idx), L.ptr(cost), L.ptr(status), T, B, L.ptr(ws), ws_bytes, L.stream_ptr()),
-            "ss_contour_align")
+    L.ops.ss_contour_align(x, x.stride(0), Lc, lc, md, md.stride(0), lt, band, ALIGN_UV_COST, ALIGN_CAP, float(shift), out, out.stride(0), idx, cost,
+                           status, T, B, ws, ws_bytes)
     return out, idx, cost, status

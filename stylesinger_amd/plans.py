@@ -13,11 +13,6 @@ from . import lib as L
 _lib = L.load
 
 
-def struct_addr(struct):
-    """Address of a ctypes struct, as the integer the C-ABI's `const ss_wavenet*` arguments take."""
-    return ctypes.addressof(struct)
-
-
 class _DiffPlan:
     """Static device buffers (+ optional captured hipGraphs) of the three diffusion loops for one (B, T).
 
@@ -43,7 +38,7 @@ class _DiffPlan:
         self.uv2 = torch.zeros(2 * B, T, device=dev, dtype=torch.int32)
         self.f0 = [self.f02[:B], self.f02[B:]]
         self.uv = [self.uv2[:B], self.uv2[B:]]
-        self.ws_f0_bytes = lib.ss_wavenet_workspace_bytes(struct_addr(pk["f0_pair"]["net"]), 2 * B, T)
+        self.ws_f0_bytes = lib.ss_wavenet_workspace_bytes(ctypes.byref(pk["f0_pair"]["net"]), 2 * B, T)
         self.ws_f0 = torch.empty(self.ws_f0_bytes, device=dev, dtype=torch.uint8)
         self.coarse_mel = torch.empty(B, T, M, **f32)
         self.cond_mel = torch.empty(B, T, H, **f32)
@@ -53,7 +48,7 @@ class _DiffPlan:
         self.ws_mel = []
         for i in range(nsplit):
             nb = self.bounds[i + 1] - self.bounds[i]
-            wsb = lib.ss_wavenet_workspace_bytes(struct_addr(pk["mel"]["net"]), nb, T)
+            wsb = lib.ss_wavenet_workspace_bytes(ctypes.byref(pk["mel"]["net"]), nb, T)
             self.ws_mel.append((wsb, torch.empty(wsb, device=dev, dtype=torch.uint8)))
         self.ws_prodiff = None   # full-batch workspace of the ProDiff decoder when ws_mel is split (allocated on first use, plan-owned)
         self.graphs = {}         # captured loops: "f0" (the f0 pair), ("f0", n_steps, eta) (its strided sampler), "mel" (DDPM or ProDiff), ("ddim", n_steps, eta)
@@ -201,7 +196,7 @@ class Plans:
             return pl.ws_mel[0]
         if keep and pl.ws_prodiff is not None:
             return pl.ws_prodiff
-        wsb = _lib().ss_wavenet_workspace_bytes(struct_addr(self._pk["mel"]["net"]), pl.B, pl.T)
+        wsb = _lib().ss_wavenet_workspace_bytes(ctypes.byref(self._pk["mel"]["net"]), pl.B, pl.T)
         ws = (wsb, torch.empty(wsb, device=pl.xm.device, dtype=torch.uint8))
         if keep:
             pl.ws_prodiff = ws
@@ -222,9 +217,9 @@ class Plans:
         """Both joint f0/uv samplers in ONE grouped loop (they are independent given their conditions). `ts` (network times, strictly
         decreasing) switches to the strided sampler `ss_f0diff_sample_strided` with `eta` = 0 deterministic Gaussian half ... 1 ancestral;
         tapes keep the reference's [S]... layout and are indexed by network time."""
-        lib, pk = _lib(), self._pk
+        pk = self._pk
         B, T = pl.B, pl.T
-        sdp = L.ptr(pl.seed)
+        sdp = pl.seed
         net = pk["f0_pair"]["net"]
         sched = pk["f0_pair"]["sched"]
         if ts is not None and sched["strided_error"] is not None:   # the checkpoint's tables do not belong to its betas (packing.f0_strided_guard)
@@ -233,16 +228,14 @@ class Plans:
         if tape is not None:
             zs, us = tape  # [S][2B][T], [S][2B][2][T]
         else:
-            L.check(lib.ss_fill_normal_rows(L.ptr(pl.f02), 2 * B, T, T, 11, sdp, L.stream_ptr()), "z0")
+            L.ops.ss_fill_normal_rows(pl.f02, 2 * B, T, T, 11, sdp)
         if ts is not None:
             ts = np.ascontiguousarray(np.asarray(ts, dtype=np.int32))
-            L.check(lib.ss_f0diff_sample_strided(struct_addr(net), L.ptr(pl.f02), L.ptr(pl.uv2), L.ptr(pl.cond2), L.ptr(pl.lo2), L.ptr(pl.hi2),
-                                                 L.ptr(pl.lens2), 2 * B, T, L.hptr(ts), len(ts), 0, len(ts), L.hptr(sched["betas_f64"]), float(eta),
-                                                 L.ptr(zs), L.ptr(us), 17, sdp, 1, L.ptr(pl.ws_f0), pl.ws_f0_bytes, L.stream_ptr()), "f0 pair strided")
+            L.ops.ss_f0diff_sample_strided(net, pl.f02, pl.uv2, pl.cond2, pl.lo2, pl.hi2, pl.lens2, 2 * B, T, ts, len(ts), 0, len(ts),
+                                           sched["betas_f64"], float(eta), zs, us, 17, sdp, 1, pl.ws_f0, pl.ws_f0_bytes)
             return
-        L.check(lib.ss_f0diff_sample(struct_addr(net), L.ptr(pl.f02), L.ptr(pl.uv2), L.ptr(pl.cond2), L.ptr(pl.lo2), L.ptr(pl.hi2),
-                                     L.ptr(pl.lens2), 2 * B, T, L.ptr(zs), L.ptr(us), 17, sdp, 0, net.steps, 1,
-                                     L.ptr(pl.ws_f0), pl.ws_f0_bytes, L.stream_ptr()), "f0 pair")
+        L.ops.ss_f0diff_sample(net, pl.f02, pl.uv2, pl.cond2, pl.lo2, pl.hi2, pl.lens2, 2 * B, T, zs, us, 17, sdp, 0, net.steps, 1, pl.ws_f0,
+                               pl.ws_f0_bytes)
 
     def ddim_timesteps(self, n):
         """n network times, strictly decreasing from K-1 to 0 (uniform stride)."""
@@ -257,16 +250,15 @@ class Plans:
     def _run_mel(self, pl, tape=None, ddim_ts=None, plms_interval=None, eta=0.0):
         """q_sample + the shallow reverse loop (batch halves on two streams); `ddim_ts` switches to the strided
         DDIM sampler (BASELINE config 5; `eta` = 0 deterministic ... 1 ancestral), `plms_interval` to the reference's PLMS sampler (pndm_speedup)."""
-        lib, pk, hp = _lib(), self._pk, self.hp
+        pk, hp = self._pk, self.hp
         B, T, M = pl.B, pl.T, hp["audio_num_mel_bins"]
         net = pk["mel"]["net"]
         K = hp["K_step"]
         sa = float(pk["mel"]["sched"]["sqrt_alphas_cumprod"][K - 1])
         s1 = float(pk["mel"]["sched"]["sqrt_one_minus_alphas_cumprod"][K - 1])
-        sdp = L.ptr(pl.seed)
+        sdp = pl.seed
         zq_n, zs_n = tape if tape is not None else (None, None)
-        L.check(lib.ss_mel_qsample(L.ptr(pl.coarse_mel), L.ptr(pk["spec_min"]), L.ptr(pk["spec_max"]), sa, s1, L.ptr(zq_n), 23, sdp,
-                                   L.ptr(pl.xm), B, T, M, L.stream_ptr()), "qsample")
+        L.ops.ss_mel_qsample(pl.coarse_mel, pk["spec_min"], pk["spec_max"], sa, s1, zq_n, 23, sdp, pl.xm, B, T, M)
         if ddim_ts is not None or plms_interval is not None:
             ac = pk["mel"]["sched"]["alphas_cumprod_np"]  # host table, read by the loop driver at launch time
             wsb, wsp = self._full_batch_ws(pl)
@@ -274,14 +266,12 @@ class Plans:
             if pl.plms_hist is None:
                 pl.plms_hist = torch.empty(6 * B * T * M, device=pl.xm.device, dtype=torch.float32)
                 pl.recount()
-            L.check(lib.ss_meldiff_sample_plms(struct_addr(net), L.ptr(pl.xm), L.ptr(pl.cond_mel), L.ptr(pl.lens), B, T, K, int(plms_interval),
-                                               L.hptr(ac), 1, L.ptr(pl.plms_hist), L.ptr(wsp), wsb, L.stream_ptr()), "meldiff plms")
+            L.ops.ss_meldiff_sample_plms(net, pl.xm, pl.cond_mel, pl.lens, B, T, K, int(plms_interval), ac, 1, pl.plms_hist, wsp, wsb)
             return
         if ddim_ts is not None:
             ts = np.ascontiguousarray(np.asarray(ddim_ts, dtype=np.int32))
             ac64 = pk["mel"]["sched"]["alphas_cumprod_f64"]
-            L.check(lib.ss_meldiff_sample_ddim(struct_addr(net), L.ptr(pl.xm), L.ptr(pl.cond_mel), L.ptr(pl.lens), B, T, L.hptr(ts), len(ts),
-                                               L.hptr(ac64), float(eta), L.ptr(zs_n), 31, sdp, 1, L.ptr(wsp), wsb, L.stream_ptr()), "meldiff ddim")
+            L.ops.ss_meldiff_sample_ddim(net, pl.xm, pl.cond_mel, pl.lens, B, T, ts, len(ts), ac64, float(eta), zs_n, 31, sdp, 1, wsp, wsb)
             return
         nsplit = len(pl.ws_mel)
         main = torch.cuda.current_stream()
@@ -293,7 +283,6 @@ class Plans:
             b0, nb = pl.bounds[i], pl.bounds[i + 1] - pl.bounds[i]
             wsb, wsp = pl.ws_mel[i]
             with torch.cuda.stream(strm):
-                L.check(lib.ss_meldiff_sample(struct_addr(net), L.ptr(pl.xm[b0:]), L.ptr(pl.cond_mel[b0:]), L.ptr(pl.lens[b0:]), nb, T,
-                                              L.ptr(zparts[i]), 29 + 7919 * b0, sdp, 0, K, 1, L.ptr(wsp), wsb, L.stream_ptr()), "meldiff")
+                L.ops.ss_meldiff_sample(net, pl.xm[b0:], pl.cond_mel[b0:], pl.lens[b0:], nb, T, zparts[i], 29 + 7919 * b0, sdp, 0, K, 1, wsp, wsb)
         for sd_ in set(side) - {main}:
             main.wait_stream(sd_)

@@ -100,9 +100,9 @@ class ReferenceProducers:
 
     def _mean_l2norm_per_item(self, part, counts):
         out = torch.empty(len(counts), part.shape[1], device=self.device, dtype=torch.float32)
-        lib, o = L.load(), 0
+        o = 0
         for b, c in enumerate(counts):
-            L.check(lib.ss_mean_l2norm(L.ptr(part[o:o + c]), L.ptr(out[b]), c, part.shape[1], L.stream_ptr()), "ss_mean_l2norm")
+            L.ops.ss_mean_l2norm(part[o:o + c], out[b], c, part.shape[1])
             o += c
         return out
 
@@ -166,8 +166,7 @@ class ReferenceProducers:
         out = torch.empty(x.shape[0], max(lens), device=self.device, dtype=torch.float32)
         n_out = torch.tensor(lens, dtype=torch.int32).to(self.device)
         n_in = None if valid_lens is None else torch.tensor([int(v) for v in valid_lens], dtype=torch.int32).to(self.device)
-        L.check(L.load().ss_round_f16_rows(L.ptr(x), x.shape[1], x.shape[1], L.ptr(n_in), L.ptr(n_out), L.ptr(out), out.shape[1], x.shape[0], L.stream_ptr()),
-                "ss_round_f16_rows")
+        L.ops.ss_round_f16_rows(x, x.shape[1], x.shape[1], n_in, n_out, out, out.shape[1], x.shape[0])
         for t_ in (n_out, n_in):
             if t_ is not None:
                 t_.record_stream(torch.cuda.current_stream(self.device))

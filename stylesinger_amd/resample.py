@@ -147,6 +147,5 @@ def resample_batch(wavs, lens, sr_in, sr_out):
     bank_d = _cached(("bank", sr_in, sr_out, dev), lambda: torch.from_numpy(bank.copy()).to(dev))
     meta = _cached(("lens", sr_in, sr_out, dev, tuple(lens)), lambda: torch.tensor([lens, n_cmp, n_out], dtype=torch.int32).to(dev))
     y = torch.empty(B, Ly, device=dev, dtype=torch.float32)
-    L.check(L.load().ss_resample_poly(L.ptr(x), x.stride(0), Lx, L.ptr(meta[0]), L.ptr(y), Ly, Ly, L.ptr(meta[1]), L.ptr(meta[2]), B,
-                                      L.ptr(bank_d), up, down, taps, left, L.stream_ptr()), "ss_resample_poly")
+    L.ops.ss_resample_poly(x, x.stride(0), Lx, meta[0], y, Ly, Ly, meta[1], meta[2], B, bank_d, up, down, taps, left)
     return y, n_out

@@ -215,7 +215,7 @@ def song_offsets(lens, out=None):
     lens = lens.to(torch.int32).contiguous()
     S = lens.numel()
     out = torch.empty(S + 1, device=lens.device, dtype=torch.int64) if out is None else out
-    L.check(L.load().ss_song_offsets(L.ptr(lens), S, L.ptr(out), L.stream_ptr()), "ss_song_offsets")
+    L.ops.ss_song_offsets(lens, S, out)
     return out
 
 
@@ -227,9 +227,8 @@ def song_place(src, seg, lens, offsets, unit, out, win=None, flags=None, cap=Non
     assert src.is_contiguous() and src.dtype == torch.float32 and out.dtype == torch.float32 and out.is_contiguous()
     assert seg.dtype == torch.int32 and lens.dtype == torch.int32 and offsets.dtype == torch.int64 and seg.numel() == B
     lds = src.numel() // B
-    L.check(L.load().ss_song_place(L.ptr(src), lds, L.ptr(seg), B, L.ptr(lens), L.ptr(offsets), lens.numel(), int(unit), L.ptr(win),
-                                   0 if win is None else win.numel(), L.ptr(out), out.numel() if cap is None else int(cap), L.ptr(flags),
-                                   L.stream_ptr()), "ss_song_place")
+    L.ops.ss_song_place(src, lds, seg, B, lens, offsets, lens.numel(), int(unit), win, 0 if win is None else win.numel(), out,
+                        out.numel() if cap is None else int(cap), flags)
     return out
 
 

@@ -48,7 +48,7 @@ class SpeakerEncoderHIP(EmotionEncoderHIP):
         then the L2-normalised mean"""
         part = self.forward(frames)
         out = torch.empty(self.E, device=self.device)
-        L.check(L.load().ss_mean_l2norm(L.ptr(part), L.ptr(out), part.shape[0], self.E, L.stream_ptr()), "ss_mean_l2norm")
+        L.ops.ss_mean_l2norm(part, out, part.shape[0], self.E)
         return out, part
 
     @torch.no_grad()

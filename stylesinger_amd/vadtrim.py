@@ -180,8 +180,8 @@ def lrt_flags_device(wavs, lens, sr=SAMPLING_RATE):
     table = _cached(("vad_lrt_table", LRT_N_FFT, spw, dev), lambda: torch.from_numpy(lrt_table_f64(LRT_N_FFT, spw)).to(dev))
     flags = torch.empty(B, max_w, device=dev, dtype=torch.uint8)
     stat = torch.empty(B, max_w, device=dev, dtype=torch.float64)
-    L.check(lib.ss_vad_lrt(L.ptr(x), x.stride(0), L.ptr(meta), B, max_w, spw, LRT_N_FFT, LRT_K_LO, LRT_K_HI, LRT_Q_DIV, LRT_PEAK_DB, LRT_N_MIN, LRT_ETA,
-                           L.ptr(table), L.ptr(flags), max_w, L.ptr(stat), max_w, L.ptr(ws), ws_bytes, L.stream_ptr()), "ss_vad_lrt")
+    L.ops.ss_vad_lrt(x, x.stride(0), meta, B, max_w, spw, LRT_N_FFT, LRT_K_LO, LRT_K_HI, LRT_Q_DIV, LRT_PEAK_DB, LRT_N_MIN, LRT_ETA, table, flags,
+                     max_w, stat, max_w, ws, ws_bytes)
     for t in (meta, ws):
         t.record_stream(torch.cuda.current_stream(dev))
     return flags, stat
@@ -211,8 +211,8 @@ def trim_long_silences_device(wavs, lens, flags, sr=SAMPLING_RATE):
     out = torch.empty(B, max_w * spw, device=wavs.device, dtype=torch.float32)
     out_lens = torch.empty(B, device=wavs.device, dtype=torch.int32)
     win_dst = torch.empty(B, max_w, device=wavs.device, dtype=torch.int32)
-    L.check(L.load().ss_vad_trim(L.ptr(wavs), Lx, L.ptr(meta), L.ptr(fl), fl.shape[1], B, max_w, spw, VAD_MOVING_AVERAGE_WIDTH, VAD_MAX_SILENCE_LENGTH,
-                                 L.ptr(out), out.shape[1], L.ptr(out_lens), L.ptr(win_dst), L.stream_ptr()), "ss_vad_trim")
+    L.ops.ss_vad_trim(wavs, Lx, meta, fl, fl.shape[1], B, max_w, spw, VAD_MOVING_AVERAGE_WIDTH, VAD_MAX_SILENCE_LENGTH, out, out.shape[1], out_lens,
+                      win_dst)
     for t in (meta, fl, win_dst):
         t.record_stream(torch.cuda.current_stream(wavs.device))
     return out, out_lens

@@ -149,9 +149,9 @@ class HifiGanGeneratorHIP(torch.nn.Module):
             for m, d in enumerate(h["resblock_dilation_sizes"][j]):
                 hg.rb_d[j][m] = d
 
-        def hold(t):
+        def hold(t):   # every pointer member of ss_hifigan is a `const float*`: checked as w_pre; `keep` owns the tensor, the struct its address
             keep.append(t)
-            return t.data_ptr()
+            return L.member_address(hg, "w_pre", t)
 
         def wino_group(c, k, d):   # F(4,4) tap groups where ss_wino44_conv_ok says so (the rule conv_same of hifigan.hip runs by), else F(4,3)
             return L.wino44_group_weight if L.wino44_conv_ok(c, k, d) else L.wino43_group_weight
@@ -216,8 +216,7 @@ class HifiGanGeneratorHIP(torch.nn.Module):
         if noise is not None:
             ri = noise["rand_ini"].to(dev).contiguous().float()
             sn = noise["sine_noise"].to(dev).contiguous().float()
-        L.check(lib.ss_hifigan_forward(ctypes.addressof(hg), L.ptr(mel), L.ptr(f0), L.ptr(lens), B, T, L.ptr(ri), L.ptr(sn), seed,
-                                       L.ptr(wav), L.ptr(har), L.ptr(ws), ws_bytes, L.stream_ptr()), "ss_hifigan_forward")
+        L.ops.ss_hifigan_forward(hg, mel, f0, lens, B, T, ri, sn, seed, wav, har, ws, ws_bytes)
         return (wav, har) if return_source else wav
 
 

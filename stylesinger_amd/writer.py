@@ -24,13 +24,12 @@ def wav_to_pcm16(wav, lens=None, hop=1, norm=False):
     wav = wav.contiguous().float()
     B, n = wav.shape
     pcm = torch.empty(B, n, device=wav.device, dtype=torch.int16)
-    lib = L.load()
     if norm:
         peak = wav.abs().amax(dim=1).clamp_min(1e-20).cpu().tolist()
         for b in range(B):
-            L.check(lib.ss_wav_to_pcm16(L.ptr(wav[b]), L.ptr(pcm[b]), n, float(np.float32(32767.0) / np.float32(peak[b])), L.stream_ptr()), "pcm16")
+            L.ops.ss_wav_to_pcm16(wav[b], pcm[b], n, float(np.float32(32767.0) / np.float32(peak[b])))
     else:
-        L.check(lib.ss_wav_to_pcm16(L.ptr(wav), L.ptr(pcm), B * n, 32767.0, L.stream_ptr()), "pcm16")
+        L.ops.ss_wav_to_pcm16(wav, pcm, B * n, 32767.0)
     if lens is not None:
         idx = torch.arange(n, device=wav.device)[None, :]
         pcm.masked_fill_(idx >= (lens.to(torch.int64) * hop)[:, None], 0)
