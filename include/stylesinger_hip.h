@@ -388,13 +388,21 @@ int ss_gemm_bf16_tile256_ok(const ss_gemm_bf16_args* args);
  * The residual stream lives in a layout of its own, written by ss_layer512_entry and by this launch only:
  *   H  = fp16(x + dstep_l), the conv's operand, in slot-major tiles: [tile = b * ceil(T / 128) + t / 128][slot 32][row 128] x 8 channels
  *      (slot s = channels 8 s .. 8 s + 7), ss_layer512_h_elems(B, T) elements. DOUBLE BUFFERED: Hout must differ from Hin (a tile reads halo
- *      rows its neighbours rewrite). Rows >= lens[b] are zero (every producer masks them);
+ *      rows its neighbours rewrite). Rows >= lens[b] - and rows [T, 128 ceil(T / 128)) of an item's last tile - MUST BE ZERO BITS: ss_layer512 is the one
+ *      member of the family whose operand must arrive masked. Its DMA fetches those rows like any other (they are the conv's padding at the end of
+ *      an item), unlike ss_gemm_bf16 and its many-round forms, whose zero padding is their own. ss_layer512_entry writes them as zeros, and so does
+ *      this launch's stream epilogue with mask_rows = 1; the fused form (Hout != NULL) with lens therefore REFUSES mask_rows = 0, which would leave the
+ *      unmasked stream in rows [lens[b], T) of Hout for the next layer's halo. The gate-only form writes no H and accepts mask_rows = 0
+ *      (tests/test_gpu_layer512_edges.py: written zeros over the padded tiles after every launch, chains of launches, items alone against the batch);
  *   P  = R, the fp16 REMAINDER of the stream: x = (H - dstep_l) + R with H = fp16(x + dstep_l) as above and R = fp16(x - (H - dstep_l)) - 22
  *      significant bits, as the fp16 pair of the two-launch form - in accumulator order, ss_layer512_stream_bytes(B, T) bytes, updated in place:
  *      [tile][m 4][q 4][wave 8][lane 64] x 4 fp16; lane (l31, lh) of (wave, m, q) holds channels 32 wave + 8 q + 4 lh .. + 3 of row 32 m + l31 of
  *      the tile. The launch takes the H term of its own rows from the activation tile it staged anyway, so the stream costs 2 bytes per element of
  *      HBM traffic each way (first form of round 6: an fp32 copy, 4 bytes each way - 256 of the 584 KB a tile moved). cur_bias = dstep_l and
- *      next_bias = dstep_(l+1) are the two biases of that representation.
+ *      next_bias = dstep_(l+1) are the two biases of that representation. The update, in fp32, sums the SMALL terms first so that one rounding
+ *      happens at the stream's own magnitude: s = (R - cur_bias) + (acc * out_scale + bias_r); x' = fma(H, post_scale, s * post_scale);
+ *      H' = fp16(x' + next_bias); R' = fp16((x' - H') + next_bias) (x' - H' is exact). Within 8e-6 of float64 while |x' + next_bias| < 64
+ *      (tests/layer512_refs.py stream_fp32; the order (H - cur_bias) + R first rounds four times there: 8.6e-6 at |x| = 51).
  * Hout == NULL: gate only (the last layer: its residual stream is never read); P and Wr are then unused. */
 typedef struct ss_layer512_args {
   const uint16_t* Hin;      /* fp16(x + dstep_l), slot-major tiles */
@@ -402,7 +410,7 @@ typedef struct ss_layer512_args {
   int32_t n_products;       /* weight terms per element = matrix products per GEMM: 2 (or 0) = "fp16x2" (hi, lo); 1 = "fp16sd": Wg / Wr hold ONE fp16 term
                              * (packs made with n_products = 1; the caller cycles noise-shaped weight sets over the evaluations, ss_wavenet.n_wsets) */
   uint16_t* Hout;           /* fp16(x' + next_bias), or NULL */
-  void* P;                  /* fp32 stream x, read and rewritten in place (x') */
+  void* P;                  /* R, the fp16 remainder of the stream (x = (H - cur_bias) + R), accumulator order; read and rewritten in place (R' of x') */
   const int32_t* lens;
   int32_t B, T;
   const uint16_t* Wg;       /* ss_layer512_pack_gate of the layer's ss_split_f16 dilated-conv pack (786 432 elements) */
@@ -412,7 +420,7 @@ typedef struct ss_layer512_args {
                              * g_compact the 256 channels contiguously (ldg >= 256) - the skip GEMM's a_compact operand */
   int64_t g_batch_stride;
   int32_t ldg;
-  int32_t mask_rows;        /* rows >= lens[b]: G = 0, stream = 0 */
+  int32_t mask_rows;        /* rows >= lens[b]: G = 0, Hout = 0, R = 0. 0 is accepted in the gate-only form (or without lens) only */
   const float* bias_r;      /* [256] residual half of the output-projection bias, or NULL */
   const float* next_bias;   /* [256] dstep_{l+1}, or NULL */
   int32_t g_compact;        /* 1: G rows are compact (see G) */

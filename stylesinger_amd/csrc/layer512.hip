@@ -19,17 +19,21 @@
 //   * Persistent workgroups (one per CU, 144 KB of LDS = two 72 KB regions): region r holds A(tile i), then G(tile i) over it; the A tile of
 //     tile i + 1 lands in the other region while tile i's epilogues run. Three barriers per tile.
 //   * The residual stream has a layout of its own (nothing but this kernel and ss_layer512_entry touches it): H = fp16(x + dstep_l) - what the
-//     conv's DMA fetches - in SLOT-MAJOR tiles [tile][slot 32][row 128] x 16 bytes (slot = 8 channels), and P = x itself in FP32 in accumulator
-//     order (16 bytes per lane = 4 channels; 1 KB per wave instruction) for the epilogue's read-modify-write. The LDS image of a tile is
+//     conv's DMA fetches - in SLOT-MAJOR tiles [tile][slot 32][row 128] x 16 bytes (slot = 8 channels), and P = R, the FP16 REMAINDER of the stream
+//     (x = (H - dstep_l) + R, R = fp16(x - (H - dstep_l)): 22 significant bits) in accumulator order (8 bytes per lane = 4 channels; 512 B per wave
+//     instruction) for the epilogue's read-modify-write; the H term of a tile's own rows is taken from the staged activation tile. The LDS image of a tile is
 //     slot-major too, so the DMA moves contiguous kilobytes, the fragment reads are conflict-free without a swizzle, and the epilogue's 8-byte
 //     H stores of a wave instruction tile 512 contiguous bytes. H is double buffered (Hin -> Hout): a tile reads 8 halo rows of its
 //     neighbours, which another workgroup rewrites; P is updated in place. (History: v0 read and wrote ss_gemm_bf16's pair layout as 8-byte vectors, 32 rows per
 //     instruction - the epilogue took 165 us per launch against the projection launch's 129; v1 kept the stream as an fp16 (hi, lo) pair in
 //     accumulator order - 16 VALU instructions per element to unpack / re-split, 7.5 k cycles per tile, profiles/r06_trace_layer512_v1_fused.log.
-//     The fp32 stream costs the same 4 bytes per element, 5 instructions, and is 2 bits MORE precise than the pair.)
+//     v2 kept an fp32 copy of the stream: 4 bytes per element each way, 256 of the 584 KB a tile moved; the (H, R) form moves 2.)
+//     ZERO PADDING IS NOT THIS KERNEL'S OWN, unlike the rest of the ss_gemm_bf16 family: rows [lens[b], T) and [T, 128 ceil(T / 128)) of Hin are fetched
+//     like any other row and must hold zero bits. ss_layer512_entry and this kernel's stream epilogue (mask_rows = 1) write them; the launcher refuses
+//     the fused form with lens and mask_rows = 0 (tests/test_gpu_layer512_edges.py holds every launch to written zeros over the padded tiles).
 // Arithmetic contract = ss_gemm_bf16 with split = 2: a * hi + a * lo of fp16 terms (weights = pairs of w * 2^s), fp32 accumulation scaled by
-// out_scale; G = fp16(g) in the hi slots of the pair layout; the conv's operand fp16(x + dstep_l); the stream itself fp32 (the two-launch form
-// keeps it as an fp16 pair = 22 bits). Results equal those of the two-launch form up to the
+// out_scale; G = fp16(g) in the hi slots of the pair layout; the conv's operand fp16(x + dstep_l); the stream itself the pair (H, R) = 22 bits, as the two-launch
+// form's fp16 pair, updated in fp32. Results equal those of the two-launch form up to the
 // fp32 summation order (tests/test_gpu_layer512.py: both against float64 of the same terms).
 #include "common.h"
 #include "device_prims.h"
@@ -440,10 +444,14 @@ __global__ __launch_bounds__(512, 2) void layer512_kernel(const ss_layer512_args
           for (int e = 0; e < 4; ++e) {
             // no contraction here: every term is rounded where the next layer's epilogue (and the other tile schedules) round it
 #pragma clang fp contract(off)
-            const float xo = (ss_t2f_packed<true>(hown[m][q][e >> 1], e & 1) - cb[q][e]) + ss_t2f_packed<true>(rv[m][q][e >> 1], e & 1);
-            const float xn = (xo + fmaf(acc2[m][4 * q + e], a.out_scale, bs[q][e])) * a.post_scale;
+            // ... and the SMALL terms are summed first, so that only ONE rounding happens at the stream's own magnitude: with (H - cb) + R, + the
+            // projection, * post_scale - four roundings of half an ulp of |x| each - a stream of |x| = 51 was 8.6e-6 off float64 (bar 8e-6, worded for
+            // |x| <~ 16: tests/test_gpu_layer512_edges.py, saturate-d2); this order is 5.9e-6 there and about half the former error at unit scale, with the
+            // same five operations. x' - H' is exact (both are multiples of x's ulp and less than 2^24 of them apart), so R' costs one fp16 rounding.
+            const float sm = (ss_t2f_packed<true>(rv[m][q][e >> 1], e & 1) - cb[q][e]) + fmaf(acc2[m][4 * q + e], a.out_scale, bs[q][e]);
+            const float xn = fmaf(ss_t2f_packed<true>(hown[m][q][e >> 1], e & 1), a.post_scale, sm * a.post_scale);
             const uint16_t hh = ss_f2t<true>(pad ? 0.f : xn + nb[q][e]);
-            const uint16_t rr = ss_f2t<true>(pad ? 0.f : xn - (ss_t2f<true>(hh) - nb[q][e]));
+            const uint16_t rr = ss_f2t<true>(pad ? 0.f : (xn - ss_t2f<true>(hh)) + nb[q][e]);
             hp[e >> 1] |= (uint32_t)hh << (16 * (e & 1));
             rp[e >> 1] |= (uint32_t)rr << (16 * (e & 1));
           }
@@ -676,6 +684,10 @@ extern "C" int ss_layer512(const ss_layer512_args* args, void* stream) {
                  "ss_layer512: the fused form needs Wr, P and an Hout buffer different from Hin (tiles read their neighbours' halo rows)");
     SS_CHECK_ARG((!a.bias_r || (((uintptr_t)a.bias_r) & 15) == 0) && (!a.next_bias || (((uintptr_t)a.next_bias) & 15) == 0) &&
                      (!a.cur_bias || (((uintptr_t)a.cur_bias) & 15) == 0), "ss_layer512: bias vectors must be 16-byte aligned");
+    // the conv's DMA fetches rows [lens[b], T) of Hin like any other row: the H layout REQUIRES zero rows past lens[b], and with mask_rows = 0 this
+    // launch would write the unmasked stream there for the next layer's halo to read (the gate-only form writes no H: it keeps the option)
+    SS_CHECK_ARG(a.mask_rows || !a.lens, "ss_layer512: the fused form (Hout != NULL) with lens needs mask_rows = 1: the H layout requires zero rows past lens[b], "
+                                         "which the next layer's halo reads as the conv's padding");
   }
   const int tpi = ss_cdiv(a.T, BM);
   const int n_tiles = tpi * a.B;

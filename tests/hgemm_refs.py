@@ -11,7 +11,9 @@ What is stated here:
   * `pack_addend`: the packed (gate-interleaved) column order of the conditioner addend, of the GATE bias and of the packed weight rows;
   * `reference`: float64 "of the same terms" for GATE, RESX (fp32 stream and pair-only stream) and STORE:
         split 0: the rounded operands;  split 1: hi*hi + hi*mid + mid*hi;  split 2: (a_hi*w_hi + a_hi*w_lo) * out_scale;
-        one_product: a_hi*w_hi only.
+        one_product: a_hi*w_hi only;  split 3 ("fp16q4", ss_gemm_bf16_gate128q / _tile256q): (a_hi*w_hi + fp4(a_hi / q_scale)*q_scale*lo_q) * out_scale
+        with lo_q = the block-scaled fp4 image of the weights' lo plane (stylesinger_amd.lib.pack_gate_q4 / pack_skip_q4, which run on the host;
+        the block order comes from the built library's ss_gate128q_kindex / ss_tile256q_kindex, so these cases need the library - not a GPU).
     It zero-pads outside [0, len) of every item ITSELF: what the input holds in rows >= len never reaches the result.
   * `CASES`: name -> the launch (kernel, split, epilogue, shape, lens, taps, groups, gate_mode, mask_rows), iterated by both test files.
 """
@@ -88,16 +90,22 @@ ONE_ROW = dict(B=1, T=1, lens=(1,))
 CASES = {}
 
 
+Q_SCALE_GATE = 2.0               # the fixed fp4 scale of the gate's A operand (the stream x + dstep; ss_wavenet.q_scale_gate)
+Q_SCALE_STORE = 2.0 ** -2        # ... of the skip GEMM's (gate outputs in (-1, 1))
+
+
 def _add(name, kernel, split, epi, shape, *, taps, K=256, N=256, group_size=0, gate_mode=0, mask_rows=True, act="none", one_product=0,
          a_compact=False):
     assert name not in CASES, name
     CASES[name] = dict(name=name, kernel=kernel, split=split, epi=epi, B=shape["B"], T=shape["T"], lens=shape["lens"], taps=tuple(taps), K=K, N=N,
                        Np=2 * N if epi == "gate" else N, group_size=group_size, gate_mode=gate_mode, mask_rows=mask_rows, act=act,
                        one_product=one_product, a_compact=a_compact)
+    if split == 3:   # (a key of the fp16q4 cases only: the other cases keep their data_key, that is their inputs)
+        CASES[name]["q_scale"] = Q_SCALE_GATE if epi == "gate" else Q_SCALE_STORE
 
 
 def _gate_kernels():
-    return [("generic", s) for s in (0, 1, 2)] + [("gate256", s) for s in (0, 1, 2)] + [("gate128", 2)]
+    return [("generic", s) for s in (0, 1, 2)] + [("gate256", s) for s in (0, 1, 2)] + [("gate128", 2), ("gate128q", 3)]
 
 
 def _build_cases():
@@ -129,6 +137,10 @@ def _build_cases():
     _add("store-tile256-s2-compact-k192-relu-edge256", "tile256", 2, "store", EDGE256, taps=(0,), K=192, act="relu", one_product=2, a_compact=True)
     _add("resxpair-tile256-s2-partial-nolens", "tile256", 2, "resx_pair", PARTIAL, taps=(0,))
     _add("store-tile256-s2-relu-partial-nolens", "tile256", 2, "store", PARTIAL, taps=(0,), K=512, act="relu")
+    # the fp16q4 skip GEMM (256-row tiles, as gemm_bf16_tile256q.hip's BM)
+    _add("store-tile256q-s3-relu-edge256", "tile256q", 3, "store", EDGE256, taps=(0,), K=512, act="relu")
+    _add("store-tile256q-s3-k192-none-edge256", "tile256q", 3, "store", EDGE256, taps=(0,), K=192, act="none")
+    _add("store-tile256q-s3-relu-partial-nolens", "tile256q", 3, "store", PARTIAL, taps=(0,), K=512, act="relu")
     for s in (0, 2):   # the ntaps = 4 loop with a partial column tile
         _add(f"store-generic-s{s}-4taps-edge256", "generic", s, "store", EDGE256, taps=(-3, 0, 1, 5), K=64, N=96, act="none")
     # weight groups: two items per group, two weight / bias / next_bias / cur_bias sets
@@ -140,6 +152,11 @@ def _build_cases():
     for kern in ("generic", "gate256", "gate128"):
         _add(f"gate-{kern}-s2-d1-mode1", kern, 2, "gate", EDGE256, taps=(-1, 0, 1), gate_mode=1)
         _add(f"gate-{kern}-s2-d8-nomask", kern, 2, "gate", EDGE256, taps=(-8, 0, 8), mask_rows=False)
+    # both fp16q4 launchers accept weight groups, ss_gemm_bf16_gate128q gate_mode = 1 and mask_rows = 0 as well: cases, not refusals
+    _add("gate-gate128q-s3-d2-groups", "gate128q", 3, "gate", EDGE256, taps=(-2, 0, 2), group_size=2)
+    _add("gate-gate128q-s3-d1-mode1", "gate128q", 3, "gate", EDGE256, taps=(-1, 0, 1), gate_mode=1)
+    _add("gate-gate128q-s3-d8-nomask", "gate128q", 3, "gate", EDGE256, taps=(-8, 0, 8), mask_rows=False)
+    _add("store-tile256q-s3-relu-groups", "tile256q", 3, "store", EDGE256, taps=(0,), K=512, act="relu", group_size=2)
 
 
 _build_cases()
@@ -171,11 +188,11 @@ def n_row_tiles(case):
 
 
 def term_dtype(case):
-    return torch.float16 if case["split"] == 2 else torch.bfloat16
+    return torch.float16 if case["split"] >= 2 else torch.bfloat16
 
 
 def out_scale(case):
-    return 2.0 ** -WSHIFT if case["split"] == 2 else 1.0
+    return 2.0 ** -WSHIFT if case["split"] >= 2 else 1.0
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -190,7 +207,8 @@ def make_inputs(case):
     g = torch.Generator(device="cpu").manual_seed(zlib.crc32(data_key(case).encode()))
     B, T, K, N, G = case["B"], case["T"], case["K"], case["N"], n_groups(case)
     nt, rows_out = len(case["taps"]), (2 * N if case["epi"] == "gate" else N)
-    d = dict(x=torch.randn(B, T, K, generator=g) * 3.0,
+    d = dict(x=torch.randn(B, T, K, generator=g) * 3.0 if not (case["split"] == 3 and case["epi"] == "store") else
+             torch.rand(B, T, K, generator=g) * 2.0 - 1.0,                 # the fp16q4 skip GEMM's operand is a gate output: (-1, 1) against q_scale = 2^-2
              w=torch.randn(G, rows_out, K, nt, generator=g) / (nt * K) ** 0.5,
              bias=torch.randn(G, rows_out, generator=g) * 0.1)
     if case["epi"] == "gate":
@@ -241,9 +259,40 @@ def products(case, x, w, exact=False):
         return [(ah.double(), wh.double()), (ah.double(), wm.double()), (am.double(), wh.double())], 1.0
     ah = _rne(x, torch.float16).double()
     wh, wl = split_terms(w, torch.float16, 2.0 ** WSHIFT)
+    if s == 3:
+        from stylesinger_amd import lib
+        qs = case["q_scale"]
+        _, mag = lib.fp4_rne(_rne(x, torch.float16) / qs)
+        aq = (mag * torch.sign(ah.float()) * qs).double()
+        return [(ah, wh.double()), (aq, lo_q4(case, w).double())], 2.0 ** -WSHIFT
     if case["one_product"]:
         return [(ah, wh.double())], 2.0 ** -WSHIFT
     return [(ah, wh.double()), (ah, wl.double())], 2.0 ** -WSHIFT
+
+
+_LO_Q = {}
+
+
+def unpack_addend(Ep, N):
+    """inverse of pack_addend"""
+    v = Ep.reshape(*Ep.shape[:-1], N // 32, 2, 32)
+    return torch.cat([v[..., 0, :].reshape(*Ep.shape[:-1], N), v[..., 1, :].reshape(*Ep.shape[:-1], N)], dim=-1)
+
+
+def lo_q4(case, w):
+    """w [rows_out, K, ntaps] -> the values the block-scaled product sees for the weights' lo plane, in w's own index order. The packers work
+    on the packed matrix [Np][ntaps * K] (gate: packed row order, tap-major columns) and quantise per 32-element block of the kernel's order."""
+    from stylesinger_amd import lib
+    key = (case["epi"], tuple(w.shape), float(w.double().sum()), float(w.double().abs().sum()))
+    if key not in _LO_Q:
+        rows, K, nt = w.shape
+        if case["epi"] == "gate":
+            Wp = pack_addend(w.permute(2, 1, 0), rows // 2).permute(2, 0, 1).reshape(rows, nt * K).contiguous()    # [packed row][tap * K + c]
+            lo = lib.pack_gate_q4(Wp, shift=WSHIFT)[1].reshape(rows, nt, K).permute(1, 2, 0)                         # [tap][c][packed row]
+            _LO_Q[key] = unpack_addend(lo, rows // 2).permute(2, 1, 0).contiguous()
+        else:
+            _LO_Q[key] = lib.pack_skip_q4(w[:, :, 0].contiguous(), shift=WSHIFT)[1][:, :, None]
+    return _LO_Q[key]
 
 
 def accumulate(case, x, w, *, exact=False, rows=None, taps=None, pad=True, leak=False, other_group=False):
@@ -324,7 +373,7 @@ def gpu_bars(case):
     """output name -> max-abs bar against `reference` (GATE with split 0 additionally: mean |C - bf16(ref)| <= 2e-4, asserted by the test)"""
     s, K = case["split"], len(case["taps"]) * case["K"]
     if case["epi"] == "gate":
-        return dict(C={0: 4e-3 + 1e-6, 1: 2e-5, 2: 3e-4}[s])
+        return dict(C={0: 4e-3 + 1e-6, 1: 2e-5, 2: 3e-4, 3: 3e-4}[s])     # 3: the bar of tests/test_gpu_fp16q4.py
     if case["epi"] == "store":
         return dict(C=2e-5 * math.sqrt(K))
     y = 0.04 if s == 0 else 1e-4 if s == 1 else 1e-5    # split 0: Y is ONE bf16 term of |y| < 8 (half an ulp = 2^-7 = 0.008; the bar of tests/test_gpu_round2.py)
@@ -340,13 +389,16 @@ def exact_bar(case):
     random walk); the bar is 8 rms (a million outputs stay under 5.5 rms), times post_scale < 1 or a gate slope <= 1.
       split 0: both operands to bf16: u_eff = sqrt(2) * 2^-9 / sqrt(3)
       split 1: mid * mid dropped (2^-18 relative) and the second terms rounded (2^-17 relative to the value, both operands): u_eff = 2^-16
-      split 2: activations to fp16 (2^-11), weights a 22-bit pair: u_eff = 2^-11 / sqrt(3); one weight term: sqrt(2) * 2^-11 / sqrt(3)"""
+      split 2: activations to fp16 (2^-11), weights a 22-bit pair: u_eff = 2^-11 / sqrt(3); one weight term: sqrt(2) * 2^-11 / sqrt(3)
+      split 3: the second product runs on fp4 images: of the weights' lo plane (2 to 3 bits of a 2^-11 correction) and of the activations
+               (which saturate at 6 q_scale), so it recovers PART of the lo plane: bounded by the one-term form. GATE: the project's 4e-3 too
+               (tests/test_gpu_fp16q4.py). The STORE operand is uniform in (-1, 1): rms 1 / sqrt(3) instead of 3."""
     s = case["split"]
-    if case["epi"] == "gate" and s in (1, 2):
+    if case["epi"] == "gate" and s in (1, 2, 3):
         return 2e-4 if s == 1 else 4e-3
     u = {0: math.sqrt(2.0) * 2.0 ** -9 / math.sqrt(3.0), 1: 2.0 ** -16,
-         2: (math.sqrt(2.0) if case["one_product"] else 1.0) * 2.0 ** -11 / math.sqrt(3.0)}[s]
-    return 8.0 * 3.0 * u
+         2: (math.sqrt(2.0) if case["one_product"] else 1.0) * 2.0 ** -11 / math.sqrt(3.0), 3: math.sqrt(2.0) * 2.0 ** -11 / math.sqrt(3.0)}[s]
+    return 8.0 * (3.0 if s != 3 else 1.0 / math.sqrt(3.0)) * u
 
 
 def edge_rows(case):

@@ -1,5 +1,5 @@
 """The 16-bit matrix-core GEMM family at every dilation and tile edge: ss_gemm_bf16 (generic kernel, 64 x 128 and 128 x 128 tiles),
-ss_gemm_bf16_gate256 (<4,0>, <8,1>, <8,2>), ss_gemm_bf16_gate128 and ss_gemm_bf16_tile256 against the float64 references "of the same terms"
+ss_gemm_bf16_gate256 (<4,0>, <8,1>, <8,2>), ss_gemm_bf16_gate128, ss_gemm_bf16_tile256 and the fp16q4 pair ss_gemm_bf16_gate128q / _tile256q against the float64 references "of the same terms"
 in tests/hgemm_refs.py, over its `CASES` table (tests/test_hgemm_refs_cpu.py checks the table and the references without a GPU).
 
 Every case is launched twice: with rows >= lens[b] of the A operand zeroed, and with them holding +-1000 (in the fp16 forms the A operand's
@@ -19,7 +19,7 @@ from stylesinger_amd import lib as L  # noqa: E402
 
 CASES = H.CASES
 DEV = "cuda:0"
-SELECT = dict(generic=False, gate256=True, gate128=128, tile256=True)   # lib.gemm_bf16's gate256= selector
+SELECT = dict(generic=False, gate256=True, gate128=128, tile256=True, gate128q=128, tile256q=True)   # lib.gemm_bf16's gate256= selector (+ split = 3)
 OK_FNS = ("ss_gemm_bf16_gate128_ok", "ss_gemm_bf16_gate256_ok", "ss_gemm_bf16_tile256_ok")
 
 
@@ -42,7 +42,7 @@ def _bits(t):
 
 
 def _operand(case, x):
-    return L.to_bf16(x) if case["split"] == 0 else L.split_bf16(x) if case["split"] == 1 else L.split_f16(x)
+    return L.to_bf16(x) if case["split"] == 0 else L.split_bf16(x) if case["split"] == 1 else L.split_f16(x)   # split 2 and 3: the fp16 pair
 
 
 def _weights(case, inp):
@@ -55,6 +55,8 @@ def _weights(case, inp):
             W = L.to_bf16(Wp)
         elif case["split"] == 1:
             W = L.split_bf16(Wp)
+        elif case["split"] == 3:   # the lo plane as block-scaled fp4 in the kernel's lane order
+            W = (L.pack_gate_q4 if case["epi"] == "gate" else L.pack_skip_q4)(Wp, shift=H.WSHIFT)[0]
         else:
             W = L.split_f16(Wp, scale=2.0 ** H.WSHIFT)
             if case["one_product"]:
@@ -87,12 +89,12 @@ def _launch(case, inp, poison, lib_spy=None):
             if n:
                 sign = 1.0 - 2.0 * ((torch.arange(n, device=DEV)[:, None] + cols[None, :]) % 2).float()
                 A[b, lens_l[b]:] = (H.POISON * sign).to(A.dtype)
-        if s == 2 and not case["a_compact"]:
+        if s >= 2 and not case["a_compact"]:
             A.view(B, T, -1, 64)[..., 32:] = H.POISON                      # the second plane of EVERY row: never fetched
     W, w_gs = _weights(case, inp)
     kw = dict(B=B, T=T, K=K, taps=case["taps"], N=N, Np=case["Np"], lens=lens, split=s, out_scale=H.out_scale(case), gate256=SELECT[case["kernel"]],
               mask_rows=case["mask_rows"], gate_mode=case["gate_mode"], one_product=case["one_product"], a_compact=case["a_compact"],
-              group_size=case["group_size"], w_gs=w_gs if case["group_size"] else 0)
+              group_size=case["group_size"], w_gs=w_gs if case["group_size"] else 0, q_scale=case.get("q_scale", 0.0))
     out = {}
     if case["epi"] == "gate":
         bias, bgs = _per_group(case, H.pack_addend(inp["bias"], N))
@@ -154,7 +156,7 @@ def _values(case, raw):
                 out[k] = mine.double().cpu()
             else:
                 hi, lo = (p.double().cpu() for p in L.split_planes(mine))
-                if s == 2:
+                if s >= 2:
                     assert torch.all(lo == H.SENTINEL), "the gate output's second plane is not written in the fp16 forms"
                 out[k] = hi + lo if s == 1 else hi
         elif case["epi"] == "store":

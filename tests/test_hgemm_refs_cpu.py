@@ -51,6 +51,27 @@ def test_operand_forms_are_the_documented_terms_and_layout():
     assert Ep[0, :32].tolist() == list(range(32)) and Ep[0, 32:64].tolist() == list(range(64, 96)) and Ep[0, 64:96].tolist() == list(range(32, 64))
 
 
+@pytest.mark.parametrize("name", ["gate-gate128q-s3-d4-edge256", "store-tile256q-s3-k192-none-edge256"])
+def test_fp4_image_of_the_lo_plane_sits_in_the_weights_own_index_order(name):
+    """lo_q4 maps the packers' [packed row][tap-major K] image back to w's [row][channel][tap]: element by element it must be the fp4 image of
+    THAT element's lo term (a permuted image would still pass every bar of a 2^-11 correction)"""
+    case = CASES[name]
+    w = H.make_inputs(case)["w"][0]
+    ws = w.float() * 2.0 ** H.WSHIFT
+    lo = (ws - ws.half().float()).double()
+    lo_q = H.lo_q4(case, w).double()
+    assert lo_q.shape == lo.shape
+    rel = float((lo_q - lo).abs().max() / lo.abs().max())
+    assert rel <= 0.26, rel                                  # the bound tests/test_gpu_fp16q4.py holds the packers to
+    assert float((lo_q - lo).pow(2).mean().sqrt() / lo.pow(2).mean().sqrt()) <= 0.15
+    prods, scale = H.products(case, H.make_inputs(case)["x"][0], w)
+    assert len(prods) == 2 and scale == 2.0 ** -H.WSHIFT
+    ah, aq = prods[0][0], prods[1][0]
+    inside = ah.abs() <= 4.0 * case["q_scale"]               # the grid steps by at most 1 below 4: half a step
+    assert bool(inside.any()) and float((aq - ah).abs()[inside].max()) <= 0.5 * case["q_scale"]
+    assert float(aq.abs().max()) <= 6.0 * case["q_scale"]    # ... and saturates at 6
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # the references are the right operation, and blind to the tails
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -90,10 +111,10 @@ def _forms():
 
 
 def test_the_generic_cases_land_on_both_tile_forms():
-    assert set(_forms()) == {"generic64", "generic128", "gate256", "gate128", "tile256"}
+    assert set(_forms()) == {"generic64", "generic128", "gate256", "gate128", "tile256", "gate128q", "tile256q"}
 
 
-@pytest.mark.parametrize("form", ["generic64", "generic128", "gate256", "gate128", "tile256"])
+@pytest.mark.parametrize("form", ["generic64", "generic128", "gate256", "gate128", "tile256", "gate128q", "tile256q"])
 def test_every_kernel_form_meets_every_tile_edge(form):
     cases = _forms()[form]
     tile = H.tile_rows(cases[0])
@@ -120,7 +141,7 @@ def test_every_gate_kernel_sees_every_dilation_and_every_mode():
         assert {1, 2, 4, 8} <= on_edges, (kern, s, on_edges)
         assert all(c["taps"][2] <= H.HALO for c in mine) or kern == "generic"
         assert any(c["T"] == 1 for c in mine) and any(c["lens"] is None for c in mine)
-    for kern in ("generic", "gate256", "gate128"):
+    for kern in ("generic", "gate256", "gate128", "gate128q"):
         mine = [c for c in CASES.values() if c["epi"] == "gate" and c["kernel"] == kern]
         assert any(c["gate_mode"] == 1 for c in mine) and any(not c["mask_rows"] for c in mine) and any(c["group_size"] for c in mine), kern
     assert any(c["taps"][-1] > H.HALO for c in CASES.values() if c["kernel"] == "generic" and c["epi"] == "gate")
@@ -188,6 +209,6 @@ def test_wrong_gate_references_stand_ten_tolerances_off(name):
 
 
 def test_every_fault_kind_is_reached_on_every_gate_kernel():
-    for kern in ("generic", "gate256", "gate128"):
+    for kern in ("generic", "gate256", "gate128", "gate128q"):
         for kind in FAULTS:
             assert any(bool(m.any()) for n in GATE_CASES if CASES[n]["kernel"] == kern for m in _fault_rows(CASES[n], kind)), (kern, kind)
