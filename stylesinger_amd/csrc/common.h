@@ -74,8 +74,13 @@ int ss_q4_guard_launch(const ss_gemm_bf16_args* a, int which, void* stream);
 // workgroup layers per CU, so the count must be the device's, not MI355X's
 int ss_n_cu();
 struct ss_conv_gemm_args;
-// gemm16.hip, library-internal: split-K skip GEMM without its reduction launch (the tail kernels of diffusion.hip add the slices)
+// gemm16.hip, library-internal: split-K skip GEMM without its reduction launch (the tail kernels of f0_sampler.hip / mel_sampler.hip add the slices)
 int ss_gemm16_store_partials(const ss_conv_gemm_args* args, int mt, int ksplit, float* partials, void* stream);
+// gemm_bf16_tile256.hip, library-internal: the shape half of ss_gemm_bf16_tile256_ok - (B, T) gives at least two rounds of 256-row tiles
+bool ss_gemm_bf16_tile256_rounds_ok(int B, int T);
+// wino43_gate16.hip, library-internal: the MT a launch of (B, T, Np, dilation, Kp) runs when it is asked for `mt` - an explicit mt as it is;
+// mt = 0: ss_wino43_gate16_pick's, with MT = 1 outside the K-staged form demoted to 2 (0 = the launch goes to the 32x32x2 kernel)
+int ss_wino43_gate16_mt(int B, int T, int Np, int dilation, int Kp, int mt);
 
 // ----------------------------------------------------------------------------------------------
 // Device math. Activations follow the torch CPU definitions the reference relies on.

@@ -516,7 +516,7 @@ extern "C" int ss_gemm16_store_splitk(const ss_conv_gemm_args* args, int mt, int
   return gemm16_store_impl(args, mt, ksplit, partials, stream, "ss_gemm16_store_splitk");
 }
 
-// library-internal (diffusion.hip): the split-K launch WITHOUT the reduction - the consumer (f0_tail_kernel / mel_tail_kernel) adds the slices itself,
+// library-internal (wavenet_stack.hip): the split-K launch WITHOUT the reduction - the consumer (f0_tail_kernel / mel_tail_kernel) adds the slices itself,
 // in the same order and with the same bias / ReLU / row mask as splitk_reduce_kernel
 int ss_gemm16_store_partials(const ss_conv_gemm_args* args, int mt, int ksplit, float* partials, void* stream) {
   return gemm16_store_impl(args, mt, ksplit, partials, stream, "ss_gemm16_store_partials", false);

@@ -355,6 +355,8 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
 
 }  // namespace
 
+bool ss_gemm_bf16_tile256_rounds_ok(int B, int T) { return (long)ss_cdiv(T, BM) * B >= 2L * ss_n_cu(); }
+
 // 1 if ss_gemm_bf16 should hand this launch to the 256-row kernel: split operands, one tap, STORE or RESX on the pair-only stream, N <= 256,
 // an even number of 32-channel chunks, and at least two rounds of 256-row tiles
 extern "C" int ss_gemm_bf16_tile256_ok(const ss_gemm_bf16_args* a) {
@@ -365,7 +367,7 @@ extern "C" int ss_gemm_bf16_tile256_ok(const ss_gemm_bf16_args* a) {
   if (a->N > BN || (a->K % 64) != 0 || a->lda < (a->a_compact ? 1 : 2) * a->K || (a->lda % 8) != 0) return 0;
   if ((int64_t)a->T * a->lda * 2 >= (1ll << 31) || (int64_t)a->T * a->ldc * 4 >= (1ll << 31) || (int64_t)a->T * a->ldy * 2 >= (1ll << 31) ||
       (int64_t)a->Np * a->K * 4 >= (1ll << 31)) return 0;
-  return (long)ss_cdiv(a->T, BM) * a->B >= 2L * ss_n_cu() ? 1 : 0;
+  return ss_gemm_bf16_tile256_rounds_ok(a->B, a->T) ? 1 : 0;
 }
 
 extern "C" int ss_gemm_bf16_tile256(const ss_gemm_bf16_args* args, void* stream) {

@@ -9,17 +9,13 @@
 //     with a hierarchical scan: per-frame closed form for the first cumsum (the per-sample phase
 //     increment is constant inside a hop), a per-chain scan over frames, and an in-block double scan
 //     for the wrapped second cumsum.
-#include "common.h"
-#include "../../include/stylesinger_hip.h"
+#include "launch_args.h"
 
 namespace {
 
 constexpr int NH = 9;      // fundamental + 8 overtones (hifigan_nsf.py:112)
 constexpr int HOP_MAX = 1024;
 constexpr size_t LDS_MAX = 160 * 1024;  // LDS of one CU: the most a workgroup can ask for
-
-inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-inline int round_up32(int x) { return (x + 31) / 32 * 32; }
 
 struct HgWs {
   int32_t* lens;  // [(n_ups+1)][B]
@@ -345,21 +341,6 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
   wav[(int64_t)b * L + i] = (i < valid) ? tanhf(acc) : 0.f;
 }
 
-inline ss_conv_gemm_args base_args(int B, int T, const int32_t* lens) {
-  ss_conv_gemm_args a;
-  memset(&a, 0, sizeof(a));
-  a.B = B;
-  a.T = T;
-  a.lens = lens;
-  a.ntaps = 1;
-  a.a_scale = 1.0f;
-  a.a_lrelu = 1.0f;
-  a.pre_scale = 1.0f;
-  a.post_scale = 1.0f;
-  a.mask_rows = 1;
-  return a;
-}
-
 // W_wino != NULL: the grouped Winograd kernel (fp32 mode; the caller checked ss_wino43_conv_ok): F(4,4) groups where ss_wino44_conv_ok
 // covers the shape (k = 7 | 11), F(4,3) groups otherwise. act_out = 1: leaky-relu(0.1)
 // of the OUTPUT in the epilogue - the value is only ever read through the next conv's input leaky-relu, which then passes lrelu = 1.
@@ -367,9 +348,7 @@ int conv_same(const float* A, int B, int Trows, int C, const int32_t* lens, cons
               int d, float lrelu, int act_out, const float* R, float post_scale, int accumulate, float* out, int bf16, hipStream_t stream) {
   ss_conv_gemm_args a = base_args(B, Trows, lens);
   a.mfma_bf16 = bf16;
-  a.A = A;
-  a.lda = C;
-  a.a_batch_stride = (int64_t)Trows * C;
+  set_a(a, A, C, Trows);
   a.Cin = C;
   a.ntaps = k;
   for (int j = 0; j < k; ++j) a.tap_off[j] = (j - (k - 1) / 2) * d;
@@ -380,14 +359,10 @@ int conv_same(const float* A, int B, int Trows, int C, const int32_t* lens, cons
   a.Kp = round_up32(C);
   a.epi = SS_EPI_STORE;
   a.bias = bias;
-  a.R = R;
-  a.ldr = C;
-  a.r_batch_stride = (int64_t)Trows * C;
+  set_r(a, R, C, Trows);
   a.post_scale = post_scale;
   a.accumulate = accumulate;
-  a.C = out;
-  a.ldc = C;
-  a.c_batch_stride = (int64_t)Trows * C;
+  set_c(a, out, C, Trows);
   if (act_out) {
     a.act = SS_ACT_LRELU_;
     a.act_slope = 0.1f;
@@ -455,9 +430,7 @@ extern "C" int ss_hifigan_forward(const ss_hifigan* hg, const float* mel, const 
   // conv_pre (k=7)
   {
     ss_conv_gemm_args a = base_args(B, T, w.lens);
-    a.A = mel;
-    a.lda = 80;
-    a.a_batch_stride = (int64_t)T * 80;
+    set_a(a, mel, 80, T);
     a.Cin = 80;
     a.ntaps = 7;
     for (int j = 0; j < 7; ++j) a.tap_off[j] = j - 3;
@@ -467,9 +440,7 @@ extern "C" int ss_hifigan_forward(const ss_hifigan* hg, const float* mel, const 
     a.Kp = 96;
     a.epi = SS_EPI_STORE;
     a.bias = hg->b_pre;
-    a.C = w.pre;
-    a.ldc = hg->c0;
-    a.c_batch_stride = (int64_t)T * hg->c0;
+    set_c(a, w.pre, hg->c0, T);
     a.mfma_bf16 = hg->mfma_bf16;
     SS_PROPAGATE(ss_conv_gemm(&a, stream));
   }
@@ -488,9 +459,7 @@ extern "C" int ss_hifigan_forward(const ss_hifigan* hg, const float* mel, const 
     for (int g = 0; g < 2; ++g) {
       const int nph = g == 0 ? nph0 : u - nph0;
       ss_conv_gemm_args a = base_args(B, rows_in, lens_in);
-      a.A = cur;
-      a.lda = cin;
-      a.a_batch_stride = (int64_t)rows_in * cin;
+      set_a(a, cur, cin, rows_in);
       a.Cin = cin;
       a.ntaps = 2;
       a.tap_off[0] = g == 0 ? 0 : 1;
@@ -502,9 +471,7 @@ extern "C" int ss_hifigan_forward(const ss_hifigan* hg, const float* mel, const 
       a.Kp = round_up32(cin);
       a.epi = SS_EPI_STORE;
       a.bias = hg->b_up[i];
-      a.C = w.x + (g == 0 ? 0 : (int64_t)nph0 * cout);
-      a.ldc = u * cout;
-      a.c_batch_stride = (int64_t)rows_in * u * cout;
+      set_c(a, w.x + (g == 0 ? 0 : (int64_t)nph0 * cout), u * cout, rows_in);   // [rows_in][u phases][cout] = the [rows_in * u][cout] output
       a.mfma_bf16 = hg->mfma_bf16;
       SS_PROPAGATE(ss_conv_gemm(&a, stream));
     }

@@ -1,4 +1,4 @@
-"""GPU parity of the strided joint f0 / uv sampler (ss_f0diff_sample_strided: f0_tail_kernel / f0_update_row of csrc/diffusion.hip with the
+"""GPU parity of the strided joint f0 / uv sampler (ss_f0diff_sample_strided: f0_tail_kernel / f0_update_row of csrc/f0_sampler.hip with the
 coefficients of a gap t -> s) against the float64 statements of tests/f0_strided_refs.py, whose input conditions tests/test_f0_strided_cpu.py
 asserts without a GPU; its loop-cut and tape-addressing contracts; its stride-1 identity with ss_f0diff_sample; and forward(f0_steps=, f0_eta=).
 

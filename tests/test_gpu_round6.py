@@ -226,7 +226,7 @@ def test_skip_gemm_compact_operand_equals_the_pair_layout(one):
 
 def test_fp16sd_fused_path_under_the_ddim_sampler():
     """The weight sets and the fp16 addend sets of "fp16sd" are indexed by the evaluation number of the sampling loop, which every sampler has to hand
-    to the stack (the `eval` argument of `run_residual_stack` in diffusion.hip): here the strided sampler. (1) eta = 1 over all 100 steps IS the reference's ancestral chain (tests/test_gpu_round4.py):
+    to the stack (the `eval` argument of `run_residual_stack` in wavenet_stack.hip): here the strided sampler. (1) eta = 1 over all 100 steps IS the reference's ancestral chain (tests/test_gpu_round4.py):
     the fused one-product path (knob layer512 = 2 forces the one item onto it) against the REAL reference's 100-step golden; (2) eta = 0 over 10 of the
     steps - only 10 of the 32 sets take part, the least favourable case for the noise shaping - against the fp32 path's own 10-step result."""
     from oracle import harness

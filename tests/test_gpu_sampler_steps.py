@@ -1,4 +1,4 @@
-"""GPU unit parity of the joint f0 / uv sampler step (f0_input_kernel, f0_tail_kernel, f0_update_row of csrc/diffusion.hip) and of the samplers'
+"""GPU unit parity of the joint f0 / uv sampler step (f0_input_kernel, f0_tail_kernel, f0_update_row of csrc/f0_sampler.hip) and of the samplers'
 loop-cut contract, through the C-ABI (ss_f0diff_sample, ss_meldiff_sample, ss_mel_qsample, ss_mel_denorm) against the float64 statements of
 tests/sampler_step_refs.py (themselves checked by tests/test_sampler_step_refs_cpu.py, which also asserts the input conditions used here).
 

@@ -552,6 +552,54 @@ def test_workspace_bytes_of_every_stack_form_are_pinned():
     assert with_knob(b"layer512", 2, _ws_net("fp16x2"), 1, 768) == 82980864 and with_knob(b"layer512", 2, _ws_net("fp16sd"), 1, 768) == 177352704
 
 
+def test_every_sampler_entry_refuses_a_bad_net_or_workspace_before_any_launch():
+    """What the six sampler entry points refuse of a net and a workspace, one table: a null workspace, too many layers, a channel count off the
+    entry's own multiple (32 for the mel pair, 64 for the f0 pair; the DDIM and PLMS entries have no such row), a grouped net where the entry
+    takes none (the f0 entries take a pair over an even item count only) and a workspace one byte short. Every pointer is a placeholder or a host
+    array: each call returns before anything is launched."""
+    import ctypes
+    l = lib.load()
+    P, B, T = 0x1000, 2, 8
+    ts = np.array([3, 1, 0], np.int32)
+    betas = np.linspace(1e-4, 0.06, 100)
+
+    def mel_net(C_=256, groups=1):
+        return _ws_net("fp32", C_, 20, groups)
+
+    def f0_net(C_=256, groups=1):
+        n = _ws_net("fp32", C_, 20, groups)
+        n.in_dim, n.out_dim = 1, 3
+        return n
+    entries = {   # name: (net maker, call(net, B, ws, ws_bytes), C off the entry's multiple or None)
+        "ss_meldiff_sample": (mel_net, lambda n, b, ws, nb: l.ss_meldiff_sample(n, P, P, None, b, T, None, 17, None, 0, 4, 1, ws, nb, None), 48),
+        "ss_prodiff_sample": (mel_net, lambda n, b, ws, nb: l.ss_prodiff_sample(n, P, P, None, b, T, None, 17, None, 4, P, P, P, 1, ws, nb, None), 48),
+        "ss_meldiff_sample_ddim": (mel_net, lambda n, b, ws, nb: l.ss_meldiff_sample_ddim(n, P, P, None, b, T, lib.hptr(ts), 3, P, 1.0, None, 17, None, 1, ws,
+                                                                                         nb, None), None),
+        "ss_meldiff_sample_plms": (mel_net, lambda n, b, ws, nb: l.ss_meldiff_sample_plms(n, P, P, None, b, T, 4, 1, P, 1, P, ws, nb, None), None),
+        "ss_f0diff_sample": (f0_net, lambda n, b, ws, nb: l.ss_f0diff_sample(n, P, P, P, P, P, None, b, T, None, None, 17, None, 0, 4, 1, ws, nb, None), 96),
+        "ss_f0diff_sample_strided": (f0_net, lambda n, b, ws, nb: l.ss_f0diff_sample_strided(n, P, P, P, P, P, None, b, T, lib.hptr(ts), 3, 0, 3, lib.hptr(betas),
+                                                                                             1.0, None, None, 17, None, 1, ws, nb, None), 96),
+    }
+    for name, (make, call, bad_c) in entries.items():
+        deep = make()
+        deep.L = lib.SS_MAX_LAYERS + 1
+        rows = {"null ws": (make(), B, None, 1 << 40), "too many layers": (deep, B, P, 1 << 40)}
+        if bad_c is not None:
+            rows["C=%d" % bad_c] = (make(C_=bad_c), B, P, 1 << 40)
+        if make is mel_net:
+            rows["grouped net"] = (make(groups=2), B, P, 1 << 40)
+        else:
+            rows["three groups"] = (make(groups=3), 3, P, 1 << 40)
+            rows["pair over an odd item count"] = (make(groups=2), 3, P, 1 << 40)
+        n = make()
+        need = l.ss_wavenet_workspace_bytes(ctypes.byref(n), B, T)
+        assert need > 0
+        rows["workspace one byte short"] = (n, B, P, need - 1)
+        for what, (net, b, ws, nb) in rows.items():
+            rc = call(ctypes.byref(net), b, ws, nb)
+            assert rc != 0 and l.ss_last_error().startswith(name.encode() + b": "), (name, what, rc, l.ss_last_error())
+
+
 def test_gate128_index_math_against_a_tagged_lds_image(tmp_path):
     """gate128_kernel (the fp16x2 gate on 256 x 128 tiles, two workgroups per CU) takes all of its DMA / fragment / epilogue addresses from
     stylesinger_amd/csrc/gate128_layout.h; tools/layout_check_gate128.cpp compiles the SAME header on the host, replays every LDS-DMA piece

@@ -2,7 +2,7 @@
 / block geometry per launch - in which every kernel is EMPTY (ss_debug_null_launch). Its replay time is what the launch edges alone cost; the
 difference to the real loop is what kernels can still win ("launch structure").
     python tools/launch_floor.py [--B 8] [--T 1500] [--steps 100]
-Per network evaluation of the fp32 C2 loop (run_residual_stack, diffusion.hip): input projection, 20 x (gate, residual projection) minus the last
+Per network evaluation of the fp32 C2 loop (run_residual_stack, wavenet_stack.hip): input projection, 20 x (gate, residual projection) minus the last
 projection, skip GEMM, output projection + sampler update (42 launches); once per loop: q-sample, conditioner projection, 20 addend re-layouts."""
 import argparse
 import os
