@@ -1022,6 +1022,28 @@ int ss_contour_align(const float* f0_hz, int64_t ldc, int Lc, const int32_t* len
                      int band, int uv_cost, int cap, float shift_semitones, float* out, int64_t ldo, int32_t* idx, int32_t* cost, int32_t* status,
                      int T, int B, void* ws, int64_t ws_bytes, void* stream);
 
+/* The score's phones laid out on the GUIDE's frame axis (forward(pitch_hz=..., pitch_timing="guide"); definition: `retime_to_guide` in
+ * stylesinger_amd/pitch.py - integers only, so every output is exact). Per item b with n_t = lens_t[b] <= T score frames, n_c = lens_c[b] <= Lc
+ * guide frames (both DEVICE arrays: no host sync), mel2ph[b] (1-based phone per score frame, row stride ldm), midi[b] (the score's note per frame,
+ * row stride ldn, as ss_contour_align takes it) and idx[b] / status_align[b] as ss_contour_align wrote them (idx dense [B][T]):
+ *   cents    Mc[i] = 100 min(midi[i], 127) for midi[i] > 0, else the rest sentinel (ss_contour_align's rule);
+ *   anchors  a_0 = 0, then every i in [1, n_t) with Mc[i] != Mc[i-1], a_m = n_t: m spans. The path is pitch-only - inside a held note and between
+ *            repeated equal notes it says nothing about time - so only the first row of a new pitch is used;
+ *   guide    g_0 = 0, g_k = idx[a_k] for 0 < k < m, g_m = n_c; then at least one guide frame per span: with h_k = g_k - k, h_k <- max(h_0 .. h_k) for
+ *            k < m (the end h_m = n_c - m stays pinned), then h_k <- min(h_k .. h_m), g_k = h_k + k: g_0 = 0, g_m = n_c, g_(k+1) - g_k >= 1;
+ *   map      guide frame j in span k (g_k <= j < g_(k+1)), r = g_(k+1) - g_k, s = a_(k+1) - a_k, x = j - g_k:
+ *            src[b][j] = a_k + ((2 x + 1) s) / (2 r) (integer division: the frame-centre rule of ss_contour_fit), out[b][j] = mel2ph[b][src].
+ * Not retimed, status[b] = 1: status_align[b] != 0, or n_c < m, or an empty item. Then one span [0, n_t) -> [0, n_c), the linear stretch
+ * src = ((2 j + 1) n_t) / (2 n_c); an empty item (n_t == 0 or n_c == 0) writes out = 0, src = -1. Otherwise status[b] = 0. Guide frames
+ * j >= n_c: out = 0, src = -1. n_spans[b] = m (0 when n_t == 0). out [B][ldo] int64, Lc columns written; src [B][Lc] int32, status and n_spans [B]
+ * are dense. One workgroup per item: the anchors are flagged in parallel and enumerated by a block-wide exclusive scan into LDS, g by a block-wide
+ * max scan, then every guide frame finds its span by a binary search in LDS. int32 arithmetic ((2 x + 1) s <= 2 * 8192 * 8192). No atomics, no
+ * allocation: graph-capturable; an item's result does not depend on B, T, Lc, the strides or the other items, and nothing at or past the lengths
+ * is read into a result. T <= SS_ALIGN_MAX_T and Lc <= SS_ALIGN_MAX_LC; larger sizes are refused, never truncated. out must not alias mel2ph. */
+int ss_retime_mel2ph(const int64_t* mel2ph, int64_t ldm, const int64_t* midi, int64_t ldn, const int32_t* idx, const int32_t* status_align,
+                     const int32_t* lens_t, const int32_t* lens_c, int64_t* out, int64_t ldo, int32_t* src, int32_t* status, int32_t* n_spans,
+                     int T, int Lc, int B, void* stream);
+
 /* Objective metrics of a rendered item a (rows i, n_a = lens_a[b] <= Ta frames) against a target b (columns j, n_b = lens_b[b] <= Tb frames), both
  * on the mel hop grid (csrc/evaluate.hip; definitions: `mcep_q`, `dtw_path`, `path_metrics` in stylesinger_amd/evaluate.py). A log-mel cepstral
  * distortion of this project's OWN definition - not SPTK / WORLD mcep MCD - next to the F0 frame error and the cents RMSE along the same path. All

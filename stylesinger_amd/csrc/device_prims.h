@@ -46,6 +46,31 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Wave-wide scans. Inclusive max scan (lane l ends with the maximum over lanes 0 .. l) and its mirror, the suffix minimum (lanes l .. 63).
+__device__ __forceinline__ int wave_scan_max(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int n = __shfl_up(v, o);
+    if (lane >= o) v = max(v, n);
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_scan_min_down(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int n = __shfl_down(v, o);
+    if (lane + o < 64) v = min(v, n);
+  }
+  return v;
+}
+// Exclusive count of a predicate: the lanes below this one for which it holds; total = the wave's count (one ballot, no shuffles).
+// Every lane of the wave must call it.
+__device__ __forceinline__ int wave_rank(bool p, int lane, int& total) {
+  const unsigned long long mask = __ballot(p);
+  total = __popcll(mask);
+  return __popcll(mask & ((1ull << lane) - 1ull));
+}
+
 // LDS-DMA of 64 x 16 bytes: lane i's 16 bytes land at lds_dst + 16 i (wave-uniform destination, per-lane source offset).
 // (A __device__ helper on purpose: with the builtin written directly inside the templated __global__ body, the host pass of hipcc
 //  (ROCm 7.2) silently drops the kernel's launch stub and the library no longer links.)

@@ -2,28 +2,13 @@
 // utils/pitch_utils.py:34-62 and the small element-wise steps of the emotion encoder's 40-mel front end
 // (data_gen/tts/emotion/audio.py:43-55). All HBM-bound, off the hot path; the GEMM-shaped steps reuse ss_conv_gemm.
 #include "common.h"
+#include "device_prims.h"
 #include "../../include/stylesinger_hip.h"
 #include <limits.h>
 
 namespace {
 
-// inclusive max-scan (dir = +1) / min-scan (dir = -1 means "suffix minimum") helpers over one 256-thread block
-__device__ __forceinline__ int wave_scan_max(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int n = __shfl_up(v, o);
-    if (lane >= o) v = max(v, n);
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_scan_min_down(int v, int lane) {  // suffix minimum inside the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int n = __shfl_down(v, o);
-    if (lane + o < 64) v = min(v, n);
-  }
-  return v;
-}
+using namespace ss_dev;   // wave_scan_max / wave_scan_min_down: the inclusive max scan and the suffix minimum of one wave
 
 // One workgroup per utterance. Pass A: prev[t] = last voiced frame <= t (or -1); pass B: next[t] = first voiced frame >= t (or
 // INT_MAX); both kept as integer bit patterns in the two output rows. Pass C: the value.

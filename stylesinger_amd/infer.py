@@ -134,7 +134,9 @@ class StyleSingerInfer(ReferenceProducers):
         `pitch_hz` = (contour in Hz [B, Lc], lens_c) with optional `pitch_shift` (semitones); without them the f0 is predicted. With
         `pitch_align` = "dtw" (+ `pitch_align_band`, guide frames; 0 / None = full) the contour is warped onto the score's notes instead of
         being scaled linearly; items the aligner left to the linear fit (`model_out['pitch_align_status']` != 0) are named in a warning where
-        this method reads the lengths on the host anyway (`out_lufs`), never through a sync of its own.
+        this method reads the lengths on the host anyway (`out_lufs`), never through a sync of its own. With `pitch_timing` = "guide" the score is
+        sung in the contour's timing (forward(pitch_timing=): the contour on the mel hop grid; as many frames come out as the contour has); items
+        left to the linear stretch (`model_out['pitch_retime_status']` != 0) are named in the same place.
         `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain).
         `out_true_peak_db`: hold every item of `wav` under this true-peak ceiling with the look-ahead limiter (`_finish_wav`, `limiter.py`; adds
         res['limiter'] = {min_gain, n_limited} as device tensors); with `out_lufs` too the loudness gain is applied in full (res['loudness_gain'])
@@ -142,7 +144,7 @@ class StyleSingerInfer(ReferenceProducers):
         Optional `style_cache`: what `model.encode_style` returned for the batch's references; the style encoder is then skipped."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
-        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band") if batch.get(k) is not None}
+        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band", "pitch_timing") if batch.get(k) is not None}
         if batch.get("style_cache") is not None:   # the references' style, encoded once by the caller (model.encode_style; `sing_score`)
             passed_on["style_cache"] = batch["style_cache"]
         out = self.model(batch["txt_tokens"], mel2ph=batch.get("mel2ph"), spk_embed=batch["spk_embed"], emo_embed=batch["emo_embed"],
@@ -167,6 +169,11 @@ class StyleSingerInfer(ReferenceProducers):
         if bad:
             warnings.warn(f"pitch_align: {what} {bad} not aligned (more guide frames per score frame than the band allows, or empty): they got the "
                           "linear fit; widen pitch_align_band")
+        rt = model_out.get("pitch_retime_status")
+        loose = [] if rt is None else [i for i, v in enumerate(rt.cpu().tolist()) if v != 0]
+        if loose:
+            warnings.warn(f"pitch_timing: {what} {loose} not retimed (not aligned, or fewer guide frames than the score has pitch changes): their "
+                          "phones are stretched linearly over the guide's frames")
         return bad
 
     def _to_lufs(self, wav, lens, target):
@@ -332,6 +339,8 @@ class StyleSingerInfer(ReferenceProducers):
         mel and the f0 as they are). Segments never overlap: the song is their concatenation. ONE host sync at the end learns the length. Loudness
         (`out_lufs`, else hparams['out_loudness_lufs']) is applied to the WHOLE song, never per segment: that would flatten its dynamics. So is the
         true-peak limiter (`out_true_peak_db`, else hparams['out_true_peak_db']; `_finish_wav`), once, after the stitch: adds 'limiter' (one entry).
+        `pitch_timing` = "guide": every segment is sung in the timing of ITS slice of the contour (forward(pitch_timing=)); notes move only inside
+        a segment, segment starts and the song's length stay the plan's; each entry of `segments` then carries `pitch_retime_status`.
         -> dict(wav [N], mel [F, 80], f0 [F] on the device, segments = [{first, last, start_frame, n_frames, batch, row}] (phones [first, last)),
         plan (the SongPlan; its batches in their device form), lufs (float, the loudness before the gain) when a target is set)."""
         from . import song
@@ -387,7 +396,9 @@ def _score_run(score, hparams, out_path, segments_out=None, vad_flags=None, max_
         with open(segments_out, "w") as fh:
             json.dump(dict(sample_rate=sr, hop=hop, n_samples=int(res["wav"].numel()),
                            segments=[dict(first_phone=g["first"], last_phone=g["last"], start_sample=g["start_frame"] * hop,
-                                          n_samples=g["n_frames"] * hop) for g in res["segments"]]), fh, indent=1)
+                                          n_samples=g["n_frames"] * hop,
+                                          **({"pitch_retime_status": g["pitch_retime_status"]} if "pitch_retime_status" in g else {}))
+                                     for g in res["segments"]]), fh, indent=1)
     return res
 
 
@@ -396,7 +407,8 @@ def main(argv=None):
     --phone-set ZH_checkpoint_phone_set.json [--ref-audio test/test.wav] [--out infer_out/test.wav] [--no-vad-trim | --vad {webrtc,lrt}]` = the reference's
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
     sing the score on a given pitch contour instead of the predicted one; `--pitch-align dtw [--pitch-align-band-s 2.0]`: the contour is a guide
-    with its own timing, warp it onto the score's notes (band in seconds around the linear fit, 0 = full) instead of scaling it linearly. `--loud-norm`: loudness-normalise the reference audio as a model trained with
+    with its own timing, warp it onto the score's notes (band in seconds around the linear fit, 0 = full) instead of scaling it linearly; `--pitch-timing guide`: the
+    other way round - lay the score out on the guide's frames (note onsets where the guide has them) so that the result is in sync with the take. `--loud-norm`: loudness-normalise the reference audio as a model trained with
     hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--out-true-peak DB [--out-lookahead-ms 2]`: hold the result under DB dBFS
     true peak with the look-ahead limiter (with --out-lufs the loudness gain is then applied in full instead of being divided by the peak); `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
     subtraction of V, e.g. 0.1) after the generator, before the loudness target and the writer.
@@ -421,6 +433,8 @@ def main(argv=None):
     ap.add_argument("--pitch-align", choices=["dtw"], help="warp the given contour onto the score's notes by dynamic time warping (a guide vocal "
                     "with a timing of its own) instead of scaling it linearly")
     ap.add_argument("--pitch-align-band-s", type=float, help="--pitch-align: half-width of the band around the linear fit, seconds (default 2.0; 0 = full)")
+    ap.add_argument("--pitch-timing", choices=["guide"], help="sing in the given contour's timing instead of the score's: note onsets where the guide "
+                    "has them, as many frames as the contour has (pitch-only alignment: no timing information inside a held or repeated note)")
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
@@ -448,7 +462,9 @@ def main(argv=None):
         ap.error("--pitch-shift needs --pitch-audio or --pitch-npy")
     if a.pitch_align is not None and not (a.pitch_audio or a.pitch_npy):
         ap.error("--pitch-align needs --pitch-audio or --pitch-npy")
-    if a.pitch_align_band_s is not None and a.pitch_align is None:
+    if a.pitch_timing is not None and not (a.pitch_audio or a.pitch_npy):
+        ap.error("--pitch-timing needs --pitch-audio or --pitch-npy")
+    if a.pitch_align_band_s is not None and a.pitch_align is None and a.pitch_timing is None:
         ap.error("--pitch-align-band-s needs --pitch-align")
     if a.pitch_align_band_s is not None and not a.pitch_align_band_s >= 0:
         ap.error("--pitch-align-band-s: seconds >= 0 (0 = full)")
@@ -463,6 +479,8 @@ def main(argv=None):
         pitch["pitch_align"] = a.pitch_align
     if a.pitch_align_band_s is not None:
         pitch["pitch_align_band_s"] = a.pitch_align_band_s
+    if a.pitch_timing is not None:
+        pitch["pitch_timing"] = a.pitch_timing
     score = None
     if a.score:
         with open(a.score) as fh:

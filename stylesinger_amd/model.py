@@ -313,6 +313,17 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             comparison). `ret` gains `pitch_align_idx` [B, T] (guide frame per score frame, -1 beyond the item), `pitch_align_cost` [B] and
             `pitch_align_status` [B] (1 = the item was not aligned and got the linear fit: more than `band` guide frames per score frame) as
             device tensors, no sync. Default `None`: the linear fit, exactly as before.
+            `pitch_timing="guide"`: sing in the GUIDE's timing instead of the score's. The contour is taken to be on the model's frame grid (hop_size /
+            audio_sample_rate: what tracking `pitch_audio` gives; a contour on another grid must be resampled by the caller). Once the score's mel2ph
+            exists (predicted durations or a given `mel2ph`) the guide is aligned to it as above (`pitch_align` may be omitted or "dtw";
+            `pitch_align_band` and `pitch_shift` apply to the alignment), and `ss_retime_mel2ph` (pitch.retime_to_guide) lays the phones out on the
+            guide's frames: note onsets where the guide has them, the phones inside a note in their proportions. The call then continues as if the
+            caller had passed that mel2ph: T_out = Lc (the render lines up with the take frame for frame), and the contour is used one-to-one.
+            `ret['mel2ph']` is the retimed one; `ret` gains `mel2ph_score`, `pitch_retime_src` [B, Lc] (score frame under every guide frame, -1
+            beyond the item), `pitch_retime_status` [B] (1 = not retimed, the linear stretch: the alignment refused the item, or the guide has fewer
+            frames than the score has pitch changes) and `pitch_align_idx` / `_cost` / `_status` on the SCORE's frame axis. The alignment is
+            pitch-only: it carries no timing information inside a held note or between repeated equal notes, where the phones are spread linearly.
+            ValueError with `f0=` / `uv=` and with `f0_steps`. Default `None`: the paths above, bit for bit.
         Both skip `ss_f0_bounds` and the f0 pair loop (and its hipGraph) and run `ss_pitch_given` in place of `ss_pitch_post`; everything from
         `pitch_embed` on is unchanged, and the mel loop draws the same noise as a predicted-f0 forward with the same `seed`. `ret` carries
         `pitch_pred`, `f0_denorm`, `f0_denorm_pred` (= `f0_denorm`, as stylesinger.py:241 yields for a given contour) and `pitch_coarse`, and
@@ -336,10 +347,18 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         if pitch_align is not None and pitch_hz is None:
             raise ValueError("forward: pitch_align warps the pitch_hz contour onto the score; it needs pitch_hz"
                              + (" (f0 / uv are taken as they are)" if f0 is not None else ""))
-        if pitch_align_band is not None and pitch_align is None:
+        if pitch_align_band is not None and pitch_align is None and kwargs.get("pitch_timing") is None:   # pitch_timing aligns too
             raise ValueError("forward: pitch_align_band is the band of pitch_align='dtw'; it needs pitch_align")
         if pitch_align_band is not None and int(pitch_align_band) < 0:
             raise ValueError(f"forward: pitch_align_band={pitch_align_band}: guide frames >= 0 (0 or None = the full matrix)")
+        pitch_timing = kwargs.get("pitch_timing")
+        if pitch_timing is not None and pitch_timing != "guide":
+            raise ValueError(f"forward: pitch_timing={pitch_timing!r}: None (the score's timing) or 'guide'")
+        if pitch_timing is not None and pitch_hz is None:
+            raise ValueError("forward: pitch_timing lays the score out on the pitch_hz contour's frames; it needs pitch_hz"
+                             + (" (f0 / uv are taken as they are)" if f0 is not None else ""))
+        if pitch_timing is not None and kwargs.get("f0_steps") is not None:
+            raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with pitch_timing (a pitch_hz contour) they do not run")
         f0_ts, f0_eta = self._f0_sampler_args(kwargs, f0 is not None or pitch_hz is not None)
         self._ensure_packed()
         # c: the per-call state the stages share (shapes, lengths, intermediate activations, the plan) and the result dict
@@ -360,7 +379,9 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
                     self._refine_mel(c)
                 else:
                     c.ret["mel_out"] = c.coarse_mel
-        return self._crop_frames(c.ret, c.T, c.T_out)
+        ret = self._crop_frames(c.ret, c.T, c.T_out)
+        ret.update(c.score_axis)
+        return ret
 
     def _f0_sampler_args(self, kwargs, contour_given):
         """(network times or None, eta) of the f0 pair loop: forward(f0_steps=, f0_eta=), else hparams['f0_sample_steps'] / ['f0_sample_eta'];
@@ -442,6 +463,9 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             mel2ph = mel2ph.contiguous()
             T = mel2ph.shape[1]
             ret["dur"] = logdur
+        c.score_axis = {}   # results that stay on the score's frame axis when the render does not (pitch_timing="guide")
+        if c.kwargs.get("pitch_timing") is not None:
+            mel2ph, T = self._retime_to_guide(c, mel2ph, T)   # from here on as if the caller had passed this mel2ph: T = the contour's width
         # hipGraph bucket: run the frame axis padded to a multiple of t_bucket (padding = mel2ph 0 -> masked like any
         # batch padding); the plan/graph cache is then keyed by the bucket and every frame-level output is cropped back.
         c.T_out = T_out = T
@@ -456,6 +480,27 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c.dec = torch.empty(B, T, H, **f32)
         L.ops.ss_gather_expand(enc, mel2ph, c.dec, B, Tp, T, H)
         # UMLN (a4): DistributionUncertainty returns x unchanged when not training (umln.py:48-50)
+
+    def _retime_to_guide(self, c, mel2ph, T):
+        """pitch_timing="guide": the score's mel2ph [B, T] laid out on the guide contour's frame axis -> (mel2ph' [B, Lc], Lc). The guide is aligned to
+        the score's note per frame (ss_contour_align, with pitch_align_band / pitch_shift as for pitch_align="dtw"), then ss_retime_mel2ph puts the
+        note onsets where the guide has them (pitch.retime_to_guide). Lengths stay on the device; Lc is the contour's shape: no host sync."""
+        from .pitch import contour_align_device, retime_device
+        hz, lens_c = c.kwargs["pitch_hz"]
+        B, dev = c.B, c.dev
+        if hz.dim() != 2 or hz.shape[0] != B:
+            raise ValueError(f"forward: pitch_hz contour {tuple(hz.shape)} for a batch of {B}: expected [{B}, Lc]")
+        hz, Lc = hz.to(dev), hz.shape[1]
+        shift = c.kwargs.get("pitch_shift")
+        L.ops.ss_count_nonzero_i64(mel2ph, c.lens_t, B, T)
+        midi = torch.empty(B, T, device=dev, dtype=torch.int64)
+        L.ops.ss_gather_expand_i64(c.note, mel2ph, midi, B, c.Tp, T)
+        _, a_idx, a_cost, a_status = contour_align_device(hz, lens_c, midi, c.lens_t, T, band=c.kwargs.get("pitch_align_band"),
+                                                          shift=0.0 if shift is None else float(shift))
+        out, src, status, _ = retime_device(mel2ph, c.lens_t, midi, a_idx, a_status, lens_c, Lc)
+        c.score_axis = dict(mel2ph_score=mel2ph, pitch_align_idx=a_idx, pitch_align_cost=a_cost, pitch_align_status=a_status)
+        c.ret["pitch_retime_src"], c.ret["pitch_retime_status"] = src, status
+        return out, Lc
 
     def _align_style(self, c, ref_mels, ref_f0):
         """Residual Style Adaptor (a5,a6; encode_style, or the caller's style_cache) + style-to-content attention (a7) -> c.style [B,T,H]."""
@@ -518,7 +563,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             if pitch_hz[0].dim() != 2 or pitch_hz[0].shape[0] != B:
                 raise ValueError(f"forward: pitch_hz contour {tuple(pitch_hz[0].shape)} for a batch of {B}: expected [{B}, Lc]")
             shift = 0.0 if pitch_shift is None else float(pitch_shift)
-            if c.kwargs.get("pitch_align") is None:
+            if c.kwargs.get("pitch_align") is None or c.kwargs.get("pitch_timing") is not None:   # retimed: the frames ARE the guide's, a 1:1 copy
                 hz = contour_fit_device(pitch_hz[0].to(dev), pitch_hz[1], lens_t, T, shift)
             else:   # "dtw": warp the guide onto the score's note per frame (the midi of _pitch_predicted)
                 from .pitch import contour_align_device

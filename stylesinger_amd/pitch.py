@@ -13,7 +13,9 @@ Pitch control (`StyleSingerHIP.forward(pitch_hz=...)`): a caller's contour in Hz
 known inside forward. `contour_fit` is the float64 definition of the fit between the two grids, `contour_fit_device` the kernel (`ss_contour_fit`,
 csrc/pitch_fit.hip) that runs it from device lengths. That fit is a linear time scaling: right for a contour that already has the score's timing.
 A guide vocal does not: `contour_align` (definition, integer arithmetic) / `contour_align_device` (`ss_contour_align`, csrc/contour_align.hip) warp
-the contour onto the score's per-frame notes by dynamic time warping (forward(pitch_align="dtw")).
+the contour onto the score's per-frame notes by dynamic time warping (forward(pitch_align="dtw")). The reverse direction - the score laid out on the
+GUIDE's frames, so that the render is in sync with the take - is `retime_to_guide` (definition, integers only) / `retime_device` (`ss_retime_mel2ph`,
+csrc/retime.hip): the alignment's path turned into a new mel2ph of the guide's length (forward(pitch_timing="guide")).
 """
 import numpy as np
 import torch
@@ -277,3 +279,88 @@ def contour_align_device(f0_hz, lens_c, midi, lens_t, T, band=None, shift=0.0):
     L.ops.ss_contour_align(x, x.stride(0), Lc, lc, md, md.stride(0), lt, band, ALIGN_UV_COST, ALIGN_CAP, float(shift), out, out.stride(0), idx, cost,
                            status, T, B, ws, ws_bytes)
     return out, idx, cost, status
+
+
+# ---- the score on the guide's clock (forward(pitch_timing="guide")) -------------------------------------------------------------------------------
+def retime_to_guide(mel2ph, midi, idx, status_align, n_c, Lc=None):
+    """The definition of the retiming (one item, integers only): the score's phones laid out on the guide's frame axis.
+    mel2ph [n_t] (1-based phone per score frame), midi [n_t] (the score's note per frame, what ss_gather_expand_i64(note, mel2ph) gives), idx [n_t] and
+    status_align as `contour_align` returned them for the (shifted) guide, n_c = valid guide frames, Lc >= n_c = width of the output (default n_c).
+      1. score cents as contour_align: Mc[i] = 100 min(midi[i], 127) for midi[i] > 0, else ALIGN_UNVOICED;
+      2. anchors a_0 = 0, every i in [1, n_t) with Mc[i] != Mc[i-1], a_m = n_t: m spans. The path is pitch-only DTW: inside a held note and between
+         repeated equal notes it carries no timing, and with the tie order up, left, diagonal only the first row of a new pitch has a meaningful
+         smallest j - so anchors are taken there alone and everything between them is interpolated;
+      3. guide positions g_0 = 0, g_k = idx[a_k] (0 < k < m), g_m = n_c;
+      4. at least one guide frame per span: h_k = g_k - k; h_k <- max(h_0 .. h_k) for k < m, the end h_m = n_c - m staying pinned (a prefix maximum
+         that included it could push g_m beyond n_c when the guide crowds the last notes); then h_k <- min(h_k .. h_m); g_k = h_k + k. For n_c >= m:
+         g_0 = 0, g_m = n_c, g_(k+1) - g_k >= 1 (asserted);
+      5. guide frame j in span k, r = g_(k+1) - g_k, s = a_(k+1) - a_k, x = j - g_k: src[j] = a_k + ((2 x + 1) s) // (2 r) (the frame-centre rule of
+         contour_fit / align_band_centres), mel2ph'[j] = mel2ph[src[j]];
+      6. NOT retimed, status 1: status_align == 1, or n_c < m, or n_t == 0, or n_c == 0. Then one span [0, n_t) -> [0, n_c), the linear stretch; an
+         empty item gives mel2ph' = 0, src = -1. Otherwise status 0;
+      7. j >= n_c: mel2ph' = 0, src = -1.
+    -> (mel2ph' int64 [Lc], src int32 [Lc], status, n_spans = m; 0 when n_t == 0)."""
+    mp = np.asarray(mel2ph, dtype=np.int64)
+    md = np.asarray(midi, dtype=np.int64)
+    n_t, n_c = len(mp), int(n_c)
+    Lc = n_c if Lc is None else int(Lc)
+    assert len(md) == n_t and 0 <= n_c <= Lc
+    out, src = np.zeros(Lc, dtype=np.int64), np.full(Lc, -1, dtype=np.int32)
+    if n_t == 0:
+        return out, src, 1, 0
+    Mc = np.where(md > 0, 100 * np.minimum(md, 127), ALIGN_UNVOICED)
+    a = np.concatenate([[0], 1 + np.flatnonzero(Mc[1:] != Mc[:-1]), [n_t]]).astype(np.int64)
+    m = len(a) - 1
+    if n_c == 0:
+        return out, src, 1, m
+    status = 1 if int(status_align) != 0 or n_c < m else 0
+    if status:
+        a, g = np.asarray([0, n_t], dtype=np.int64), np.asarray([0, n_c], dtype=np.int64)
+    else:
+        k = np.arange(m + 1, dtype=np.int64)
+        g = np.concatenate([[0], np.asarray(idx, dtype=np.int64)[a[1:m]], [n_c]])
+        h = g - k
+        h[:m] = np.maximum.accumulate(h[:m])
+        h = np.minimum.accumulate(h[::-1])[::-1]
+        g = h + k
+        assert g[0] == 0 and g[m] == n_c and (np.diff(g) >= 1).all(), "n_c >= m leaves every span a guide frame"
+    j = np.arange(n_c, dtype=np.int64)
+    span = np.searchsorted(g, j, side="right") - 1
+    r, s, x = (g[1:] - g[:-1])[span], (a[1:] - a[:-1])[span], j - g[span]
+    src[:n_c] = a[span] + ((2 * x + 1) * s) // (2 * r)
+    out[:n_c] = mp[src[:n_c]]
+    return out, src, status, m
+
+
+@torch.no_grad()
+def retime_device(mel2ph, lens_t, midi, idx, status_align, lens_c, Lc):
+    """mel2ph int64 [B, >= T] and midi int64 [B, >= T] on the device, idx int32 [B, T] / status_align int32 [B] as `contour_align_device` returned them,
+    lens_t int32 [B] ON THE DEVICE (score frames per item: no host sync), lens_c [B] valid guide frames (host ints or a device tensor; None = Lc),
+    Lc = the guide's width -> (mel2ph' int64 [B, Lc], src int32 [B, Lc], status int32 [B], n_spans int32 [B]): `retime_to_guide` of every item
+    (`ss_retime_mel2ph`). status 1 = not retimed (the linear stretch): see `retime_to_guide`. Sizes beyond ALIGN_MAX_T / ALIGN_MAX_LC are refused."""
+    if not all(torch.is_tensor(t) and t.device.type == "cuda" for t in (mel2ph, midi, idx, status_align)):
+        raise L.StyleSingerHipError("retime_device needs device tensors: there is no CPU path")
+    B, T = idx.shape
+    Lc = int(Lc)
+    dev = idx.device
+    if T > ALIGN_MAX_T or Lc > ALIGN_MAX_LC:
+        raise ValueError(f"retime_device: {T} score frames / {Lc} guide frames exceed the kernel's caps ({ALIGN_MAX_T} / {ALIGN_MAX_LC}); "
+                         "cut the score into segments (sing_score)")
+    rows = lambda t: t if t.dtype == torch.int64 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.long().contiguous()
+    mp, md = rows(mel2ph), rows(midi)
+    for name, t in (("mel2ph", mp), ("midi", md)):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < T:
+            raise ValueError(f"retime_device: {name} {tuple(t.shape)} for an alignment of {B} items and {T} frames")
+    ix = idx.to(torch.int32).contiguous()
+    sa = status_align.to(torch.int32).reshape(-1).contiguous()
+    lc = torch.full((B,), Lc, dtype=torch.int32) if lens_c is None else torch.as_tensor(lens_c)
+    lc = lc.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    lt = lens_t.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if lc.numel() != B or lt.numel() != B or sa.numel() != B:
+        raise ValueError(f"retime_device: {lc.numel()} guide lengths, {lt.numel()} score lengths and {sa.numel()} alignment states for {B} items")
+    out = torch.empty(B, Lc, device=dev, dtype=torch.int64)
+    src = torch.empty(B, Lc, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    n_spans = torch.empty(B, device=dev, dtype=torch.int32)
+    L.ops.ss_retime_mel2ph(mp, mp.stride(0), md, md.stride(0), ix, sa, lt, lc, out, out.stride(0), src, status, n_spans, T, Lc, B)
+    return out, src, status, n_spans

@@ -29,20 +29,31 @@ ALIGN_BAND_S = 2.0   # default half-width of the pitch_align band, seconds aroun
 def align_inputs(inp, has_contour, sr, hop):
     """The alignment keys of `inp` (host only, no device): inp['pitch_align'] (None | "dtw") and inp['pitch_align_band_s'] (seconds >= 0; default
     ALIGN_BAND_S; 0 = the full matrix) -> {} or {pitch_align: "dtw", pitch_align_band: round(s * sr / hop) guide frames (0 = full)}. Refused: another
-    mode, a band without pitch_align, either without a contour (`has_contour`: inp gave pitch_hz or pitch_audio)."""
-    mode, band_s = inp.get("pitch_align"), inp.get("pitch_align_band_s")
-    if mode is None:
+    mode, a band without pitch_align, either without a contour (`has_contour`: inp gave pitch_hz or pitch_audio).
+    inp['pitch_timing'] (None | "guide": forward(pitch_timing=), the score sung in the guide's timing) aligns too: it takes the band with or without
+    pitch_align, needs a contour like it, and adds pitch_timing = "guide" to the result."""
+    mode, band_s, timing = inp.get("pitch_align"), inp.get("pitch_align_band_s"), inp.get("pitch_timing")
+    if timing is not None and timing != "guide":
+        raise ValueError(f"preprocess_input: inp['pitch_timing'] = {timing!r}: None (the score's timing) or 'guide'")
+    if timing is not None and not has_contour:
+        raise ValueError("preprocess_input: inp['pitch_timing'] lays the score out on the frames of inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
+    if mode is None and timing is None:
         if band_s is not None:
             raise ValueError("preprocess_input: inp['pitch_align_band_s'] is the band of inp['pitch_align'] = 'dtw'; it needs pitch_align")
         return {}
-    if mode != "dtw":
+    if mode is not None and mode != "dtw":
         raise ValueError(f"preprocess_input: inp['pitch_align'] = {mode!r}: None (the linear fit) or 'dtw'")
     if not has_contour:
         raise ValueError("preprocess_input: inp['pitch_align'] warps inp['pitch_hz'] / inp['pitch_audio'] onto the score; it needs one of them")
     band_s = ALIGN_BAND_S if band_s is None else float(band_s)
     if not band_s >= 0:
         raise ValueError(f"preprocess_input: inp['pitch_align_band_s'] = {band_s}: seconds >= 0 (0 = the full matrix)")
-    return dict(pitch_align="dtw", pitch_align_band=int(round(band_s * sr / hop)))
+    out = dict(pitch_align_band=int(round(band_s * sr / hop)))
+    if mode is not None:
+        out["pitch_align"] = mode
+    if timing is not None:
+        out["pitch_timing"] = timing
+    return out
 
 
 class ReferenceProducers:
@@ -302,7 +313,9 @@ class ReferenceProducers:
         inp['pitch_audio'] (a WAV path or a (waveform, sample_rate) pair: a guide vocal, resampled like `ref_audio` and tracked on the device as
         `preprocess_batch` tracks the reference audio, 80-800 Hz), and inp['pitch_shift'] (semitones). inp['pitch_align'] = "dtw" (+
         inp['pitch_align_band_s'], seconds, default ALIGN_BAND_S, 0 = full) asks for the warp of forward(pitch_align=): -> `pitch_align` and
-        `pitch_align_band` = round(s * audio_sample_rate / hop_size) guide frames. -> {} when `inp` has none of them."""
+        `pitch_align_band` = round(s * audio_sample_rate / hop_size) guide frames. inp['pitch_timing'] = "guide" asks for forward(pitch_timing=):
+        the score sung in the guide's timing (the contour must be on the mel hop grid, as a tracked `pitch_audio` is) -> `pitch_timing` and the
+        band. -> {} when `inp` has none of them."""
         if inp.get("pitch_hz") is not None and inp.get("pitch_audio") is not None:
             raise ValueError("preprocess_input: give inp['pitch_hz'] or inp['pitch_audio'], not both")
         out = {}

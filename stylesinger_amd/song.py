@@ -22,6 +22,8 @@ Policy
     (`pitch.contour_fit`, float64) and sliced per segment; every slice has its segment's length, so `ss_contour_fit` copies it bit for bit.
     With pitch_align = "dtw" (+ pitch_align_band_s) every segment then warps ITS slice onto its own notes (`ss_contour_align`), the slice's two ends
     pinned to the segment's: the planner's cut of the contour stays linear, the warp only moves notes inside a segment.
+    With pitch_timing = "guide" every segment lays ITS phones out on its slice's frames instead (`ss_retime_mel2ph`, forward(pitch_timing=)): a
+    slice has its segment's frame count, so notes move only inside a segment - segment starts and the song's length are those of the plan.
   * Batches: segments ordered by frame count (phone count when frames are unknown), descending, ties in song order; `segment_batch` per batch.
 """
 import dataclasses
@@ -33,7 +35,7 @@ import torch
 from . import lib as L
 from .producers import align_inputs, has_features, row
 
-PITCH_KEYS = ("pitch_hz", "pitch_audio", "pitch_shift", "pitch_align", "pitch_align_band_s")
+PITCH_KEYS = ("pitch_hz", "pitch_audio", "pitch_shift", "pitch_align", "pitch_align_band_s", "pitch_timing")
 NO_PH_DUR = ("song-level pitch control ({keys}) needs inp['ph_dur'] (seconds per phone): without it the durations are the model's own, so the "
              "segment frame counts are not known before rendering and the contour cannot be cut into per-segment slices")
 
@@ -101,7 +103,7 @@ class SongPlan:
     """What `plan_song` returns, and what the renderer and the tests consume.
     segments[s] (song order): dict(index, first, last (exclusive), seconds, n_frames | None, start_frame | None, batch, row);
     batches[i]: dict of host tensors as `infer_batch` takes them (txt_tokens, note, note_dur, note_type [nb, Tp] zero padded; with ph_dur mel2ph
-        [nb, T]; with a contour pitch_hz = ([nb, T] fp32, [n_frames]), pitch_shift, pitch_align + pitch_align_band) - `sing_score` replaces each by its device form, with the
+        [nb, T]; with a contour pitch_hz = ([nb, T] fp32, [n_frames]), pitch_shift, pitch_align / pitch_timing + pitch_align_band) - `sing_score` replaces each by its device form, with the
         reference's features and style encoding added, so `infer_batch(plan.batches[i], seed=seed + i)` is what was rendered;
     rows[i][r] = song index of row r of batch i; n_frames = the song's frame count (None without ph_dur)."""
     segments: list
@@ -126,14 +128,15 @@ def check_pitch_keys(inp):
 def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_encoder=None):
     """inp: the reference's input dict at any length - `ph` (or `ph_token`), `note`, `note_dur`, `note_type`, optionally `ph_dur`, `pitch_hz`
     (a 1-D contour in Hz over the whole song, any length), `pitch_shift`, `pitch_align` ("dtw": each segment warps its slice of the contour onto its
-    own notes; the cut between segments stays linear) with `pitch_align_band_s`. -> SongPlan."""
+    own notes; the cut between segments stays linear) with `pitch_align_band_s`, `pitch_timing` ("guide": each segment is sung in the timing of
+    its slice). -> SongPlan."""
     keys = check_pitch_keys(inp)
     if "pitch_audio" in keys:
         raise ValueError("plan_song: the planner runs on the host; track inp['pitch_audio'] first and give its contour as inp['pitch_hz'] "
                          "(StyleSingerInfer.sing_score does)")
     if "pitch_shift" in keys and "pitch_hz" not in keys:
         raise ValueError("plan_song: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
-    align = align_inputs(inp, "pitch_hz" in keys, sr, hop)   # {} | pitch_align + pitch_align_band (frames); refusals as preprocess_input
+    align = align_inputs(inp, "pitch_hz" in keys, sr, hop)   # {} | pitch_align / pitch_timing + pitch_align_band (frames); refusals as preprocess_input
     if inp.get("ph_token") is not None:
         tokens = np.asarray(inp["ph_token"], dtype=np.int64)
     elif ph_encoder is not None and inp.get("ph") is not None:
@@ -293,11 +296,16 @@ def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flig
         song_place(res["mel"].contiguous(), seg, lens, offsets, 80, mel, flags=flags)
         song_place(res["f0"].contiguous(), seg, lens, offsets, 1, f0, flags=flags)
     unaligned = [res["model_out"]["pitch_align_status"].to(torch.int64) for res in results if "pitch_align_status" in res["model_out"]]
-    n_st = sum(u.numel() for u in unaligned)
-    *starts, flagged = (int(v) for v in torch.cat([*unaligned, offsets, flags.to(torch.int64)]).cpu())   # the one host sync of the stitch
-    st, starts = starts[:n_st], starts[n_st:]
-    if any(st):   # pitch_align: (batch order) rows -> song indices
-        rows_flat = [s for rows in plan.rows for s in rows]
+    loose = [res["model_out"]["pitch_retime_status"].to(torch.int64) for res in results if "pitch_retime_status" in res["model_out"]]
+    n_st, n_rt = sum(u.numel() for u in unaligned), sum(u.numel() for u in loose)
+    *starts, flagged = (int(v) for v in torch.cat([*unaligned, *loose, offsets, flags.to(torch.int64)]).cpu())   # the one host sync of the stitch
+    st, rt, starts = starts[:n_st], starts[n_st:n_st + n_rt], starts[n_st + n_rt:]
+    rows_flat = [s for rows in plan.rows for s in rows]   # (batch order) rows -> song indices
+    retime_status = {rows_flat[k]: v for k, v in enumerate(rt)}
+    if any(rt):
+        warnings.warn(f"sing_score: pitch_timing left segment(s) {sorted(s for s, v in retime_status.items() if v)} to the linear stretch (not aligned, "
+                      "or fewer guide frames than the segment has pitch changes)")
+    if any(st):
         warnings.warn(f"sing_score: pitch_align left segment(s) {sorted(rows_flat[k] for k, v in enumerate(st) if v)} to the linear fit (more guide "
                       "frames per score frame than the band allows); widen pitch_align_band_s")
     if flagged != 0:
@@ -308,6 +316,8 @@ def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flig
     for s, g in enumerate(plan.segments):
         g["start_frame"], g["n_frames"] = starts[s], starts[s + 1] - starts[s]
         out["segments"].append({k: g[k] for k in ("first", "last", "start_frame", "n_frames", "batch", "row")})
+        if retime_status:
+            out["segments"][-1]["pitch_retime_status"] = retime_status[s]
     long_ = [s for s, g in enumerate(plan.segments) if g["n_frames"] > 3000]
     if long_:
         warnings.warn(f"sing_score: {len(long_)} segment(s) came out longer than the 3000 frames the model was trained on (first: phones "
