@@ -502,6 +502,17 @@ int ss_layernorm(const float* x, float* y, const float* gamma, const float* beta
 int ss_attention(const float* Q, const float* K, const float* V, float* O, int B, int H, int D, int Tq, int Tk, int ldq,
                  int ldk, int ldv, int ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs,
                  const int32_t* qlens, const int32_t* klens, float scale, void* stream);
+/* The same core over a pool of R key segments with prior weights (additive export, ABI 20): K/V are [B][R*Ts][ldk|ldv], segment r of
+ * item b is rows [r*Ts, r*Ts + seg_lens[b][r]) and every score of it gets seg_logw[b][r] added before the softmax, which runs over
+ * the valid keys of all segments at once:  O[q] = sum_{r,k} softmax_{(r,k)}(scale Q[q].K[r,k] + seg_logw[b][r]) V[r,k].
+ * seg_logw = log of the normalised weight; a segment whose seg_logw is not finite (weight 0 -> -inf) or whose seg_lens is <= 0 is
+ * skipped, and its rows (like every row past a segment's length) are never read. A query with no valid key at all is written as 0.
+ * It is the key_padding_mask + additive attn_mask form of nn.MultiheadAttention (lse.py:19,41) without the [Tq][R*Ts] mask.
+ * D must be 128, R >= 1, Ts a positive multiple of 32 (the key tile: no tile straddles two segments); seg_lens and seg_logw are
+ * required. R = 1 with seg_logw = 0 returns the bits of ss_attention with klens = seg_lens. */
+int ss_attention_seg(const float* Q, const float* K, const float* V, float* O, int B, int H, int D, int Tq, int R, int Ts, int ldq,
+                     int ldk, int ldv, int ldo, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs, const int32_t* qlens,
+                     const int32_t* seg_lens, const float* seg_logw, float scale, void* stream);
 
 /* out[b][t][:] = scale * table[idx[b][t]][:]  (+ out if accumulate).  idx int64 (torch LongTensor).
  * nn.Embedding lookups: tts_modules.py:339-346, stylesinger.py:31-36,246 */

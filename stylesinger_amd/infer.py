@@ -141,10 +141,14 @@ class StyleSingerInfer(ReferenceProducers):
         `out_true_peak_db`: hold every item of `wav` under this true-peak ceiling with the look-ahead limiter (`_finish_wav`, `limiter.py`; adds
         res['limiter'] = {min_gain, n_limited} as device tensors); with `out_lufs` too the loudness gain is applied in full (res['loudness_gain'])
         and the limiter takes the place of the peak rule.
-        Optional `style_cache`: what `model.encode_style` returned for the batch's references; the style encoder is then skipped."""
+        Optional `style_cache`: what `model.encode_style` returned for the batch's references; the style encoder is then skipped.
+        A pool of references per item (`_device_batch` with inp['ref_audios']): `ref_mels` [B, R, Tr, 80], `ref_f0` [B, R, Tr] and optional
+        `ref_weights` (host values; priors on the style attention, forward(ref_weights=)), or a `style_cache` from `model.encode_style_blend`;
+        `spk_embed` / `emo_embed` are then the blended [B, 256] (`model.blend_embeds`)."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
-        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band", "pitch_timing") if batch.get(k) is not None}
+        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band", "pitch_timing", "ref_weights")
+                     if batch.get(k) is not None}
         if batch.get("style_cache") is not None:   # the references' style, encoded once by the caller (model.encode_style; `sing_score`)
             passed_on["style_cache"] = batch["style_cache"]
         out = self.model(batch["txt_tokens"], mel2ph=batch.get("mel2ph"), spk_embed=batch["spk_embed"], emo_embed=batch["emo_embed"],
@@ -243,7 +247,7 @@ class StyleSingerInfer(ReferenceProducers):
             from .denoise import device_table, geometry
             device_table(geometry(self.vocoder.hparams)[0], self.device)
         for i, batch in enumerate(batches):
-            need = max(int(batch["mel2ph"].shape[1]) if batch.get("mel2ph") is not None else 0, int(batch["ref_mels"].shape[1]))
+            need = max(int(batch["mel2ph"].shape[1]) if batch.get("mel2ph") is not None else 0, int(batch["ref_mels"].shape[-2]) + (31 if batch["ref_mels"].dim() == 4 else 0))   # (a pool's frame axis is padded to the 32-key tile)
             if need > warm:
                 warm = need
                 self.model.warm_caches(warm, self.device)
@@ -332,7 +336,8 @@ class StyleSingerInfer(ReferenceProducers):
         """Sing a score of any length in the reference's voice: `inp` = the reference's input dict (`ph` | `ph_token`, `note`, `note_dur`, `note_type`,
         optionally `ph_dur` = seconds per phone, `pitch_hz` | `pitch_audio`, `pitch_shift`, `pitch_align` (+ `pitch_align_band_s`): every segment
         then warps ITS slice of the contour onto its own notes, the slice's ends pinned; the planner's cut of the contour stays linear;
-        `ref_audio` or the reference's features). The score
+        `ref_audio` or the reference's features, or `ref_audios` (+ `ref_srs`, `ref_weights`) = a weighted pool of references, blended as
+        `_device_batch` / `model.encode_style_blend` describe and encoded once for the whole song). The score
         is cut into phrases at its rests (`song.plan_song`: policy and limits there), the reference is processed and its style encoded ONCE, the
         plan's batches run through `infer_batches` (batch i with seed + i), and the segments are put on one timeline on the device
         (`ss_song_offsets` + three `ss_song_place` per batch: the waveform with a raised-cosine fade of `fade_ms` on both sides of every joint, the
@@ -366,14 +371,19 @@ class StyleSingerInfer(ReferenceProducers):
         return score_wavs(self, wav, lens, tw[None] if tw.dim() == 1 else tw, target_lens, srs_b=target_srs, align=align, band_s=band_s)
 
     @classmethod
-    def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, pitch=None, **ctor):
+    def example_run(cls, hparams=None, ref_audio="test/test.wav", out_path="infer_out/test.wav", vad_flags=None, pitch=None, ref_blend=None, **ctor):
         """inference/StyleSinger.py:181-331: the example score (stylesinger_amd/example_input.json = that method's input dict, extracted by
         `python -m oracle.gen_golden --round6`) sung in the style of `ref_audio`, written to `out_path` as 16-bit PCM (utils/audio.py:12-17).
         `ctor`: how to build the instance - `exp_dir` + `vocoder_dir` (the reference's checkpoints, `from_checkpoints`) or explicit
-        `model_state` / `vocoder_state` / `emotion_state` / `speaker_state` / `phone_set`."""
+        `model_state` / `vocoder_state` / `emotion_state` / `speaker_state` / `phone_set`. `ref_blend` = (paths, weights): sing in a weighted
+        blend of these references instead (inp['ref_audios'] / ['ref_weights']; `ref_audio` is then unused)."""
         with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "example_input.json")) as fh:
             inp = {k: v for k, v in json.load(fh).items() if k != "source"}
-        inp["ref_audio"] = ref_audio
+        if ref_blend is not None:
+            inp.pop("ref_audio", None)   # (the example dict names the reference's own test clip)
+            inp["ref_audios"], inp["ref_weights"] = list(ref_blend[0]), list(ref_blend[1])
+        else:
+            inp["ref_audio"] = ref_audio
         inp.update(pitch or {})   # pitch control: pitch_hz | pitch_audio, pitch_shift (`_pitch_inputs`)
         ins = _instance(cls, hparams, ctor)
         out = ins.infer_once(inp, vad_flags=vad_flags)
@@ -412,6 +422,7 @@ def main(argv=None):
     hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--out-true-peak DB [--out-lookahead-ms 2]`: hold the result under DB dBFS
     true peak with the look-ahead limiter (with --out-lufs the loudness gain is then applied in full instead of being divided by the peak); `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
     subtraction of V, e.g. 0.1) after the generator, before the loudness target and the writer.
+    `--ref-blend PATH WEIGHT` (repeatable) [`--ref-weight W`]: sing in a weighted blend of --ref-audio (weight W, default 1) and these references.
     `--score song.json [--max-seconds 12] [--segment-batch 8] [--fade-ms 5] [--segments-out timeline.json]`: sing a score of any length (the keys of
     example_input.json, optionally `ph_dur`; its `ref_audio` unless --ref-audio is given) with `sing_score`; pitch flags then need `ph_dur` in the score."""
     import argparse
@@ -422,6 +433,10 @@ def main(argv=None):
     ap.add_argument("--speaker-ckpt", required=True, help="resemblyzer's pretrained.pt")
     ap.add_argument("--phone-set", required=True)
     ap.add_argument("--ref-audio", help="the reference voice (default: the score file's ref_audio, else test/test.wav)")
+    ap.add_argument("--ref-blend", nargs=2, action="append", metavar=("PATH", "WEIGHT"), help="one more reference voice and its weight (repeatable): "
+                    "the style attention then runs over --ref-audio and these together, the weights as priors on it (not a linear mix of outputs), "
+                    "and the speaker / emotion embeddings are the weighted, re-normalised means (rendered quality of such blends is unassessed)")
+    ap.add_argument("--ref-weight", type=float, metavar="W", help="--ref-blend: the weight of --ref-audio itself (default 1.0)")
     ap.add_argument("--out", default="infer_out/test.wav")
     ap.add_argument("--no-vad-trim", action="store_true", help="explicit opt-out of trim_long_silences (webrtcvad missing)")
     ap.add_argument("--vad", choices=["webrtc", "lrt"], help="the voice-activity decision inside trim_long_silences: webrtc = the reference's (the "
@@ -481,6 +496,16 @@ def main(argv=None):
         pitch["pitch_align_band_s"] = a.pitch_align_band_s
     if a.pitch_timing is not None:
         pitch["pitch_timing"] = a.pitch_timing
+    if a.ref_weight is not None and not a.ref_blend:
+        ap.error("--ref-weight is the weight of --ref-audio among --ref-blend references; it needs --ref-blend")
+    ref_blend = None
+    if a.ref_blend:
+        from .model import resolve_ref_weights
+        try:
+            weights = [1.0 if a.ref_weight is None else a.ref_weight] + [float(w) for _, w in a.ref_blend]
+            resolve_ref_weights(weights, 1, len(weights))
+        except ValueError as e:
+            ap.error(f"--ref-blend / --ref-weight: {e}")
     score = None
     if a.score:
         with open(a.score) as fh:
@@ -496,9 +521,13 @@ def main(argv=None):
             ap.error(str(e))
         if a.ref_audio or not score.get("ref_audio"):
             score["ref_audio"] = a.ref_audio or "test/test.wav"
+        if a.ref_blend:   # the first reference is the one --ref-audio (or the score file) names
+            score["ref_audios"], score["ref_weights"] = [score.pop("ref_audio")] + [p for p, _ in a.ref_blend], weights
     elif a.segments_out:
         ap.error("--segments-out needs --score")
     a.ref_audio = a.ref_audio or "test/test.wav"
+    if a.ref_blend:
+        ref_blend = ([a.ref_audio] + [p for p, _ in a.ref_blend], weights)
     emo = torch.load(a.emotion_ckpt, map_location="cpu", weights_only=False)
     spk = torch.load(a.speaker_ckpt, map_location="cpu", weights_only=False)
     hp = {}
@@ -535,7 +564,7 @@ def main(argv=None):
         _score_run(score, hp or None, a.out, segments_out=a.segments_out, vad_flags=False if a.no_vad_trim else a.vad, max_seconds=a.max_seconds,
                    segment_batch=a.segment_batch, fade_ms=a.fade_ms, **ctor)
         return
-    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch=pitch, **ctor)
+    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch=pitch, ref_blend=ref_blend, **ctor)
 
 
 if __name__ == "__main__":

@@ -770,3 +770,8 @@ def layernorm(x, gamma, beta, *, B, T, C_, out=None, lens=None, mask_rows=False,
 
 def attention(Q, K, V, O, *, B, H, D, Tq, Tk, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, qlens=None, klens=None, scale):
     ops.ss_attention(Q, K, V, O, B, H, D, Tq, Tk, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, qlens, klens, float(scale))
+
+
+def attention_seg(Q, K, V, O, *, B, H, D, Tq, R, Ts, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, qlens=None, seg_lens, seg_logw, scale):
+    """ss_attention_seg: the attention core over R key segments of Ts rows with per-segment lengths and log prior weights [B, R]."""
+    ops.ss_attention_seg(Q, K, V, O, B, H, D, Tq, R, Ts, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, qlens, seg_lens, seg_logw, float(scale))

@@ -37,6 +37,51 @@ def _noise_btm(x, dev, shape, T):
     return _pad_frames(x.to(dev).float().reshape(*shape), T).transpose(-1, -2).contiguous()
 
 
+def resolve_ref_weights(ref_weights, B, R):
+    """The prior weights of a pool of R references per item -> (logw fp32 [B, R], p float64 [B, R]) as host numpy arrays: p = w / sum(w) in
+    float64, logw = float32(log p) with -inf where p == 0 (R = 1 gives 0.0 exactly). `ref_weights`: None (equal weights), a length-R sequence
+    (the same weights for every item) or [B, R]; host values - a device tensor is copied to the host. Refused with ValueError before a device is
+    touched: another shape, a negative or non-finite weight, a row that sums to zero."""
+    import numpy as np
+    if B < 1 or R < 1:
+        raise ValueError(f"ref_weights: {R} references for a batch of {B}: at least one each")
+    if ref_weights is None:
+        w = np.ones((B, R), dtype=np.float64)
+    else:
+        if torch.is_tensor(ref_weights):
+            ref_weights = ref_weights.detach().cpu().numpy()
+        w = np.array(ref_weights, dtype=np.float64)
+        if w.ndim == 1 and w.shape[0] == R:
+            w = np.broadcast_to(w, (B, R)).copy()
+        if w.shape != (B, R):
+            raise ValueError(f"ref_weights: shape {tuple(w.shape)} for {R} references and a batch of {B}: expected [{R}] or [{B}, {R}]")
+    if not np.isfinite(w).all():
+        raise ValueError("ref_weights: every weight must be finite")
+    if (w < 0).any():
+        raise ValueError("ref_weights: every weight must be >= 0")
+    with np.errstate(over="ignore"):
+        total = w.sum(axis=1, keepdims=True)
+    if not (total > 0).all():
+        raise ValueError("ref_weights: the weights of an item must not all be zero")
+    p = w / total
+    if not (p.sum(axis=1) > 0).all() or not np.isfinite(p).all():   # (w / sum(w) of huge weights: inf / inf)
+        raise ValueError("ref_weights: the weights of an item do not normalise in float64")
+    with np.errstate(divide="ignore"):
+        logw = np.log(p).astype(np.float32)
+    return logw, p
+
+
+def blend_embeds(e, p):
+    """The embedding of a reference pool: e [B, R, C] unit-norm embeddings, p [B, R] normalised weights (a tensor or host values) ->
+    l2norm(sum_r p_r e_r) [B, C] fp32, divided by max(norm, 1e-12). Torch ops on e's device, no host sync."""
+    e = e.float()
+    p = torch.as_tensor(p).to(device=e.device, dtype=torch.float32)
+    if e.dim() != 3 or tuple(p.shape) != tuple(e.shape[:2]):
+        raise ValueError(f"blend_embeds: embeddings {tuple(e.shape)} with weights {tuple(p.shape)}: expected [B, R, C] and [B, R]")
+    m = (e * p[:, :, None]).sum(dim=1)
+    return m / m.norm(dim=1, keepdim=True).clamp_min(1e-12)
+
+
 class StyleSingerHIP(Packing, Plans, torch.nn.Module):
     def __init__(self, dictionary=None, out_dims=None, hparams=None):
         super().__init__()
@@ -281,6 +326,28 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         return dict(sty=sty, lens_r=lens_r, ref_f0=ref_f0, style_pre_rq=pre_rq, rq_codes=codes, style_rq=zq)
 
     @torch.no_grad()
+    def encode_style_blend(self, ref_mels, ref_f0, ref_weights=None):
+        """The style of a POOL of R references per item, weighted: ref_mels [B, R, Tr, 80], ref_f0 [B, R, Tr], ref_weights None (equal), a length-R
+        sequence or [B, R] host values (`resolve_ref_weights`: w >= 0, normalised per item). Every reference is encoded on its own by
+        `encode_style` (one pass over the flat [B * R] batch; positions restart per reference), its frame axis zero-padded to Ts, a multiple of
+        the attention's 32-key tile. The result is a style cache for forward(style_cache=...) whose tensors all lead with B: `sty` [B, R * Ts, H]
+        with reference r in rows [r * Ts, r * Ts + seg_lens[b, r]), `seg_lens` int32 [B, R], `seg_logw` fp32 [B, R] = log of the normalised
+        weight (-inf = weight 0), and `ref_f0`, `style_pre_rq`, `rq_codes`, `style_rq` as [B, R * Ts, ...]. The style-to-content attention then
+        runs over all references at once with seg_logw added to the scores (`ss_attention_seg`): the weights are PRIORS on the attention over the
+        pooled frames - equal weights = the clips concatenated, (1, 0) = the first clip alone - not a linear mix of outputs. The speaker and
+        emotion embeddings are blended separately (`blend_embeds`); how a checkpoint renders blended embeddings is unassessed."""
+        if ref_mels.dim() != 4 or ref_f0.dim() != 3 or tuple(ref_f0.shape) != tuple(ref_mels.shape[:3]):
+            raise ValueError(f"encode_style_blend: ref_mels {tuple(ref_mels.shape)} / ref_f0 {tuple(ref_f0.shape)}: expected [B, R, Tr, 80] and [B, R, Tr]")
+        B, R, Tr, M = ref_mels.shape
+        logw, _p = resolve_ref_weights(ref_weights, B, R)
+        Ts = (Tr + 31) // 32 * 32
+        sc = self.encode_style(_pad_frames(ref_mels.float(), Ts, dim=2).reshape(B * R, Ts, M), _pad_frames(ref_f0.float(), Ts).reshape(B * R, Ts))
+        out = {k: sc[k].reshape(B, R * Ts, *sc[k].shape[2:]) for k in ("sty", "ref_f0", "style_pre_rq", "rq_codes", "style_rq")}
+        out["seg_lens"] = sc["lens_r"].reshape(B, R)
+        out["seg_logw"] = torch.from_numpy(logw).to(ref_mels.device)
+        return out
+
+    @torch.no_grad()
     @torch.no_grad()
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, emo_embed=None, ref_mels=None, ref_f0=None, f0=None, uv=None,
                 skip_decoder=False, global_steps=0, infer=False, note=None, note_dur=None, note_type=None, **kwargs):
@@ -298,6 +365,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         shallow_diffusion_tts.py:165-197), `plan_slot` (workspace/graph set to use: give concurrent forwards on different streams
         different slots), `style_cache` (the dict encode_style() returned for these references: skips
         the style encoder).
+
+        Several references per item: `ref_mels` [B, R, Tr, 80] with `ref_f0` [B, R, Tr] (+ `ref_weights`: None = equal, a length-R sequence or
+        [B, R] host values >= 0) is a weighted pool - `encode_style_blend` encodes every reference on its own and the style-to-content attention
+        runs over all of them at once with log(weight) added to the scores (`ss_attention_seg`): priors on the attention, not a linear mix of
+        outputs. A `style_cache` from `encode_style_blend` does the same without the encoder. `spk_embed` / `emo_embed` stay [B, 256]: blend
+        them with `blend_embeds` (unassessed on a checkpoint). 3-D `ref_mels` behave exactly as before; `ref_weights` with them is a ValueError.
 
         Pitch control (infer=True only): sing on a GIVEN f0 contour instead of the two f0 diffusions' output. Two forms:
           * `f0=, uv=` [B, T_out] - the reference's own form (hparams['use_gt_f0'], tasks/StyleSinger/stylesinger.py:176-188): what
@@ -360,6 +433,15 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         if pitch_timing is not None and kwargs.get("f0_steps") is not None:
             raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with pitch_timing (a pitch_hz contour) they do not run")
         f0_ts, f0_eta = self._f0_sampler_args(kwargs, f0 is not None or pitch_hz is not None)
+        pooled = ref_mels is not None and ref_mels.dim() == 4
+        if pooled and (ref_f0 is None or ref_f0.dim() != 3):
+            raise ValueError(f"forward: ref_mels {tuple(ref_mels.shape)} is a pool of references per item; ref_f0 must then be [B, R, Tr]")
+        if kwargs.get("ref_weights") is not None:
+            if kwargs.get("style_cache") is not None:
+                raise ValueError("forward: ref_weights are part of the style_cache (encode_style_blend(..., ref_weights)); give them there")
+            if not pooled:
+                raise ValueError("forward: ref_weights weigh a pool of references: ref_mels [B, R, Tr, 80] and ref_f0 [B, R, Tr]")
+            resolve_ref_weights(kwargs["ref_weights"], ref_mels.shape[0], ref_mels.shape[1])   # refused here, before anything is launched
         self._ensure_packed()
         # c: the per-call state the stages share (shapes, lengths, intermediate activations, the plan) and the result dict
         c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, noise=kwargs.get("noise"), seed=int(kwargs.get("seed", self.hp["seed"])),
@@ -508,8 +590,18 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         B, T, H = c.B, c.T, self.hp["hidden_size"]
         sc = c.kwargs.get("style_cache")
         if sc is None:
-            sc = self.encode_style(ref_mels, ref_f0)
-        sty, lens_r, Tr = sc["sty"], sc["lens_r"], sc["sty"].shape[1]
+            if ref_mels.dim() == 4:   # a pool of references per item (checked by forward): the weighted blend
+                sc = self.encode_style_blend(ref_mels, ref_f0, c.kwargs.get("ref_weights"))
+            else:
+                sc = self.encode_style(ref_mels, ref_f0)
+        seg_lens = sc.get("seg_lens")   # a blend cache (encode_style_blend): R segments of Ts key rows, one ss_attention_seg launch per layer
+        sty, lens_r, Tr = sc["sty"], sc.get("lens_r"), sc["sty"].shape[1]
+        if seg_lens is not None:
+            R = seg_lens.shape[1]
+            if tuple(seg_lens.shape) != (B, R) or tuple(sc["seg_logw"].shape) != (B, R) or Tr % R or (Tr // R) % 32:
+                raise ValueError(f"forward: style_cache of a blend: sty {tuple(sty.shape)}, seg_lens {tuple(seg_lens.shape)}, seg_logw "
+                                 f"{tuple(sc['seg_logw'].shape)} for a batch of {B}: expected [B, R * Ts, H] with Ts a multiple of 32 and [B, R] twice")
+            seg_lens, seg_logw = seg_lens.contiguous(), sc["seg_logw"].contiguous()
         ret["ref_f0"], ret["style_pre_rq"] = sc["ref_f0"], sc["style_pre_rq"]
         ret["rq_codes"], ret["style_rq"], ret["rq_loss"] = sc["rq_codes"], sc["style_rq"], 0.0
         xs = c.dec.clone()
@@ -520,8 +612,13 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         for al in pk["align"]:
             self._gemm(xs, al["q"], q, B, T, mask_rows=False)
             self._gemm(sty, al["kv"], kv, B, Tr, mask_rows=False)
-            L.attention(q, kv, kv[:, :, H:], att, B=B, H=2, D=H // 2, Tq=T, Tk=Tr, ldq=H, ldk=2 * H, ldv=2 * H, ldo=H,
-                        q_bs=T * H, k_bs=Tr * 2 * H, v_bs=Tr * 2 * H, o_bs=T * H, qlens=None, klens=lens_r, scale=(H // 2) ** -0.5)
+            if seg_lens is not None:
+                L.attention_seg(q, kv, kv[:, :, H:], att, B=B, H=2, D=H // 2, Tq=T, R=R, Ts=Tr // R, ldq=H, ldk=2 * H, ldv=2 * H, ldo=H,
+                                q_bs=T * H, k_bs=Tr * 2 * H, v_bs=Tr * 2 * H, o_bs=T * H, qlens=None, seg_lens=seg_lens, seg_logw=seg_logw,
+                                scale=(H // 2) ** -0.5)
+            else:
+                L.attention(q, kv, kv[:, :, H:], att, B=B, H=2, D=H // 2, Tq=T, Tk=Tr, ldq=H, ldk=2 * H, ldv=2 * H, ldo=H,
+                            q_bs=T * H, k_bs=Tr * 2 * H, v_bs=Tr * 2 * H, o_bs=T * H, qlens=None, klens=lens_r, scale=(H // 2) ** -0.5)
             self._gemm(att, al["out"], xs, B, T, R=xs, mask_rows=False)
             L.layernorm(xs, *al["n1"], B=B, T=T, C_=H)
             self._gemm(xs, al["l1"], ffh, B, T, act=L.ACT_RELU, mask_rows=False)

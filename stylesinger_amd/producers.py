@@ -293,6 +293,10 @@ class ReferenceProducers:
         """`preprocess_input` + `input_to_batch` (inference/StyleSinger.py:94-172) for ONE item with every producer on the device: the dict
         `infer_batch` takes, device tensors only (+ `ref_f0_hz`, `n_mel`, `wav_fn`). ONE pass of the f0 tracker."""
         sr, hop = int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])
+        if inp.get("ref_audios") is not None:
+            return self._device_batch_pool(inp, vad_flags)
+        if inp.get("ref_weights") is not None or inp.get("ref_srs") is not None:
+            raise ValueError("preprocess_input: inp['ref_weights'] / inp['ref_srs'] belong to inp['ref_audios'] (a list of references)")
         wav, in_sr, path = as_waveform(inp["ref_audio"], inp.get("ref_sr") or sr, "ref_audio")
         if "ph_token" not in inp:
             if self.ph_encoder is None:
@@ -305,6 +309,55 @@ class ReferenceProducers:
                                       mel2ph=row(inp["mel2ph"], torch.long) if "mel2ph" in inp else None, emo_vad_flags=self._resolve_vad(vad_flags),
                                       ref_srs=[in_sr])
         batch["n_mel"], batch["wav_fn"] = out_len(len(wav), in_sr, sr) // hop + 1, path
+        batch.update(self._pitch_inputs(inp))
+        return batch
+
+    @torch.no_grad()
+    def _device_batch_pool(self, inp, vad_flags=None):
+        """`_device_batch` for a POOL of references: inp['ref_audios'] = a list of R entries, each whatever `as_waveform` accepts (a list under
+        'ref_audio' could not say this: a (waveform, sample_rate) pair already means one clip there), inp['ref_srs'] = optional rates of bare
+        arrays (one per entry, None = the model's), inp['ref_weights'] = optional R weights >= 0 (default equal; `model.resolve_ref_weights`).
+        The R clips go through `preprocess_batch` ONCE, as a batch of R. -> the dict `infer_batch` takes with `ref_mels` [1, R, Tr, 80],
+        `ref_f0` [1, R, Tr], `ref_weights` (the normalised weights, host float64 [1, R]) and `spk_embed` / `emo_embed` [1, 256] = the
+        weighted, re-normalised means of the clips' embeddings (`model.blend_embeds`); `n_mel` / `wav_fn` are lists of R."""
+        from .model import blend_embeds, resolve_ref_weights
+        sr, hop = int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])
+        if inp.get("ref_audio") is not None:
+            raise ValueError("preprocess_input: give inp['ref_audio'] (one reference) or inp['ref_audios'] (a list of references), not both")
+        if inp.get("ref_sr") is not None:
+            raise ValueError("preprocess_input: with inp['ref_audios'] the rates of bare arrays go in inp['ref_srs'] (one per reference), not inp['ref_sr']")
+        auds = inp["ref_audios"]
+        if not isinstance(auds, (list, tuple)) or len(auds) < 1:
+            raise ValueError("preprocess_input: inp['ref_audios'] must be a non-empty list of references (WAV paths, (waveform, sample_rate) pairs or arrays)")
+        R = len(auds)
+        srs = inp.get("ref_srs")
+        if srs is not None and len(srs) != R:
+            raise ValueError(f"preprocess_input: {len(srs)} inp['ref_srs'] for {R} inp['ref_audios']")
+        _logw, p = resolve_ref_weights(inp.get("ref_weights"), 1, R)   # a bad weight is refused before a file is read or a device touched
+        vad = self._resolve_vad(vad_flags)
+        if vad is not None and not isinstance(vad, str):
+            raise ValueError("preprocess_input: vad_flags as an array describes ONE clip; with inp['ref_audios'] give None, False, 'webrtc' or 'lrt'")
+        clips = [as_waveform(a, (srs[i] if srs is not None and srs[i] else sr), f"ref_audios[{i}]") for i, a in enumerate(auds)]
+        lens = [len(w) for w, _, _ in clips]
+        if min(lens) < 1:
+            raise ValueError(f"preprocess_input: inp['ref_audios'][{lens.index(min(lens))}] is empty")
+        wavs = np.zeros((R, max(lens)), dtype=np.float32)
+        for i, (w, _, _) in enumerate(clips):
+            wavs[i, :len(w)] = w
+        if "ph_token" not in inp:
+            if self.ph_encoder is None:
+                raise ValueError("preprocess_input: give inp['ph_token'], construct StyleSingerInfer(..., phone_set=<phone_set.json>) or set "
+                                 "self.ph_encoder (the reference's build_token_encoder(f'{processed_data_dir}/phone_set.json'))")
+            inp["ph_token"] = self.ph_encoder.encode(" ".join(inp["ph"]))
+        in_srs = [r for _, r, _ in clips]
+        batch = self.preprocess_batch(torch.from_numpy(wavs), lens, None, None, row(inp["ph_token"], torch.long), row(inp["note"], torch.long),
+                                      row(inp["note_dur"], torch.float32), row(inp["note_type"], torch.long),
+                                      mel2ph=row(inp["mel2ph"], torch.long) if "mel2ph" in inp else None, emo_vad_flags=vad, ref_srs=in_srs)
+        batch["spk_embed"] = blend_embeds(batch["spk_embed"][None], p)
+        batch["emo_embed"] = blend_embeds(batch["emo_embed"][None], p)
+        batch["ref_mels"], batch["ref_f0"], batch["ref_f0_hz"] = batch["ref_mels"][None], batch["ref_f0"][None], batch["ref_f0_hz"][None]
+        batch["ref_weights"] = p
+        batch["n_mel"], batch["wav_fn"] = [out_len(n, r, sr) // hop + 1 for n, r in zip(lens, in_srs)], [path for _, _, path in clips]
         batch.update(self._pitch_inputs(inp))
         return batch
 
@@ -350,7 +403,11 @@ class ReferenceProducers:
         `speaker_state` (the two encoders' checkpoints). `vad_flags`: see `_resolve_vad` (None = webrtcvad on the host unless the instance was made with `vad=`,
         False = opt out, "lrt" = this project's own decision on the device).
         Pitch control (`_pitch_inputs`): `inp['pitch_hz']` / `inp['pitch_shift']` pass through; `inp['pitch_audio']` (a guide vocal) is tracked
-        on the device and replaced by its contour in `inp['pitch_hz']`."""
+        on the device and replaced by its contour in `inp['pitch_hz']`.
+        One reference only, as in the reference: a pool (`inp['ref_audios']`) has no single `mel` / `f0` to return - use `infer_once`."""
+        if inp.get("ref_audios") is not None:
+            raise ValueError("preprocess_input mirrors the reference's single-reference dict (mel, f0, spk_embed, emo_embed of ONE clip); "
+                             "inp['ref_audios'] (a pool of references) goes through infer_once or sing_score")
         batch = self._device_batch(inp, vad_flags)
         n_mel = batch["n_mel"]
         inp.update(item_name=inp.get("name"), wav_fn=batch["wav_fn"],

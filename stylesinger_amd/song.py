@@ -237,21 +237,29 @@ def song_place(src, seg, lens, offsets, unit, out, win=None, flags=None, cap=Non
 
 # ---- the renderer: `StyleSingerInfer.sing_score` ----------------------------------------------------------------------------------------------
 def _song_reference(ins, inp, vad_flags):
-    """The reference of a song, processed ONCE: (ref_mels [1, Tr, 80], ref_f0 [1, Tr], spk_embed [1, 256], emo_embed [1, 256]) on the device,
+    """The reference of a song, processed ONCE: (ref_mels [1, Tr, 80], ref_f0 [1, Tr], spk_embed [1, 256], emo_embed [1, 256], None) on the device,
     from the features in `inp` (`mel`, `spk_embed`, `emo_embed`, `f0`: as `infer_once` accepts them) or from inp['ref_audio'] through the
-    producers of `_device_batch`."""
+    producers of `_device_batch`. A pool of references (inp['ref_audios'], + 'ref_srs', 'ref_weights'): ref_mels [1, R, Tr, 80], ref_f0 [1, R, Tr], the
+    two embeddings blended, and the normalised weights as a fifth entry (None for one reference)."""
     d = ins.device
+    if inp.get("ref_audios") is not None:
+        if has_features(inp):
+            raise ValueError("sing_score: give inp['ref_audios'] (a pool of references) or the features of one reference (mel / spk_embed / emo_embed / f0), not both")
+        one = {k: inp[k] for k in ("ref_audios", "ref_audio", "ref_sr", "ref_srs", "ref_weights", "ph", "ph_token", "note", "note_dur", "note_type") if k in inp}
+        b = ins._device_batch(one, vad_flags)
+        inp.setdefault("ph_token", one["ph_token"])
+        return b["ref_mels"], b["ref_f0"], b["spk_embed"], b["emo_embed"], b["ref_weights"]
     if has_features(inp):
         from .pitch import norm_interp_f0
         f0, _uv = norm_interp_f0(np.asarray(inp["f0"]), ins.hparams)
         return (row(inp["mel"], torch.float32).to(d), f0[None].to(d), row(inp["spk_embed"], torch.float32).to(d),
-                row(inp["emo_embed"], torch.float32).to(d))
+                row(inp["emo_embed"], torch.float32).to(d), None)
     if inp.get("ref_audio") is None:
         raise ValueError("sing_score: give inp['ref_audio'] (the reference voice), or its features mel / spk_embed / emo_embed / f0")
     one = {k: inp[k] for k in ("ref_audio", "ref_sr", "ph", "ph_token", "note", "note_dur", "note_type") if k in inp}
     b = ins._device_batch(one, vad_flags)
     inp.setdefault("ph_token", one["ph_token"])
-    return b["ref_mels"], b["ref_f0"], b["spk_embed"], b["emo_embed"]
+    return b["ref_mels"], b["ref_f0"], b["spk_embed"], b["emo_embed"], None
 
 
 @torch.no_grad()
@@ -264,13 +272,14 @@ def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flig
     inp = dict(inp)
     check_pitch_keys(inp)   # pitch control without ph_dur is refused before a device is touched
     seed = hp["seed"] if seed is None else seed
-    ref_mels, ref_f0, spk, emo = _song_reference(ins, inp, vad_flags)
+    ref_mels, ref_f0, spk, emo, ref_w = _song_reference(ins, inp, vad_flags)
     if inp.get("pitch_audio") is not None:   # the guide vocal is tracked on the device; the planner takes its contour
         hz, _n = ins._pitch_inputs({"pitch_audio": inp.pop("pitch_audio")})["pitch_hz"]
         inp["pitch_hz"] = hz[0].cpu().numpy()
     plan = plan_song(inp, sr=sr, hop=hop, max_seconds=max_seconds, segment_batch=segment_batch, ph_encoder=ins.ph_encoder)
     S = len(plan.segments)
-    style = ins.model.encode_style(ref_mels, ref_f0)
+    # one encode for the whole song; a pool of references is encoded once too, as one blend cache (every tensor of it leads with the batch)
+    style = ins.model.encode_style(ref_mels, ref_f0) if ref_mels.dim() == 3 else ins.model.encode_style_blend(ref_mels, ref_f0, ref_w)
     fade = max(0, int(round(float(fade_ms) * sr / 1000.0))) if S > 1 else 0
     win = torch.from_numpy(fade_window(fade)).to(d) if fade else None
     segs_dev, rows_dev = [], []
@@ -278,7 +287,7 @@ def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flig
         nb = len(plan.rows[i])
         b = {k: ((v[0].to(d), v[1]) if k == "pitch_hz" else v.to(d) if torch.is_tensor(v) else v) for k, v in hb.items()}
         rep = lambda x: x.expand(nb, *x.shape[1:]).contiguous()
-        b.update(spk_embed=rep(spk), emo_embed=rep(emo), ref_mels=ref_mels.expand(nb, -1, -1), ref_f0=ref_f0.expand(nb, -1),
+        b.update(spk_embed=rep(spk), emo_embed=rep(emo), ref_mels=ref_mels.expand(nb, *ref_mels.shape[1:]), ref_f0=ref_f0.expand(nb, *ref_f0.shape[1:]),
                  style_cache={k: rep(v) for k, v in style.items()})
         plan.batches[i] = b
         rows_dev.append(torch.tensor(plan.rows[i], dtype=torch.long).to(d))
