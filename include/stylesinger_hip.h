@@ -711,6 +711,23 @@ int ss_meldiff_sample(const ss_wavenet* net, float* x, const float* cond, const 
 int ss_meldiff_sample_ddim(const ss_wavenet* net, float* x, const float* cond, const int32_t* lens, int B, int T,
                            const int32_t* ts, int n_ts, const double* alphas_cumprod, float eta, const float* noise, uint64_t seed,
                            const uint64_t* seed_dev, int precompute_cond, void* ws, int64_t ws_bytes, void* stream);
+/* DPM-Solver++ multistep sampler (Lu et al. 2022, Algorithm 2: data prediction, "2M") over the same strided list: ts[0] > ts[1] > ... (HOST array)
+ * inside [0, net->steps), alphas_cumprod as above (HOST, DOUBLE). With alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha / sigma) and
+ * x0_i = clamp(sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] eps, -1, 1) at t = ts[i] (the DDIM entry's own x0), the transition t -> s = ts[i+1] is
+ *   order 1:  x' = c1 x0_i + c2 x, (c1, c2) = the DDIM coefficients at eta = 0 (= -alpha_s (e^-h - 1), sigma_s / sigma_t; h = lambda_s - lambda_t)
+ *   order 2:  x' = b0 x0_i + b1 x0_{i-1} + c2 x, r = (lambda_t - lambda_{ts[i-1]}) / h, b0 = c1 (1 + 1/(2r)), b1 = -c1 / (2r)
+ * The first transition of a list and the last one (to x_0: ac_s = 1, h = inf) are first order whatever `order` says; order = 1 is
+ * ss_meldiff_sample_ddim(eta = 0) bit for bit. Deterministic: nothing is drawn. Coefficients in double on the host, cast to fp32 once.
+ *   hist: device scratch of 2*B*T*in_dim floats, 16-byte aligned like x: [0, n) the evaluation's eps, [n, 2n) the clamped x0 of the previous
+ *         position. Rows t >= lens[b] of x and of the stored x0 are written as 0.
+ *   [i_lo, i_hi): the list positions this call runs (whole list: 0, n_ts), the loop-cut contract of ss_f0diff_sample_strided; a call with
+ *         i_lo > 0 and order = 2 finds x0 of position i_lo - 1 in hist, where the call that ran that position left it.
+ * Refused before any launch (SS_ERR_ARG, ss_last_error): a null pointer, n_ts < 1, a list that is not strictly decreasing or leaves [0, steps),
+ * a bad [i_lo, i_hi), an order outside {1, 2}, in_dim not a multiple of 4, x or hist not 16-byte aligned. */
+int ss_meldiff_sample_dpmpp(const ss_wavenet* net, float* x, const float* cond, const int32_t* lens, int B, int T, const int32_t* ts, int n_ts,
+                            int i_lo, int i_hi, const double* alphas_cumprod /* HOST [steps] */, int order /* 1 | 2 */,
+                            float* hist /* device, 2*B*T*in_dim floats: eps scratch, x0 history */, int precompute_cond, void* ws, int64_t ws_bytes,
+                            void* stream);
 
 /* PLMS ("pndm_speedup") sampler of the reference: modules/diff/shallow_diffusion_tts.py:165-197 (p_sample_plms) driven as
  * in :254-260 - network times reversed(range(0, step_hi, interval)) with step_hi = K_step (the shallow-diffusion depth x

@@ -66,6 +66,11 @@ DEFAULT_HPARAMS = dict(
     # not reference keys: sample the two f0 / uv diffusions at this many of their f0_timesteps network times (forward(f0_steps=); None = the
     # reference's full ancestral loop) with this eta (0 = deterministic Gaussian half ... 1 = ancestral)
     f0_sample_steps=None, f0_sample_eta=1.0,
+    # not reference keys: how the shallow mel loop is sampled when forward() is not told (forward(sampler=, mel_steps=, mel_order=, mel_spacing=,
+    # eta=)): mel_sampler None = the reference's choice (PLMS under pndm_speedup, else its ancestral loop) or "ddpm" / "ddim" / "plms" / "dpmpp"
+    # (DPM-Solver++ multistep); mel_sample_steps = network times of the strided samplers; mel_sample_order 1 | 2 (dpmpp); mel_sample_spacing
+    # None = the sampler's own default ("uniform" for ddim, "logsnr" for dpmpp); mel_sample_eta (ddim)
+    mel_sampler=None, mel_sample_steps=None, mel_sample_order=2, mel_sample_spacing=None, mel_sample_eta=0.0,
 )
 
 # The released HiFi-GAN config ships only inside the un-vendored checkpoint

@@ -282,6 +282,104 @@ extern "C" int ss_meldiff_sample_ddim(const ss_wavenet* net, float* x, const flo
 }
 
 // ---------------------------------------------------------------------------------------------
+// DPM-Solver++ multistep sampler (Lu et al. 2022, "DPM-Solver++", Algorithm 2: data prediction, 2M) over the strided list of the DDIM entry.
+// With alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha / sigma), h = lambda_s - lambda_t and x0_i the clamped x0 prediction at ts[i]
+// (ss_ddpm_update's own expression), the transition t = ts[i] -> s = ts[i+1] is
+//   order 1:  x' = c1 x0_i + c2 x,  (c1, c2) = ddim_coef(ac_t, ac_s, 0) = (-alpha_s (e^-h - 1), sigma_s / sigma_t): DDIM with eta = 0
+//   order 2:  x' = b0 x0_i + b1 x0_{i-1} + c2 x,  r = (lambda_t - lambda_{ts[i-1]}) / h,  b0 = c1 (1 + 1/(2r)),  b1 = -c1 / (2r)
+// Order 2 needs a previous x0 and a finite h: the first transition of a list and the last one (to x_0: h = inf) are first order, the last one
+// through the fused DDPM epilogue exactly as DDIM's. Every other position is one plain evaluation (mel_eps) and one update launch.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// x0 as ss_ddpm_update forms it, then x' = fma(b1, x0_prev, fma(b0, x0, c2 * x)) (second) or fma(b0, x0, c2 * x)
+__device__ __forceinline__ float dpmpp_update(float x, float eps, float x0_prev, float recip, float recipm1, float b0, float b1, float c2, bool second,
+                                              float& x0_out) {
+#pragma clang fp contract(off)
+  const float a = recip * x, b = recipm1 * eps;
+  const float x0 = fminf(fmaxf(a - b, -1.0f), 1.0f);
+  const float c2x = c2 * x;
+  float xn = __builtin_fmaf(b0, x0, c2x);
+  if (second) xn = __builtin_fmaf(b1, x0_prev, xn);
+  x0_out = x0;
+  return xn;
+}
+
+// One thread per float4 of [B][T][M] (M a multiple of 4: a float4 never straddles a row); the grid covers all n4 of them. x and x0 (the history,
+// read as x0_prev when `second`) are updated in place; rows t >= lens[b] of both are written as 0.
+__global__ __launch_bounds__(256) void dpmpp_update_kernel(float4* __restrict__ x, const float4* __restrict__ eps, float4* __restrict__ x0h,
+                                                           const int32_t* __restrict__ lens, int64_t n4, int T, int M4, float recip, float recipm1,
+                                                           float b0, float b1, float c2, int second) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const int64_t row = i / M4;
+  const int b = (int)(row / T), t = (int)(row % T);
+  if (lens && t >= lens[b]) {
+    x[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    x0h[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const float4 xv = x[i], ev = eps[i];
+  const float4 pv = second ? x0h[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 xn, x0;
+  xn.x = dpmpp_update(xv.x, ev.x, pv.x, recip, recipm1, b0, b1, c2, second != 0, x0.x);
+  xn.y = dpmpp_update(xv.y, ev.y, pv.y, recip, recipm1, b0, b1, c2, second != 0, x0.y);
+  xn.z = dpmpp_update(xv.z, ev.z, pv.z, recip, recipm1, b0, b1, c2, second != 0, x0.z);
+  xn.w = dpmpp_update(xv.w, ev.w, pv.w, recip, recipm1, b0, b1, c2, second != 0, x0.w);
+  x[i] = xn;
+  x0h[i] = x0;
+}
+
+inline double half_logsnr(double ac) { return 0.5 * log(ac / (1.0 - ac)); }
+}  // namespace
+
+extern "C" int ss_meldiff_sample_dpmpp(const ss_wavenet* net, float* x, const float* cond, const int32_t* lens, int B, int T, const int32_t* ts,
+                                       int n_ts, int i_lo, int i_hi, const double* alphas_cumprod, int order, float* hist, int do_precompute,
+                                       void* ws, int64_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SS_CHECK_ARG(net && x && cond && ws && ts && alphas_cumprod && hist, "ss_meldiff_sample_dpmpp: null pointer");
+  SS_CHECK_ARG(n_ts >= 1, "ss_meldiff_sample_dpmpp: n_ts=%d must be positive", n_ts);
+  for (int i = 0; i < n_ts; ++i)
+    SS_CHECK_ARG(ts[i] >= 0 && ts[i] < net->steps && (i == 0 || ts[i] < ts[i - 1]),
+                 "ss_meldiff_sample_dpmpp: ts must be strictly decreasing in [0, steps=%d) (ts[%d]=%d)", net->steps, i, ts[i]);
+  SS_CHECK_ARG(0 <= i_lo && i_lo <= i_hi && i_hi <= n_ts, "ss_meldiff_sample_dpmpp: bad position range [%d, %d) of %d", i_lo, i_hi, n_ts);
+  SS_CHECK_ARG(order == 1 || order == 2, "ss_meldiff_sample_dpmpp: order=%d must be 1 or 2", order);
+  SS_CHECK_ARG(net->in_dim > 0 && net->in_dim % 4 == 0, "ss_meldiff_sample_dpmpp: in_dim=%d must be a multiple of 4 (one float4 per thread)", net->in_dim);
+  SS_CHECK_ARG(((uintptr_t)x | (uintptr_t)hist) % 16 == 0, "ss_meldiff_sample_dpmpp: x and hist must be 16-byte aligned");
+  SamplerCtx s;
+  SS_PROPAGATE(open_sampler("ss_meldiff_sample_dpmpp", net, B, T, cond, lens, ws, ws_bytes, 1, false, do_precompute != 0, stream, s));
+  const int M = net->in_dim;
+  const int64_t n = (int64_t)B * T * M, n4 = n / 4;
+  float* eps = hist;        // the evaluation's output
+  float* x0h = hist + n;    // x0 of the previous position
+  const int64_t blocks = (n4 + 255) / 256;
+  SS_CHECK_ARG(blocks <= 0x7fffffff, "ss_meldiff_sample_dpmpp: B*T*in_dim=%lld is beyond one grid", (long long)n);
+  for (int i = i_lo; i < i_hi; ++i) {
+    const int t = ts[i];
+    const bool last = i + 1 == n_ts;   // the list's last entry, wherever the call is cut
+    const DdimCoef k = ddim_coef(alphas_cumprod[t], last ? 1.0 : alphas_cumprod[ts[i + 1]], 0.0);
+    if (last) {   // to x_0: first order, the fused epilogue (DDIM's last transition, launch for launch)
+      SS_PROPAGATE(mel_step(net, s.sf, x, lens, B, T, s.w, t, i, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], (float)k.c1, (float)k.c2, 0.0f, nullptr, 0, nullptr,
+                            (uint32_t)t, stream));
+      continue;
+    }
+    double b0 = k.c1, b1 = 0.0;
+    const bool second = order == 2 && i > 0;
+    if (second) {
+      const double lam_t = half_logsnr(alphas_cumprod[t]);
+      const double r = (lam_t - half_logsnr(alphas_cumprod[ts[i - 1]])) / (half_logsnr(alphas_cumprod[ts[i + 1]]) - lam_t);
+      b0 = k.c1 * (1.0 + 1.0 / (2.0 * r));
+      b1 = -k.c1 / (2.0 * r);
+    }
+    SS_PROPAGATE(mel_eps(net, s.sf, x, eps, lens, B, T, s.w, t, i, stream));
+    hipLaunchKernelGGL(dpmpp_update_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<float4*>(x), reinterpret_cast<const float4*>(eps),
+                       reinterpret_cast<float4*>(x0h), lens, n4, T, M / 4, net->sqrt_recip_ac[t], net->sqrt_recipm1_ac[t], (float)b0, (float)b1, (float)k.c2,
+                       second ? 1 : 0);
+    SS_CHECK_LAUNCH("dpmpp_update_kernel");
+  }
+  return SS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // PLMS / "pndm_speedup" sampler of the reference (shallow_diffusion_tts.py:165-197 p_sample_plms, loop :254-260):
 //   x_prev = x + (a_prev - a_t) * (kx * x - ke * eps'),  eps' = linear multistep combination of the eps history.
 // The reference runs it for one utterance at a time (its `max(t - interval, 0)` on a tensor only works for B = 1).

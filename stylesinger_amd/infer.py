@@ -462,6 +462,14 @@ def main(argv=None):
     ap.add_argument("--f0-steps", type=int, help="sample the two f0 / uv diffusions at this many of their f0_timesteps network times "
                     "(hparams['f0_sample_steps']; default: every one, the reference's loop)")
     ap.add_argument("--f0-eta", type=float, help="--f0-steps: 0 = deterministic Gaussian half ... 1 = ancestral (hparams['f0_sample_eta'], default 1)")
+    ap.add_argument("--mel-sampler", choices=["ddpm", "ddim", "plms", "dpmpp"], help="how the shallow mel diffusion is sampled (hparams['mel_sampler']): "
+                    "ddpm = the reference's ancestral loop, plms = its PLMS sampler (stride: hparams['pndm_speedup']), ddim / dpmpp = --mel-steps network "
+                    "times, first order / DPM-Solver++ multistep (default: the checkpoint's own choice)")
+    ap.add_argument("--mel-steps", type=int, help="--mel-sampler ddim | dpmpp: at most this many network times (hparams['mel_sample_steps'])")
+    ap.add_argument("--mel-order", type=int, choices=[1, 2], help="--mel-sampler dpmpp: 2 = the 2M multistep update (default), 1 = first order")
+    ap.add_argument("--mel-spacing", choices=["uniform", "logsnr"], help="--mel-steps: the times uniform in t or in the log-SNR "
+                    "(hparams['mel_sample_spacing']; default: uniform for ddim, logsnr for dpmpp)")
+    ap.add_argument("--mel-eta", type=float, help="--mel-sampler ddim: 0 = deterministic (default) ... 1 = ancestral (hparams['mel_sample_eta'])")
     ap.add_argument("--score", help="a score of any length as JSON (the keys of example_input.json, optionally ph_dur = seconds per phone): split at "
                     "its rests, rendered in batches, stitched on the device")
     ap.add_argument("--max-seconds", type=float, default=12.0, help="--score: longest merged segment")
@@ -558,6 +566,26 @@ def main(argv=None):
         if not 0.0 <= a.f0_eta <= 1.0:
             ap.error("--f0-eta: inside [0, 1]")
         hp["f0_sample_eta"] = a.f0_eta
+    for flag, val in (("--mel-steps", a.mel_steps), ("--mel-order", a.mel_order), ("--mel-spacing", a.mel_spacing), ("--mel-eta", a.mel_eta)):
+        if val is not None and a.mel_sampler is None:
+            ap.error(f"{flag} belongs to --mel-sampler")
+    if a.mel_sampler is not None:
+        strided = a.mel_sampler in ("ddim", "dpmpp")
+        if strided and a.mel_steps is None:
+            ap.error(f"--mel-sampler {a.mel_sampler} needs --mel-steps")
+        if a.mel_steps is not None and (not strided or a.mel_steps < 1):
+            ap.error("--mel-steps: at least 1, with --mel-sampler ddim or dpmpp")
+        if a.mel_spacing is not None and not strided:
+            ap.error("--mel-spacing belongs to --mel-sampler ddim or dpmpp")
+        if a.mel_order is not None and a.mel_sampler != "dpmpp":
+            ap.error("--mel-order belongs to --mel-sampler dpmpp")
+        if a.mel_eta is not None and (a.mel_sampler != "ddim" or not 0.0 <= a.mel_eta <= 1.0):
+            ap.error("--mel-eta: inside [0, 1], with --mel-sampler ddim")
+        hp["mel_sampler"] = a.mel_sampler
+        for key, val in (("mel_sample_steps", a.mel_steps), ("mel_sample_order", a.mel_order), ("mel_sample_spacing", a.mel_spacing),
+                         ("mel_sample_eta", a.mel_eta)):
+            if val is not None:
+                hp[key] = val
     ctor = dict(exp_dir=a.exp_dir, vocoder_dir=a.vocoder_dir, emotion_state=emo.get("model_state", emo),
                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
     if score is not None:

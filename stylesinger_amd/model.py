@@ -18,7 +18,7 @@ from . import lib as L
 from . import spec as _spec
 from .config import make_hparams
 from .packing import Packing, _sin_table
-from .plans import Plans
+from .plans import MEL_SAMPLERS, MEL_SPACING_DEFAULT, MEL_SPACINGS, Plans, logsnr_timesteps
 
 
 def _pad_frames(x, T, dim=-1):
@@ -252,9 +252,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
 
     @torch.no_grad()
     def mel_stage(self, coarse_mel, cond, lens=None, z_q=None, z_steps=None, sampler="ddpm", ddim_steps=None, plms_interval=None, seed=1234,
-                  eta=0.0):
+                  eta=0.0, mel_steps=None, mel_order=None, mel_spacing=None):
         """The shallow mel diffusion alone (a11 output -> a12): coarse mel [B,T,80] + condition [B,T,256] -> mel [B,T,80].
-        z_q [B,1,80,T] / z_steps [K,B,1,80,T]: optional recorded noise (reference layout); default device Philox."""
+        z_q [B,1,80,T] / z_steps [K,B,1,80,T]: optional recorded noise (reference layout); default device Philox.
+        `sampler` and its arguments as in forward ("dpmpp": mel_steps, mel_order, mel_spacing; runs eagerly); the hparams defaults are not read."""
+        sm = self._mel_sampler_args(dict(sampler=sampler, ddim_steps=ddim_steps, plms_interval=plms_interval, eta=eta, mel_steps=mel_steps,
+                                         mel_order=mel_order, mel_spacing=mel_spacing), use_hparams=False)
         self._ensure_packed()
         pk, hp = self._pk, self.hp
         dev = coarse_mel.device
@@ -267,8 +270,9 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         pl.coarse_mel.copy_(coarse_mel)
         zq_n = None if z_q is None else _noise_btm(z_q, dev, (B, M, T), T)
         zs_n = None if z_steps is None else _noise_btm(z_steps, dev, (K, B, M, T), T)
-        self._run_mel(pl, (zq_n, zs_n), ddim_ts=self.ddim_timesteps(ddim_steps) if sampler == "ddim" else None,
-                      plms_interval=plms_interval if sampler == "plms" else None, eta=eta)
+        ts = self.mel_timesteps(sm.steps, sm.spacing) if sm.steps is not None else None
+        self._run_mel(pl, (zq_n, zs_n), ddim_ts=ts if sm.name == "ddim" else None, plms_interval=sm.interval, eta=sm.eta,
+                      dpmpp=(ts, sm.order) if sm.name == "dpmpp" else None)
         mel_out = torch.empty(B, T, M, device=dev, dtype=torch.float32)
         L.ops.ss_mel_denorm(pl.xm, pk["spec_min"], pk["spec_max"], mel_out, B, T, M, pl.lens, None)
         return mel_out
@@ -357,6 +361,15 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         parity tests; default = on-device Philox), `seed` (Philox seed), `sampler="ddim", ddim_steps=n, eta=0.0` (strided
         DDIM mel sampler, BASELINE config 5; eta = 0 deterministic, eta = 1 with ddim_steps = K_step IS the reference's ancestral
         sampler; default = the reference's 100-step ancestral sampler),
+        `sampler="dpmpp", mel_steps=n, mel_order=2, mel_spacing="logsnr"|"uniform"` (DPM-Solver++ multistep, data prediction, over at most n
+        network times - `ss_meldiff_sample_dpmpp`: order 2 = "2M" with a first-order first and last transition, order 1 = DDIM with eta = 0 bit
+        for bit; deterministic after q_sample; "logsnr" spaces the times uniformly in the half log-SNR (`plans.logsnr_timesteps`: the list may be
+        shorter than n) and is this sampler's default, `sampler="ddim"` honours `mel_spacing` too and defaults to "uniform"; `mel_steps` is
+        also read by "ddim" where `ddim_steps` is absent). Without `sampler` the hparams decide: `mel_sampler` / `mel_sample_steps` /
+        `mel_sample_order` / `mel_sample_spacing` / `mel_sample_eta`, then `pndm_speedup`, then the reference's loop; `mel_sampler` other than
+        "plms" together with `pndm_speedup` is a ValueError, as are an unknown sampler or spacing, mel_steps < 1 and an order outside {1, 2}.
+        `ret["mel_sampler"]` = dict(name, ts, order) names the list whenever a strided sampler ran. What a checkpoint renders at a given n is
+        unassessed,
         `f0_steps=n, f0_eta=1.0` (strided sampler of the two f0 / uv diffusions: n of the f0_timesteps network times, `ss_f0diff_sample_strided`;
         f0_eta = 0 deterministic Gaussian half ... 1 ancestral, n = f0_timesteps with f0_eta = 1 IS the reference's loop to fp32 rounding of the
         coefficients; defaults hparams['f0_sample_steps'] = None - the reference's full loop, unchanged - and hparams['f0_sample_eta'];
@@ -433,6 +446,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         if pitch_timing is not None and kwargs.get("f0_steps") is not None:
             raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with pitch_timing (a pitch_hz contour) they do not run")
         f0_ts, f0_eta = self._f0_sampler_args(kwargs, f0 is not None or pitch_hz is not None)
+        mel_sampler = self._mel_sampler_args(kwargs)
         pooled = ref_mels is not None and ref_mels.dim() == 4
         if pooled and (ref_f0 is None or ref_f0.dim() != 3):
             raise ValueError(f"forward: ref_mels {tuple(ref_mels.shape)} is a pool of references per item; ref_f0 must then be [B, R, Tr]")
@@ -447,7 +461,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, noise=kwargs.get("noise"), seed=int(kwargs.get("seed", self.hp["seed"])),
                                   kwargs=kwargs)
         c.f32 = dict(device=c.dev, dtype=torch.float32)
-        c.f0_ts, c.f0_eta = f0_ts, f0_eta
+        c.f0_ts, c.f0_eta, c.mel_sampler = f0_ts, f0_eta, mel_sampler
         self._encode_text(c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed)
         self._regulate_length(c, mel2ph, f0, uv)
         self._align_style(c, ref_mels, ref_f0)
@@ -483,6 +497,65 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         if not 0.0 <= eta <= 1.0:
             raise ValueError(f"forward: f0_eta={eta}: 0 (deterministic Gaussian half) ... 1 (ancestral)")
         return (None if steps is None else self.f0_strided_timesteps(int(steps))), eta
+
+    def _mel_sampler_args(self, kwargs, use_hparams=True):
+        """How the mel loop is sampled: forward(sampler=, mel_steps= / ddim_steps=, mel_order=, mel_spacing=, eta=, plms_interval=), else
+        hparams['mel_sampler'] / ['mel_sample_steps'] / ['mel_sample_order'] / ['mel_sample_spacing'] / ['mel_sample_eta'], else the reference's
+        own choice: PLMS under hparams['pndm_speedup'], otherwise its ancestral loop ("ddpm"). Returns a namespace (name, steps, order, spacing,
+        eta, interval); `mel_timesteps` turns steps and spacing into network times once the schedule is packed. Raises ValueError on a bad value;
+        touches no device. `use_hparams=False` (mel_stage, whose `sampler` argument always has a value) reads the arguments alone."""
+        hp = self.hp if use_hparams else {}
+        pndm = hp.get("pndm_speedup")
+        name = kwargs.get("sampler")
+        if name is None:
+            name = hp.get("mel_sampler")
+            if name is not None and name != "plms" and pndm:
+                raise ValueError(f"hparams: mel_sampler={name!r} together with pndm_speedup={pndm} (the reference's PLMS sampler): set one of them")
+        if name is None:
+            name = "plms" if pndm else "ddpm"
+        if name not in MEL_SAMPLERS:
+            raise ValueError(f"mel sampler {name!r}: one of {', '.join(MEL_SAMPLERS)}")
+        spacing = kwargs.get("mel_spacing")
+        if spacing is None:
+            spacing = hp.get("mel_sample_spacing")
+        if spacing is not None and spacing not in MEL_SPACINGS:
+            raise ValueError(f"mel_spacing={spacing!r}: one of {', '.join(MEL_SPACINGS)} (None = the sampler's own default)")
+        order = kwargs.get("mel_order")
+        if order is None:
+            order = hp.get("mel_sample_order", 2)
+        if order not in (1, 2):
+            raise ValueError(f"mel_order={order!r}: 1 (first order: DDIM with eta = 0) or 2 (DPM-Solver++ 2M)")
+        eta = kwargs.get("eta")
+        eta = float(hp.get("mel_sample_eta", 0.0) if eta is None else eta)
+        steps = interval = None
+        if name in MEL_SPACING_DEFAULT:   # the strided samplers
+            steps = kwargs.get("mel_steps")
+            if steps is None and name == "ddim":
+                steps = kwargs.get("ddim_steps")
+            if steps is None:
+                steps = hp.get("mel_sample_steps")
+            if steps is None:
+                raise ValueError(f"mel sampler {name!r} needs a number of network times: mel_steps" + (" / ddim_steps" if name == "ddim" else "")
+                                 + " or hparams['mel_sample_steps']")
+            if int(steps) < 1:
+                raise ValueError(f"mel_steps={steps}: at least 1 (more than K_step = {self.hp['K_step']} means all of them)")
+            steps, spacing = int(steps), spacing or MEL_SPACING_DEFAULT[name]
+        elif name == "plms":
+            interval = kwargs.get("plms_interval")
+            if interval is None:
+                interval = pndm
+            if not interval:
+                raise ValueError("mel sampler 'plms' needs its stride: plms_interval or hparams['pndm_speedup']")
+            interval = int(interval)
+        return types.SimpleNamespace(name=name, steps=steps, order=int(order), spacing=spacing, eta=eta, interval=interval)
+
+    def mel_timesteps(self, n, spacing="uniform"):
+        """n network times of the shallow mel loop, K_step-1 ... 0: "uniform" in t (`ddim_timesteps`) or "logsnr" (`plans.logsnr_timesteps` over
+        the checkpoint's float64 schedule; the list may come out shorter than n). Needs the packed schedule for "logsnr"."""
+        if spacing == "uniform":
+            return self.ddim_timesteps(n)
+        self._ensure_packed()
+        return logsnr_timesteps(self._pk["mel"]["sched"]["alphas_cumprod_f64"], self.hp["K_step"], n)
 
     def _encode_text(self, c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed):
         """Phoneme encoder (a1) + note encoder (a2) + speaker / emotion projections -> c.enc [B,Tp,H], c.spk, c.emo [B,H]."""
@@ -760,17 +833,23 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         self._gemm(gcat, pk["ln_proj"], pl.cond_mel, B, T, mask_rows=False)
         ret["diff_cond"] = pl.cond_mel.clone()
         pl.coarse_mel.copy_(c.coarse_mel)
-        ddim_ts = self.ddim_timesteps(int(kwargs["ddim_steps"])) if kwargs.get("sampler") == "ddim" else None
-        plms = kwargs.get("plms_interval", hp.get("pndm_speedup")) if kwargs.get("sampler", "plms" if hp.get("pndm_speedup") else None) == "plms" else None
-        eta = float(kwargs.get("eta", 0.0))
+        sm = c.mel_sampler   # resolved and checked by forward before anything ran (_mel_sampler_args)
+        eta = sm.eta
+        ts = self.mel_timesteps(sm.steps, sm.spacing) if sm.steps is not None else None
+        if ts is not None:
+            ret["mel_sampler"] = dict(name=sm.name, ts=list(ts), order=sm.order if sm.name == "dpmpp" else 1)
 
         def tape(nz, steps):  # recorded mel noise -> (z_q, z_steps or None) on the device
             return (_noise_btm(nz["z_q"], dev, (B, M, c.T_out), T), _noise_btm(nz["z_steps"], dev, (K, B, M, c.T_out), T) if steps else None)
-        if plms:   # never captured
-            self._run_mel(pl, (None, None) if noise is None else tape(noise["mel"], False), plms_interval=int(plms))
-        elif ddim_ts is not None:   # one captured graph per (B, T bucket, number of sampler steps, eta)
-            run = lambda n=None: self._run_mel(pl, n and tape(n["mel"], eta > 0.0 and "z_steps" in n["mel"]), ddim_ts=ddim_ts, eta=eta)
-            self._run_loop(pl, ("ddim", len(ddim_ts), eta), run, tape=noise, graphs=c.graphs)
+        if sm.name == "plms":   # never captured
+            self._run_mel(pl, (None, None) if noise is None else tape(noise["mel"], False), plms_interval=sm.interval)
+        elif sm.name == "ddim":   # one captured graph per (B, T bucket, number of sampler steps, eta); off the uniform stride, per list of times
+            run = lambda n=None: self._run_mel(pl, n and tape(n["mel"], eta > 0.0 and "z_steps" in n["mel"]), ddim_ts=ts, eta=eta)
+            self._run_loop(pl, ("ddim", len(ts) if sm.spacing == "uniform" else tuple(ts), eta), run, tape=noise, graphs=c.graphs)
+        elif sm.name == "dpmpp":   # one captured graph per (B, T bucket, list of times, order); draws nothing after q_sample: only z_q is read
+            self._dpmpp_buffers(pl)   # plan-owned and allocated out here: the captured graph replays into them
+            run = lambda n=None: self._run_mel(pl, n and tape(n["mel"], False), dpmpp=(ts, sm.order))
+            self._run_loop(pl, ("dpmpp", tuple(ts), sm.order), run, tape=noise, graphs=c.graphs)
         else:
             with self._q4_guard(pl, eager=not c.graphs):
                 self._run_loop(pl, "mel", lambda n=None: self._run_mel(pl, n and tape(n["mel"], True)), tape=noise, graphs=c.graphs)

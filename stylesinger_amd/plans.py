@@ -51,8 +51,11 @@ class _DiffPlan:
             wsb = lib.ss_wavenet_workspace_bytes(ctypes.byref(pk["mel"]["net"]), nb, T)
             self.ws_mel.append((wsb, torch.empty(wsb, device=dev, dtype=torch.uint8)))
         self.ws_prodiff = None   # full-batch workspace of the ProDiff decoder when ws_mel is split (allocated on first use, plan-owned)
-        self.graphs = {}         # captured loops: "f0" (the f0 pair), ("f0", n_steps, eta) (its strided sampler), "mel" (DDPM or ProDiff), ("ddim", n_steps, eta)
+        # captured loops: "f0" (the f0 pair), ("f0", n_steps, eta) (its strided sampler), "mel" (DDPM or ProDiff), ("ddim", n_steps or times, eta),
+        # ("dpmpp", times, order)
+        self.graphs = {}
         self.plms_hist = None
+        self.dpmpp_hist = None   # eps scratch + x0 history of the DPM-Solver++ sampler (allocated on first use, plan-owned: its graphs replay into it)
         self.uses = 0   # forwards that asked for this shape (auto mode captures on the second one)
         self.recount()
 
@@ -103,6 +106,25 @@ def strided_timesteps(S, n):
     """n network times of a schedule of S, strictly decreasing from S-1 to 0 at a uniform stride; n is clipped to [1, S] (n = S: all of them,
     n = 1: time 0 alone - linspace's first point)."""
     return sorted({int(round(v)) for v in np.linspace(0, S - 1, max(1, min(int(n), S)))}, reverse=True)
+
+
+def logsnr_timesteps(ac64, K, n):
+    """Network times of the first K of a schedule (ac64 = cumprod(1 - betas) in float64), spaced uniformly in the half log-SNR
+    lambda_t = 1/2 log(ac_t / (1 - ac_t)) rather than in t: a grid of min(max(n, 2), K) points from lambda_{K-1} to lambda_0, each snapped to the
+    nearest network time (numpy's first minimum on ties), together with both ends K-1 and 0, strictly decreasing. Several grid points may snap to
+    one time - the list is then shorter than n. n = 1 is time K-1 alone (one evaluation there and the jump to x_0)."""
+    K, n = int(K), int(n)
+    if n <= 1 or K <= 1:
+        return [K - 1]
+    ac = np.asarray(ac64, np.float64)[:K]
+    lam = 0.5 * np.log(ac / (1.0 - ac))
+    grid = np.linspace(lam[K - 1], lam[0], min(max(n, 2), K))
+    return sorted({int(np.argmin(np.abs(lam - g))) for g in grid} | {K - 1, 0}, reverse=True)
+
+
+MEL_SAMPLERS = ("ddpm", "ddim", "plms", "dpmpp")
+MEL_SPACINGS = ("uniform", "logsnr")
+MEL_SPACING_DEFAULT = {"ddim": "uniform", "dpmpp": "logsnr"}   # each strided sampler's own default
 
 
 class Plans:
@@ -247,9 +269,18 @@ class Plans:
         S = self.hp["f0_timesteps"]
         return [S - 1] if int(n) <= 1 else strided_timesteps(S, n)
 
-    def _run_mel(self, pl, tape=None, ddim_ts=None, plms_interval=None, eta=0.0):
+    def _dpmpp_buffers(self, pl):
+        """(hist, (bytes, workspace)) of the DPM-Solver++ sampler on this plan, both plan-owned: a captured graph replays into them, so they are
+        allocated before `_run_loop` captures, never inside the loop function."""
+        if pl.dpmpp_hist is None:
+            pl.dpmpp_hist = torch.empty(2 * pl.B * pl.T * self.hp["audio_num_mel_bins"], device=pl.xm.device, dtype=torch.float32)
+            pl.recount()
+        return pl.dpmpp_hist, self._full_batch_ws(pl, keep=True)
+
+    def _run_mel(self, pl, tape=None, ddim_ts=None, plms_interval=None, eta=0.0, dpmpp=None):
         """q_sample + the shallow reverse loop (batch halves on two streams); `ddim_ts` switches to the strided
-        DDIM sampler (BASELINE config 5; `eta` = 0 deterministic ... 1 ancestral), `plms_interval` to the reference's PLMS sampler (pndm_speedup)."""
+        DDIM sampler (BASELINE config 5; `eta` = 0 deterministic ... 1 ancestral), `plms_interval` to the reference's PLMS sampler (pndm_speedup),
+        `dpmpp` = (network times, order) to DPM-Solver++ multistep (`ss_meldiff_sample_dpmpp`; deterministic: of the tape only z_q is read)."""
         pk, hp = self._pk, self.hp
         B, T, M = pl.B, pl.T, hp["audio_num_mel_bins"]
         net = pk["mel"]["net"]
@@ -259,6 +290,12 @@ class Plans:
         sdp = pl.seed
         zq_n, zs_n = tape if tape is not None else (None, None)
         L.ops.ss_mel_qsample(pl.coarse_mel, pk["spec_min"], pk["spec_max"], sa, s1, zq_n, 23, sdp, pl.xm, B, T, M)
+        if dpmpp is not None:
+            ts = np.ascontiguousarray(np.asarray(dpmpp[0], dtype=np.int32))
+            hist, (wsb, wsp) = self._dpmpp_buffers(pl)
+            L.ops.ss_meldiff_sample_dpmpp(net, pl.xm, pl.cond_mel, pl.lens, B, T, ts, len(ts), 0, len(ts), pk["mel"]["sched"]["alphas_cumprod_f64"],
+                                          int(dpmpp[1]), hist, 1, wsp, wsb)
+            return
         if ddim_ts is not None or plms_interval is not None:
             ac = pk["mel"]["sched"]["alphas_cumprod_np"]  # host table, read by the loop driver at launch time
             wsb, wsp = self._full_batch_ws(pl)

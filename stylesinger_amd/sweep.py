@@ -66,13 +66,16 @@ class StyleCache:
 
 @torch.no_grad()
 def style_transfer_sweep(infer, refs, targets, rank=0, world=1, batch=32, ddim_steps=50, t_bucket=1, vocode=True, emit=None, seed=None,
-                         stats=None, f0_steps=None):
+                         stats=None, mel_sampler="ddim", mel_spacing=None, f0_steps=None):
     """refs[i] = dict(ref_mels [Tr,80], ref_f0 [Tr], spk_embed [256], emo_embed [256]);
     targets[j] = dict(txt_tokens [Tp], note [Tp], note_dur [Tp], note_type [Tp], mel2ph [T]).
     Calls emit(ref_idx, target_idx, mel [T,80], f0 [T], wav [T*hop] or None) per pair; returns the number of pairs done and
     the number of mel frames produced by this rank. `stats` (a dict, optional) receives the per-reference style-cache accounting of this
     call: references on this rank, style-encoder runs, cache hits, hit rate. `f0_steps`: sample the f0 / uv diffusions at this many network
-    times (forward(f0_steps=); None = the model's hparams default, the reference's full loop)."""
+    times (forward(f0_steps=); None = the model's hparams default, the reference's full loop). `mel_sampler`: "ddim" (eta = 0, the default)
+    or "dpmpp" (DPM-Solver++ 2M) over `ddim_steps` network times, `mel_spacing`: "uniform" / "logsnr" (None = the sampler's own default)."""
+    if mel_sampler not in ("ddim", "dpmpp"):
+        raise ValueError(f"style_transfer_sweep: mel_sampler={mel_sampler!r}: 'ddim' or 'dpmpp' (the strided samplers: ddim_steps network times)")
     model, dev = infer.model, infer.device
     cache = StyleCache(model)
     n_pairs = n_frames = 0
@@ -91,7 +94,8 @@ def style_transfer_sweep(infer, refs, targets, rank=0, world=1, batch=32, ddim_s
                     emo_embed=torch.stack([refs[i]["emo_embed"] for i in ref_idxs]).to(dev),
                     ref_mels=None, ref_f0=None, global_steps=infer.hparams.get("diff_start", 0) + 1, infer=True,
                     note=rep(tgt["note"]), note_dur=rep(tgt["note_dur"]), note_type=rep(tgt["note_type"]),
-                    style_cache=sc, sampler="ddim", ddim_steps=ddim_steps, **({} if seed is None else {"seed": seed}),
+                    style_cache=sc, sampler=mel_sampler, **({"ddim_steps": ddim_steps} if mel_sampler == "ddim" else {"mel_steps": ddim_steps}),
+                    **({} if mel_spacing is None else {"mel_spacing": mel_spacing}), **({} if seed is None else {"seed": seed}),
                     **({} if f0_steps is None else {"f0_steps": f0_steps}))
         mel, f0, lens = out["mel_out"], out["f0_denorm"], out["lens"]
         wav = infer.vocode(mel, f0, lens) if vocode else None
