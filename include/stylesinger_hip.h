@@ -360,22 +360,25 @@ int ss_gemm_bf16_gate256_ok(const ss_gemm_bf16_args* args);
 int ss_gemm_bf16_gate128(const ss_gemm_bf16_args* args, void* stream);
 int ss_gemm_bf16_gate128_ok(const ss_gemm_bf16_args* args);
 /* ss_gemm_bf16_gate128 for split = 3 ("fp16q4") operands: per pair of 32-channel steps 32 fp16 MFMAs (a * hi) + 8 block-scaled fp4 ones
- * (a_q * lo_q, v_mfma_scale_f32_32x32x64_f8f6f4) instead of 64. NOT YET RUN ON HARDWARE; nothing dispatches to it.
+ * (a_q * lo_q, v_mfma_scale_f32_32x32x64_f8f6f4) instead of 64; q_scale = the activations' fp4 scale, a power of two. The denoiser stack dispatches
+ * here for fp16q4 launches that pass ss_gemm_bf16_gate128q_ok (the rules of ss_gemm_bf16_gate128_ok, or any size with the "q4_force" knob).
  * ss_gate128q_kindex(out): the K index (tap * 256 + channel) of element e of lane half h in step pair p, out[(p * 2 + h) * 32 + e], 12 pairs -
  * the order the weights' fp4 lo terms are packed in (returns the number of entries written: 768). */
 int ss_gemm_bf16_gate128q(const ss_gemm_bf16_args* args, void* stream);
 int ss_gemm_bf16_gate128q_ok(const ss_gemm_bf16_args* args);
 int ss_gate128q_kindex(int32_t* out, int n);
 /* The long-K STORE GEMM (the skip GEMM) of ss_gemm_bf16_tile256 for split = 3 ("fp16q4") operands: the same second product on the block-scaled
- * fp4 instruction, pairs = consecutive 32-channel chunks, A scale q_scale (gate outputs: 2^-2). NOT YET RUN ON HARDWARE; nothing dispatches
- * to it. ss_tile256q_kindex(out, n_pairs): K index of element e of lane half h in chunk pair p, out[(p * 2 + h) * 32 + e] (returns the count). */
+ * fp4 instruction, pairs = consecutive 32-channel chunks, A scale q_scale (gate outputs: 2^-2). The denoiser stack dispatches here for fp16q4
+ * launches that pass ss_gemm_bf16_tile256q_ok. ss_tile256q_kindex(out, n_pairs): K index of element e of lane half h in chunk pair p, out[(p * 2 + h) * 32 + e] (returns the count). */
 int ss_gemm_bf16_tile256q(const ss_gemm_bf16_args* args, void* stream);
 int ss_gemm_bf16_tile256q_ok(const ss_gemm_bf16_args* args);
 int ss_tile256q_kindex(int32_t* out, int n_pairs);
 /* The split-operand 1-tap forms of ss_gemm_bf16 for many-round launches (BASELINE config 4 in bf16x2 precision): SS_HEPI_RESX on the pair-only
  * stream (X = NULL) and SS_HEPI_STORE (the K = L*C skip GEMM), N <= 256, K a multiple of 64. 256 rows x all columns per workgroup, 8 waves, both
  * operands by LDS-DMA, epilogues through LDS as 16-byte vectors. ss_gemm_bf16 dispatches here when ss_gemm_bf16_tile256_ok(args) (and the
- * "gate256" knob) say so; same arithmetic contract, results equal up to the K summation order. */
+ * "gate256" knob) say so; same arithmetic contract, results equal up to the K summation order.
+ * For this kernel and the four above (gate256, gate128, gate128q, tile256q): ss_gemm_bf16_*_ok(args) = the kernel's launch contract holds (every shape, stride, alignment and range rule its
+ * launcher enforces) and the launch has enough rounds of tiles; the launcher returns SS_ERR_ARG with the broken rule for anything else. */
 int ss_gemm_bf16_tile256(const ss_gemm_bf16_args* args, void* stream);
 int ss_gemm_bf16_tile256_ok(const ss_gemm_bf16_args* args);
 /* ONE launch per residual layer of the mel denoiser in "fp16x2" precision for many-round launches (BASELINE configs[3]); replaces the

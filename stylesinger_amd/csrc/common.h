@@ -38,6 +38,40 @@ void ss_set_error(const char* fmt, ...);
 
 static inline int ss_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Sub-rules of the launch contracts of the LDS-DMA GEMM kernels (gemm_bf16_gate*.hip, gemm_bf16_tile256*.hip), each written here once.
+// three taps (-d, 0, d) with 1 <= d <= halo
+static inline bool ss_taps_symmetric(int ntaps, const int* tap_off, int halo) {
+  return ntaps == 3 && tap_off[1] == 0 && tap_off[0] == -tap_off[2] && tap_off[2] >= 1 && tap_off[2] <= halo;
+}
+// rows x ld elements of `bytes` bytes are addressed by a signed 32-bit byte offset
+static inline bool ss_fits_i31(int64_t rows, int64_t ld, int bytes) { return rows * ld * bytes < (1ll << 31); }
+static inline bool ss_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the fp16q4 activation scale: a power of two 2^e with -21 <= e <= 19 (frexp exponent in [-20, 20]), so that its exponent field is the E8M0 byte
+static inline bool ss_q_scale_ok(float q) {
+  int ex = 0;
+  return q > 0.f && frexpf(q, &ex) == 0.5f && ex >= -20 && ex <= 20;
+}
+// 0 < out_scale <= 1: the power-of-two shift of the fp16 weight pack, undone after the fp32 accumulation
+static inline bool ss_out_scale_ok(float s) { return s > 0.f && s <= 1.f; }
+// A kernel that needs `lds` bytes of dynamic LDS, above the default limit: ss_allow_lds raises the limit - the attribute is per device and cheap,
+// so it is set on every launch (a process may drive several GPUs); failures are reported, not cached - and ss_launch_lds does that and launches.
+template <class... P>
+static inline int ss_allow_lds(const char* name, void (*kern)(P...), size_t lds) {
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) {
+    ss_set_error("%s: hipFuncSetAttribute(%d bytes of LDS): %s", name, (int)lds, hipGetErrorString(e));
+    return SS_ERR_HIP;
+  }
+  return SS_OK;
+}
+template <class... P, class... A>
+static inline int ss_launch_lds(const char* name, void (*kern)(P...), int grid, int block, size_t lds, void* stream, A... args) {
+  SS_PROPAGATE(ss_allow_lds(name, kern, lds));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, (hipStream_t)stream, args...);
+  SS_CHECK_LAUNCH(name);
+  return SS_OK;
+}
+
 // Run-time tuning knobs (ss_set_tuning): process-wide, read at launch time, never change results.
 //   gate16: tiling of the Winograd F(4,3) gate launch. 1 (default) = pick per launch (ss_wino43_gate16_pick: 16x16x4 tiles of
 //     16*MT quads when that fills the chip better, else the 32x32x2 kernel); 0 = always the 32x32x2 kernel; 2 / 3 = force MT.

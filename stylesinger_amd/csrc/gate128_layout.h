@@ -6,6 +6,7 @@
 #pragma once
 
 #if defined(__HIPCC__)
+#include "gemm_lds_dma.h"   // hip_runtime.h's qualifiers, and what the two kernels and their text fragments use
 #define G128_HD __host__ __device__ __forceinline__
 #else
 #define G128_HD inline
@@ -106,3 +107,20 @@ G128_HD int q_reg_ks(int r) { return r & 1; }
 // tile256q_store_kernel (gemm_bf16_tile256q.hip): the same pairing for a 1-tap GEMM - pair p = chunks (2 p, 2 p + 1); element e of lane half h:
 // chunk 2 p + (e >> 4), k-step (e >> 3) & 1, channel 16 ks + 8 h + (e & 7) of it. The fp4 terms sit in the weight line of chunk 2 p + 1.
 G128_HD int t128q_kindex(int p, int h, int e) { return 32 * (2 * p + (e >> 4)) + 16 * ((e >> 3) & 1) + 8 * h + (e & 7); }
+
+#if defined(__HIPCC__)
+// The launch rules gate128_kernel and gate128q_kernel share (everything but the operand form, which each file's contract adds): nullptr, or the
+// first rule broken, without the kernel's name.
+inline const char* g128_shared_contract(const ss_gemm_bf16_args& a) {
+  using namespace g128;
+  if (!(a.A && a.W && a.C)) return "null A/W/C";
+  if (!(a.epi == SS_HEPI_GATE && ss_taps_symmetric(a.ntaps, a.tap_off, HALO))) return "GATE with taps (-d, 0, d), 1 <= d <= 8 only";
+  if (!(a.K == 256 && (a.Np % BN) == 0 && 2 * a.N <= a.Np && (a.lda % 8) == 0 && (a.N % 32) == 0 && (a.ldc % 8) == 0 && (a.lde % 4) == 0 && a.lda >= 2 * a.K &&
+        a.ldc >= 2 * a.N))
+    return "K = 256, Np % 128, 2 N <= Np, N % 32, lda % 8 and >= 2 K, ldc % 8 and >= 2 N, lde % 4";
+  if (!(ss_aligned16(a.A) && ss_aligned16(a.W) && (a.a_batch_stride & 7) == 0 && (!a.E || (ss_aligned16(a.E) && (a.e_batch_stride & 3) == 0))))
+    return "A / W / E must be 16-byte aligned";
+  if (!(ss_fits_i31(a.T, a.lda, 2) && ss_fits_i31(a.T, a.lde, 4) && ss_fits_i31(a.T, a.ldc, 2) && ss_fits_i31(a.Np, 3 * a.K, 4))) return "item too large for 32-bit offsets";
+  return nullptr;
+}
+#endif

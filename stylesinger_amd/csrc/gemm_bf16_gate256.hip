@@ -10,12 +10,10 @@
 //   * global -> LDS by LDS-DMA (buffer_load ... lds, 16 B per lane): no staging registers, no ds_write, no VALU in the loop; the XOR slot
 //     swizzle is applied to the per-lane SOURCE address because the DMA image is lane-linear. The weight tile of step s+1 and the A
 //     chunk of the next channel chunk are in flight under the MFMAs of step s; one raw s_barrier + counted s_waitcnt per step.
+// What it shares with the other many-round 16-bit kernels (gate128 / gate128q, tile256 / tile256q) is in gemm_lds_dma.h.
 // Arithmetic contract unchanged: bf16 operands (rounded once where they are produced), exact products, fp32 accumulation, fp32 addend,
 // hardware exp/rcp activations, bf16 gate output - the same values as gemm_bf16_kernel<GATE> up to the K summation order.
-#include "common.h"
-#include "device_prims.h"
-#include "../../include/stylesinger_hip.h"
-#include "pair16.h"
+#include "gemm_lds_dma.h"
 #include <type_traits>
 #include <utility>
 
@@ -85,37 +83,34 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
   // SPLIT = 2: the A operand's second plane (logical slots 4-7) is never read by the matrix cores - its lanes fetch nothing (out of range: the
   // DMA writes zeros), which halves the A traffic from L2 / HBM
   const int a_lo_dead = (W2 && slot0 >= 4) ? (int)0x80000000 : 0;
-  auto dma_a = [&](char* buf, int cc, int dead) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-      // the row offset of piece j goes into the VGPR offset (one add), NOT the SGPR offset: for the rows before the item (t0 - 8 + r < 0)
-      // the per-lane offset is negative, i.e. >= 2^31 as unsigned, and the hardware adds the SGPR offset without wrapping - a positive
-      // SGPR part would leave valid rows of later pieces out of range
-      glds16(rsrc_a, buf + (wave + 8 * j) * 8 * ROWB, (a_voff + 64 * j * a.lda * 2) | dead | (j == 4 ? a_tail_dead : 0) | a_lo_dead, cc * (BKH * 2));
-  };
   auto piece_a = [&](char* buf, int cc, int j) {
+    // the row offset of piece j goes into the VGPR offset (one add), NOT the SGPR offset: for the rows before the item (t0 - 8 + r < 0)
+    // the per-lane offset is negative, i.e. >= 2^31 as unsigned, and the hardware adds the SGPR offset without wrapping - a positive
+    // SGPR part would leave valid rows of later pieces out of range
     glds16(rsrc_a, buf + (wave + 8 * j) * 8 * ROWB, (a_voff + 64 * j * a.lda * 2) | (j == 4 ? a_tail_dead : 0) | a_lo_dead, cc * (BKH * 2));
   };
-  auto piece_b = [&](char* buf, int cc, int tap, int j) {
-    glds16(rsrc_w, buf + (wave + 8 * j) * 8 * ROWB, b_voff, (tap * CCS + cc) * (BKH * 2) + 64 * j * ldw * 2);
+  auto piece_b = [&](char* buf, int S, int j) {   // the weight tile of step S = 3 cc + tap: line tap * CCS + cc of the tap-major packed rows
+    glds16(rsrc_w, buf + (wave + 8 * j) * 8 * ROWB, b_voff, ((S % 3) * CCS + S / 3) * (BKH * 2) + 64 * j * ldw * 2);
   };
-  auto dma_b = [&](char* buf, int cc, int tap, int dead) {
+  auto dma_a = [&](char* buf, int cc) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) glds16(rsrc_w, buf + (wave + 8 * j) * 8 * ROWB, b_voff | dead, (tap * CCS + cc) * (BKH * 2) + 64 * j * ldw * 2);
+    for (int j = 0; j < 5; ++j) piece_a(buf, cc, j);
+  };
+  auto dma_b = [&](char* buf, int S) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) glds16(rsrc_w, buf + (wave + 8 * j) * 8 * ROWB, b_voff, ((S % 3) * CCS + S / 3) * (BKH * 2) + 64 * j * ldw * 2);
   };
 
   // ---- fragment addresses. A, tap j: row = HALO + (j - 1) d + 128 wm + 32 m + l31; k-step ks reads slot (2 ks + lh) ^ swz(row).
   // 32 m more rows leave the swizzle unchanged ((16 m) & 7 == 0): m is an immediate offset. Kept as (row base, swizzle) per tap and
   // combined with one XOR per read: the 128 accumulator registers leave no room for a table of all 16 addresses.
-  int a_base[3], a_swz[3];
+  frags<4, ROWB> a_frags[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const int row = HALO + (j - 1) * d + 128 * wm + l31;
-    a_base[j] = row * ROWB;
-    a_swz[j] = ((row >> 1) & 7) ^ lh;
+    a_frags[j] = {row * ROWB, ((row >> 1) & 7) ^ lh};
   }
-  const int b_base = (64 * wn + l31) * ROWB;
-  const int b_swz = (((64 * wn + l31) >> 1) & 7) ^ lh;
+  const frags<2, ROWB> b_frags{(64 * wn + l31) * ROWB, (((64 * wn + l31) >> 1) & 7) ^ lh};
 
   // conditioner addend: fp32 [rows][lde], the tile's 256 packed columns are 1 KB contiguous per row -> one row per DMA instruction.
   // Quarter q = tile rows 128 h + 32 q + (0..31), h = 0, 1 -> 64 pieces; wave w issues pieces w, w + 8, ..., w + 56.
@@ -128,233 +123,123 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
   };
   auto dma_e = [&](char* buf, int q) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      glds16(rsrc_e, buf + (wave + 8 * j) * 1024, e_voff, (q * 32 + (j < 4 ? 8 * j : 128 + 8 * (j - 4))) * a.lde * 4);
+    for (int j = 0; j < 8; ++j) piece_e(buf, q, j);
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+  clear_acc(acc);
 
-  // step S = 3 cc + tap, fully unrolled (CCS is a template parameter): MFMAs of (A chunk cc at the tap's row offset, weight tile
-  // (cc, tap)). At its top: my pieces of this step's operands have landed - counted vmcnt: the A chunk of cc+1 is issued in the tap-1
-  // step AFTER that step's weight pieces, so at the top of the tap-2 step its 5 pieces may still fly; barrier (everyone's pieces landed,
-  // everyone finished reading step S-1); then the weight pieces of step S+1 (and, at tap 1, the A chunk cc+1) are issued and fly under
-  // this step's MFMAs. Weight tiles alternate B0 / B1 every step, A chunks A0 / A1 every channel chunk.
+  // step S = 3 cc + tap, fully unrolled (CCS is a template parameter): MFMAs of (A chunk cc at the tap's row offset, weight tile (cc, tap)).
+  // Its head - counted vmcnt, barrier, current / next buffers - and the DMA pieces it issues (the weight tile of step S+1, at tap 1 the A chunk
+  // cc+1, in the last step the first addend quarter) are gate_step's (gemm_lds_dma.h); they fly under this step's MFMAs.
   // ---- SPLIT: 2 k-steps x 3 product groups of 8 MFMAs per step: G0 = mid x hi, G1 = hi x mid, G2 = hi x hi (G2 reuses G1's A and G0's B
   // fragments). Software pipeline ACROSS the step barrier: the last two groups of a step (G1, G2 of its second k-step: 16 MFMAs whose
   // fragments already sit in registers) are issued AFTER the next step's barrier, with that step's DMA pieces placed between them and its
   // first fragment reads in flight - so the matrix pipe has work while every wave of the workgroup is issuing DMA / waiting on LDS
-  // (before: ~2 k of a step's 5.2 k cycles with the pipe idle, 410 us per C4 launch).
+  // (before: ~2 k of a step's 5.2 k cycles with the pipe idle, 410 us per C4 launch). Fragment reads: slot 2 ks = hi, 4 + 2 ks = mid / lo of k-step ks.
   [[maybe_unused]] bf16x8 p_ah[4], p_bh[2], p_bm[2];
-  auto mfma8 = [&](const bf16x8 (&fa)[4], const bf16x8 (&fb)[2]) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m], fb[n], acc[m][n], 0, 0, 0);
+  constexpr bool F16 = W2;   // fp16 terms in the fp16x2 form, bf16 terms otherwise
+  // what both split forms do after their first fragment reads: the 16 MFMAs step S-1 deferred, this step's DMA pieces between them
+  auto deferred = [&](const auto& st) {
+    st.template deferred<F16>(acc, p_ah, p_bm, p_bh, [&](int i) { st.piece(i, piece_b, piece_a, [&](int j) { piece_e(EQ0, 0, j); }); });
   };
   auto step_split = [&](auto stag) {
-    constexpr int S = decltype(stag)::value;
-    constexpr int CC = S / 3, TAP = S % 3;
-    constexpr bool LAST = S + 1 >= 3 * CCS;
-    const char* Ac = (CC & 1) ? A1 : A0;
-    const char* Bc = (S & 1) ? B1 : B0;
-    char* Bn = (S & 1) ? B0 : B1;
-    char* An = (CC & 1) ? A0 : A1;
-    if constexpr (TAP == 2 && CC + 1 < CCS) wait_vmcnt<5>();   // the 5 pieces of A chunk cc+1, issued last step after its weight pieces
-    else wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    auto rd_a = [&](int slot, bf16x8 (&f)[4]) {   // a_swz / b_swz carry lh: slot (2 ks) ^ swz = hi, (4 + 2 ks) ^ swz = mid of k-step ks
-      const int ao = a_base[TAP] + ((slot ^ a_swz[TAP]) << 4);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) f[m] = *reinterpret_cast<const bf16x8*>(Ac + ao + m * 32 * ROWB);
-    };
-    auto rd_b = [&](int slot, bf16x8 (&f)[2]) {
-      const int bo = b_base + ((slot ^ b_swz) << 4);
-#pragma unroll
-      for (int n = 0; n < 2; ++n) f[n] = *reinterpret_cast<const bf16x8*>(Bc + bo + n * 32 * ROWB);
-    };
+    const gate_step<decltype(stag)::value, CCS> st(A0, B0, A1, B1);
+    st.open();
+    constexpr int TAP = st.TAP;
     bf16x8 am0[4], bh0[2];
-    rd_a(4, am0);
-    rd_b(0, bh0);
+    a_frags[TAP](st.Ac, 4, am0);
+    b_frags(st.Bc, 0, bh0);
     __builtin_amdgcn_sched_barrier(0);
-    // DMA pieces this step issues (same order as dma_b, dma_a, dma_e: the vmcnt counts above rely on it): the weight tile of step S+1, at tap
-    // 1 the A chunk cc+1, in the last step the first addend quarter (into A0 / B0, which that step does not read)
-    constexpr int NB = LAST ? 0 : 4, NA = (TAP == 1 && CC + 1 < CCS) ? 5 : 0, NE = LAST ? 8 : 0, NP = NB + NA + NE;
-    auto piece = [&](int i) {
-      if (i < NB) piece_b(Bn, (S + 1) / 3, (S + 1) % 3, i);
-      else if (i < NB + NA) piece_a(An, CC + 1, i - NB);
-      else piece_e(EQ0, 0, i - NB - NA);
-    };
-    if constexpr (S > 0) {   // the 16 MFMAs deferred by step S-1, one DMA piece after every MFMA until the pieces are out
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int m = (i >> 1) & 3, n = i & 1;
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p_ah[m], i < 8 ? p_bm[n] : p_bh[n], acc[m][n], 0, 0, 0);
-        if (i < NP) {
-          __builtin_amdgcn_sched_barrier(0);
-          piece(i);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      static_assert(NP <= 16, "more DMA pieces than deferred MFMAs");
-    } else {
-#pragma unroll
-      for (int i = 0; i < NP; ++i) piece(i);
-    }
+    deferred(st);
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 ah0[4], bm0[2], am1[4], bh1[2];
-    rd_a(0, ah0);
-    rd_b(4, bm0);
+    a_frags[TAP](st.Ac, 0, ah0);
+    b_frags(st.Bc, 4, bm0);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(am0, bh0);          // G0(0)
+    mfma8<F16>(acc, am0, bh0);     // G0(0)
     __builtin_amdgcn_sched_barrier(0);
-    rd_a(6, am1);
-    rd_b(2, bh1);
+    a_frags[TAP](st.Ac, 6, am1);
+    b_frags(st.Bc, 2, bh1);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(ah0, bm0);          // G1(0)
+    mfma8<F16>(acc, ah0, bm0);     // G1(0)
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(ah0, bh0);          // G2(0)
+    mfma8<F16>(acc, ah0, bh0);     // G2(0)
     __builtin_amdgcn_sched_barrier(0);
-    rd_a(2, p_ah);
-    rd_b(6, p_bm);
+    a_frags[TAP](st.Ac, 2, p_ah);
+    b_frags(st.Bc, 6, p_bm);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(am1, bh1);          // G0(1); G1(1) = p_ah x p_bm and G2(1) = p_ah x p_bh run after the next barrier
+    mfma8<F16>(acc, am1, bh1);     // G0(1); G1(1) = p_ah x p_bm and G2(1) = p_ah x p_bh run after the next barrier
 #pragma unroll
     for (int n = 0; n < 2; ++n) p_bh[n] = bh1[n];
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (LAST) {
-      mfma8(p_ah, p_bm);
-      mfma8(p_ah, p_bh);
+    if constexpr (st.LAST) {
+      mfma8<F16>(acc, p_ah, p_bm);
+      mfma8<F16>(acc, p_ah, p_bh);
     }
   };
   // ---- SPLIT = 2: products H0 = hi x hi, L0 = hi x lo of k-step 0 run inside the step, H1 / L1 of k-step 1 (fragments p_ah, p_bh, p_bm) are
-  // deferred past the next barrier exactly like G1(1) / G2(1) above: the same pipeline with one product group less per k-step.
+  // deferred past the next barrier exactly like G1(1) / G2(1) above (L1 then H1): the same pipeline with one product group less per k-step.
   auto step_w2 = [&](auto stag) {
-    constexpr int S = decltype(stag)::value;
-    constexpr int CC = S / 3, TAP = S % 3;
-    constexpr bool LAST = S + 1 >= 3 * CCS;
-    const char* Ac = (CC & 1) ? A1 : A0;
-    const char* Bc = (S & 1) ? B1 : B0;
-    char* Bn = (S & 1) ? B0 : B1;
-    char* An = (CC & 1) ? A0 : A1;
-    if constexpr (TAP == 2 && CC + 1 < CCS) wait_vmcnt<5>();
-    else wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    auto rd_a = [&](int slot, bf16x8 (&f)[4]) {
-      const int ao = a_base[TAP] + ((slot ^ a_swz[TAP]) << 4);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) f[m] = *reinterpret_cast<const bf16x8*>(Ac + ao + m * 32 * ROWB);
-    };
-    auto rd_b = [&](int slot, bf16x8 (&f)[2]) {
-      const int bo = b_base + ((slot ^ b_swz) << 4);
-#pragma unroll
-      for (int n = 0; n < 2; ++n) f[n] = *reinterpret_cast<const bf16x8*>(Bc + bo + n * 32 * ROWB);
-    };
-    auto mm8 = [&](const bf16x8 (&fa)[4], const bf16x8 (&fb)[2]) {
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = ss_mfma_32x32x16<true>(fa[m], fb[n], acc[m][n]);
-    };
+    const gate_step<decltype(stag)::value, CCS> st(A0, B0, A1, B1);
+    st.open();
+    constexpr int TAP = st.TAP;
     bf16x8 ah0[4], bh0[2];
-    rd_a(0, ah0);
-    rd_b(0, bh0);
+    a_frags[TAP](st.Ac, 0, ah0);
+    b_frags(st.Bc, 0, bh0);
     __builtin_amdgcn_sched_barrier(0);
-    constexpr int NB = LAST ? 0 : 4, NA = (TAP == 1 && CC + 1 < CCS) ? 5 : 0, NE = LAST ? 8 : 0, NP = NB + NA + NE;
-    auto piece = [&](int i) {
-      if (i < NB) piece_b(Bn, (S + 1) / 3, (S + 1) % 3, i);
-      else if (i < NB + NA) piece_a(An, CC + 1, i - NB);
-      else piece_e(EQ0, 0, i - NB - NA);
-    };
-    if constexpr (S > 0) {   // the 16 MFMAs deferred by step S-1 (L1 then H1), one DMA piece after every MFMA until the pieces are out
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int m = (i >> 1) & 3, n = i & 1;
-        acc[m][n] = ss_mfma_32x32x16<true>(p_ah[m], i < 8 ? p_bm[n] : p_bh[n], acc[m][n]);
-        if (i < NP) {
-          __builtin_amdgcn_sched_barrier(0);
-          piece(i);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      static_assert(NP <= 16, "more DMA pieces than deferred MFMAs");
-    } else {
-#pragma unroll
-      for (int i = 0; i < NP; ++i) piece(i);
-    }
+    deferred(st);
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 bm0[2];
-    rd_b(4, bm0);
+    b_frags(st.Bc, 4, bm0);
     __builtin_amdgcn_sched_barrier(0);
-    mm8(ah0, bh0);            // H0
+    mfma8<F16>(acc, ah0, bh0);     // H0
     __builtin_amdgcn_sched_barrier(0);
-    rd_a(2, p_ah);
-    rd_b(2, p_bh);
+    a_frags[TAP](st.Ac, 2, p_ah);
+    b_frags(st.Bc, 2, p_bh);
     __builtin_amdgcn_sched_barrier(0);
-    mm8(ah0, bm0);            // L0
+    mfma8<F16>(acc, ah0, bm0);     // L0
     __builtin_amdgcn_sched_barrier(0);
-    rd_b(6, p_bm);            // H1 = p_ah x p_bh and L1 = p_ah x p_bm run after the next barrier
+    b_frags(st.Bc, 6, p_bm);       // H1 = p_ah x p_bh and L1 = p_ah x p_bm run after the next barrier
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (LAST) {
-      mm8(p_ah, p_bm);
-      mm8(p_ah, p_bh);
+    if constexpr (st.LAST) {
+      mfma8<F16>(acc, p_ah, p_bm);
+      mfma8<F16>(acc, p_ah, p_bh);
     }
   };
+  // ---- plain bf16: the step's DMA goes out in one burst after the barrier, then four k-steps of one product
   auto step = [&](auto stag) {
     constexpr int S = decltype(stag)::value;
-    constexpr int CC = S / 3, TAP = S % 3;
-    constexpr bool LAST = S + 1 >= 3 * CCS;
-    const char* Ac = (CC & 1) ? A1 : A0;
-    const char* Bc = (S & 1) ? B1 : B0;
-    char* Bn = (S & 1) ? B0 : B1;
-    char* An = (CC & 1) ? A0 : A1;
-    // (no DMA is ever issued past the last step: the epilogue's addend quarters reuse this memory and must not race with zero fills)
-    if constexpr (TAP == 2 && CC + 1 < CCS) wait_vmcnt<5>();   // the 5 pieces of A chunk cc+1, issued last step after its weight pieces
-    else wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    if constexpr (!LAST) dma_b(Bn, (S + 1) / 3, (S + 1) % 3, 0);
+    const gate_step<S, CCS> st(A0, B0, A1, B1);
+    st.open();
+    constexpr int TAP = st.TAP;
+    if constexpr (!st.LAST) dma_b(st.Bn, S + 1);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TAP == 1 && CC + 1 < CCS) dma_a(An, CC + 1, 0);
-    if constexpr (LAST) {   // the first addend quarter flies under the last step (into A0 / B0, which that step does not read)
+    if constexpr (st.A_NEXT) dma_a(st.An, st.CC + 1);
+    if constexpr (st.LAST) {   // the first addend quarter flies under the last step (into A0 / B0, which that step does not read)
       __builtin_amdgcn_sched_barrier(0);
       dma_e(EQ0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (SPLIT) {
-      static_assert(!SPLIT, "the split form has its own step (step_split)");
-    } else {
     // fragments of k-step ks+1 are read before the MFMAs of k-step ks issue (two register sets of 6 x 16 B): the two waves of a SIMD
     // belong to the same workgroup and leave every barrier in lockstep, so a partner's MFMAs do NOT cover this wave's LDS latency
     bf16x8 af[2][4], bf[2][2];
-    auto read_frags = [&](int ks, bf16x8 (&fa)[4], bf16x8 (&fb)[2]) {
-      const int ao = a_base[TAP] + (((2 * ks) ^ a_swz[TAP]) << 4);
-      const int bo = b_base + (((2 * ks) ^ b_swz) << 4);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) fa[m] = *reinterpret_cast<const bf16x8*>(Ac + ao + m * 32 * ROWB);
-#pragma unroll
-      for (int n = 0; n < 2; ++n) fb[n] = *reinterpret_cast<const bf16x8*>(Bc + bo + n * 32 * ROWB);
+    auto read_ks = [&](int ks, bf16x8 (&fa)[4], bf16x8 (&fb)[2]) {
+      a_frags[TAP](st.Ac, 2 * ks, fa);
+      b_frags(st.Bc, 2 * ks, fb);
     };
-    read_frags(0, af[0], bf[0]);
+    read_ks(0, af[0], bf[0]);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if (ks + 1 < 4) read_frags(ks + 1, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
+      if (ks + 1 < 4) read_ks(ks + 1, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][m], bf[ks & 1][n], acc[m][n], 0, 0, 0);
+      mfma8<false>(acc, af[ks & 1], bf[ks & 1]);
       __builtin_amdgcn_sched_barrier(0);
-    }
     }
   };
-  dma_a(A0, 0, 0);
+  dma_a(A0, 0);
   __builtin_amdgcn_sched_barrier(0);
-  dma_b(B0, 0, 0, 0);
+  dma_b(B0, 0);
   __builtin_amdgcn_sched_barrier(0);
   static_assert((CCS & 1) == 0, "the epilogue's LDS plan assumes the last step reads A1 / B1");
   if constexpr (W2) unrolled_steps(step_w2, std::make_integer_sequence<int, 3 * CCS>{});
@@ -372,11 +257,7 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
   const int ocl = 32 * wn + l31;                 // output channel inside the tile
   const bool ch_ok = (n0 >> 1) + ocl < a.N;
   const float b0 = (biasg && ch_ok) ? biasg[n0 + pcl] : 0.f, b1 = (biasg && ch_ok) ? biasg[n0 + pcl + 32] : 0.f;
-  const bool sig_first = a.gate_mode == 0;
-  const float L2E = 1.44269504088896340736f;
-  const float m0 = (sig_first ? -1.0f : -2.0f) * L2E, s0 = sig_first ? 1.0f : 2.0f, h0 = sig_first ? 0.0f : -1.0f;
-  const float m1 = (sig_first ? -2.0f : -1.0f) * L2E, s1 = sig_first ? 2.0f : 1.0f, h1 = sig_first ? -1.0f : 0.0f;
-  auto act = [](float x, float mul, float sc, float sh) { return fmaf(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * mul)), sc, sh); };
+  const gate_act gate(a.gate_mode);
   const int row_lim = a.mask_rows ? (len < a.T ? len : a.T) : a.T;
   const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(
       uniform_ptr((uint16_t*)a.C + (int64_t)b * a.c_batch_stride), 0, __builtin_amdgcn_readfirstlane((int)((int64_t)a.T * a.ldc * 2)), 0x00020000);
@@ -402,8 +283,8 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
       const float e0 = *reinterpret_cast<const float*>(Eq + e_rd + rr * 1024);
       const float e1 = *reinterpret_cast<const float*>(Eq + e_rd + rr * 1024 + 128);
       float g;
-      if constexpr (W2) g = act(fmaf(acc[q][0][r], a.out_scale, b0 + e0), m0, s0, h0) * act(fmaf(acc[q][1][r], a.out_scale, b1 + e1), m1, s1, h1);
-      else g = act(acc[q][0][r] + b0 + e0, m0, s0, h0) * act(acc[q][1][r] + b1 + e1, m1, s1, h1);
+      if constexpr (W2) g = gate(fmaf(acc[q][0][r], a.out_scale, b0 + e0), fmaf(acc[q][1][r], a.out_scale, b1 + e1));
+      else g = gate(acc[q][0][r] + b0 + e0, acc[q][1][r] + b1 + e1);
       if (t0 + 128 * wm + 32 * q + 4 * lh + rr >= row_lim) g = 0.f;
       const uint16_t gh = ss_f2t<W2>(g);
       *reinterpret_cast<uint16_t*>(OUT + o_wr + rr * OROW) = gh;
@@ -441,16 +322,25 @@ __global__ __launch_bounds__(512, 2) void gate256_kernel(const ss_gemm_bf16_args
 
 }  // namespace
 
-// 1 if ss_gemm_bf16 should hand this GATE launch to the 256x256 kernel: three symmetric taps, dilation <= 8, K a multiple of 64,
-// Np a multiple of 256, and enough rows that 256-row tiles fill the chip several times over
+// The launch contract: nullptr, or the first rule the launch breaks (the launcher puts the kernel's name in front). ss_gemm_bf16_gate256_ok asks it, so a launch that misses a rule takes the
+// generic kernel instead of failing; ss_gemm_bf16_gate256 refuses with the same message.
+static const char* gate256_contract(const ss_gemm_bf16_args& a) {
+  if (!(a.A && a.W && a.C)) return "null A/W/C";
+  if (!(a.epi == SS_HEPI_GATE && ss_taps_symmetric(a.ntaps, a.tap_off, HALO))) return "GATE with taps (-d, 0, d), 1 <= d <= 8 only";
+  if (!(a.K == 256 && (a.Np % BN) == 0 && 2 * a.N <= a.Np && (a.lda % 8) == 0 && (a.N % 8) == 0 && (a.ldc % 8) == 0))
+    return "K = 256, Np % 256, 2 N <= Np, lda % 8, N % 8, ldc % 8";
+  if (!(ss_fits_i31(a.T, a.lda, 2) && ss_fits_i31(a.T, a.lde, 4) && ss_fits_i31(a.T, a.ldc, 2) && ss_fits_i31(a.Np, 3 * a.K, 4)))
+    return "item too large for 32-bit offsets";
+  if (!(a.split == 0 || ((a.split == 1 || a.split == 2) && (a.N % 32) == 0 && a.lda >= 2 * a.K && a.ldc >= 2 * a.N)))
+    return "split = 0 | 1 | 2; split operands need N % 32 == 0, lda >= 2 K, ldc >= 2 N";
+  if (!(a.split != 2 || ss_out_scale_ok(a.out_scale))) return "split = 2 needs 0 < out_scale <= 1";
+  return nullptr;
+}
+
+// 1 if ss_gemm_bf16 should hand this GATE launch to the 256x256 kernel: the contract holds and there are enough rows that 256-row tiles fill
+// the chip several times over
 extern "C" int ss_gemm_bf16_gate256_ok(const ss_gemm_bf16_args* a) {
-  if (!a || a->epi != SS_HEPI_GATE || a->ntaps != 3) return 0;
-  const int d = a->tap_off[2];
-  if (d < 1 || d > HALO || a->tap_off[0] != -d || a->tap_off[1] != 0) return 0;
-  if (a->K != 256 || (a->Np % BN) != 0 || (a->lda % 8) != 0 || (a->N % 8) != 0 || (a->ldc % 8) != 0) return 0;
-  if (a->split && ((a->N % 32) != 0 || a->lda < 2 * a->K || a->ldc < 2 * a->N)) return 0;
-  // 32-bit offsets inside an item (the launcher asserts the same): longer items take the generic kernel
-  if ((int64_t)a->T * a->lda * 2 >= (1ll << 31) || (int64_t)a->T * a->lde * 4 >= (1ll << 31) || (int64_t)a->T * a->ldc * 2 >= (1ll << 31)) return 0;
+  if (!a || gate256_contract(*a)) return 0;
   const long tiles = (long)ss_cdiv(a->T, BM) * a->B * (a->Np / BN);
   return tiles >= 4l * ss_n_cu() ? 1 : 0;   // four rounds of one workgroup per CU (1024 tiles on the 256 CUs of an MI355X)
 }
@@ -458,33 +348,14 @@ extern "C" int ss_gemm_bf16_gate256_ok(const ss_gemm_bf16_args* a) {
 extern "C" int ss_gemm_bf16_gate256(const ss_gemm_bf16_args* args, void* stream) {
   SS_CHECK_ARG(args != nullptr, "ss_gemm_bf16_gate256: null args");
   const ss_gemm_bf16_args& a = *args;
-  SS_CHECK_ARG(a.A && a.W && a.C, "ss_gemm_bf16_gate256: null A/W/C");
-  SS_CHECK_ARG(a.epi == SS_HEPI_GATE && a.ntaps == 3 && a.tap_off[1] == 0 && a.tap_off[0] == -a.tap_off[2] && a.tap_off[2] >= 1 &&
-                   a.tap_off[2] <= HALO, "ss_gemm_bf16_gate256: GATE with taps (-d, 0, d), 1 <= d <= 8 only");
-  SS_CHECK_ARG(a.K == 256 && (a.Np % BN) == 0 && 2 * a.N <= a.Np && (a.lda % 8) == 0 && (a.N % 8) == 0 && (a.ldc % 8) == 0,
-               "ss_gemm_bf16_gate256: K = 256, Np %% 256, lda %% 8, N %% 8, ldc %% 8");
-  SS_CHECK_ARG((int64_t)a.T * a.lda * 2 < (1ll << 31) && (int64_t)a.T * a.lde * 4 < (1ll << 31) && (int64_t)a.T * a.ldc * 2 < (1ll << 31) &&
-                   (int64_t)a.Np * 3 * a.K * 4 < (1ll << 31), "ss_gemm_bf16_gate256: item too large for 32-bit offsets");
-  SS_CHECK_ARG(a.split == 0 || ((a.split == 1 || a.split == 2) && (a.N % 32) == 0 && a.lda >= 2 * a.K && a.ldc >= 2 * a.N), "ss_gemm_bf16_gate256: split operands need N %% 32 == 0, lda >= 2 K, ldc >= 2 N");
-  SS_CHECK_ARG(a.split != 2 || (a.out_scale > 0.f && a.out_scale <= 1.f), "ss_gemm_bf16_gate256: split = 2 needs 0 < out_scale <= 1");
+  const char* why = gate256_contract(a);
+  SS_CHECK_ARG(!why, "ss_gemm_bf16_gate256: %s", why);
   const int m_tiles_per_item = ss_cdiv(a.T, BM);
   const int m_tiles = m_tiles_per_item * a.B;
   const int n_tiles = a.Np / BN;
-  const int grid = ss_cdiv(m_tiles, 8) * 8 * n_tiles;
   // operands 144 KB; the split epilogue's view is 2 x 64 KB addend quarters + a 32 KB staging tile = all 160 KB of the CU
   const size_t lds = a.split ? (size_t)160 * 1024 : (size_t)2 * AROWS * ROWB + (size_t)2 * BN * ROWB;
-  auto go = [&](auto kern) {
-    // the attribute is per device and cheap: set on every launch (a process may drive several GPUs), failures are reported, not cached
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      ss_set_error("ss_gemm_bf16_gate256: hipFuncSetAttribute(%d bytes of LDS): %s", (int)lds, hipGetErrorString(e));
-      return SS_ERR_HIP;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, (hipStream_t)stream, a, m_tiles_per_item, m_tiles, n_tiles, a.tap_off[2]);
-    return SS_OK;
-  };
   // plain: 4 channel chunks of 64 x 3 taps = 12 steps; split: 8 chunks of 32 (both planes) x 3 taps = 24 steps
-  SS_PROPAGATE(a.split == 2 ? go(&gate256_kernel<8, 2>) : a.split ? go(&gate256_kernel<8, 1>) : go(&gate256_kernel<4, 0>));
-  SS_CHECK_LAUNCH("ss_gemm_bf16_gate256");
-  return SS_OK;
+  const auto kern = a.split == 2 ? &gate256_kernel<8, 2> : a.split ? &gate256_kernel<8, 1> : &gate256_kernel<4, 0>;
+  return ss_launch_lds("ss_gemm_bf16_gate256", kern, ss_cdiv(m_tiles, 8) * 8 * n_tiles, 512, lds, stream, a, m_tiles_per_item, m_tiles, n_tiles, a.tap_off[2]);
 }

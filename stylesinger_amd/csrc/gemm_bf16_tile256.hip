@@ -14,10 +14,7 @@
 // accumulation (the order of the K products inside an accumulator differs: results agree to fp32 rounding).
 // W2 (ss_gemm_bf16_args.split = 2, "fp16x2"): fp16 terms, the A operand's second plane is neither fetched (dead DMA lanes write zeros) nor read, two products hi*hi + hi*lo per
 // k-step (32 MFMAs per step, the 16 of the second k-step deferred), accumulators scaled by args.out_scale where the epilogue first touches them.
-#include "common.h"
-#include "device_prims.h"
-#include "../../include/stylesinger_hip.h"
-#include "pair16.h"
+#include "gemm_lds_dma.h"
 #include <type_traits>
 
 namespace {
@@ -76,16 +73,11 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
   };
 
   // fragment addresses (see gate256_kernel): row = 128 wm + 32 m + l31 for A, 64 wn + 32 n + l31 for B; slot (2 ks) ^ swz = hi, (4 + 2 ks) ^ swz = mid
-  const int a_base = (128 * wm + l31) * ROWB, a_swz = (((128 * wm + l31) >> 1) & 7) ^ lh;
-  const int b_base = (64 * wn + l31) * ROWB, b_swz = (((64 * wn + l31) >> 1) & 7) ^ lh;
+  const frags<4, ROWB> a_frags{(128 * wm + l31) * ROWB, (((128 * wm + l31) >> 1) & 7) ^ lh};
+  const frags<2, ROWB> b_frags{(64 * wn + l31) * ROWB, (((64 * wn + l31) >> 1) & 7) ^ lh};
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+  clear_acc(acc);
 
   // the two product groups (hi x mid, hi x hi of the second k-step) a step defers past the next barrier; zero fragments before the first step
   bf16x8 p_ah[4], p_bh[2], p_bm[2];
@@ -104,30 +96,14 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
       p_bh[n][e] = (__bf16)0.f;
       p_bm[n][e] = (__bf16)0.f;
     }
-  auto mfma8 = [&](const bf16x8 (&fa)[4], const bf16x8 (&fb)[2]) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) acc[m][n] = ss_mfma_32x32x16<W2>(fa[m], fb[n], acc[m][n]);
-  };
   auto step = [&](const char* Ac, const char* Bc, char* An, char* Bn, int c, bool more) {
     wait_vmcnt<0>();                  // my pieces of chunk c have landed (nothing younger is in flight)
     __builtin_amdgcn_s_barrier();     // everyone's have; everyone finished reading chunk c-1's buffers
-    auto rd_a = [&](int slot, bf16x8 (&f)[4]) {
-      const int ao = a_base + ((slot ^ a_swz) << 4);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) f[m] = *reinterpret_cast<const bf16x8*>(Ac + ao + m * 32 * ROWB);
-    };
-    auto rd_b = [&](int slot, bf16x8 (&f)[2]) {
-      const int bo = b_base + ((slot ^ b_swz) << 4);
-#pragma unroll
-      for (int n = 0; n < 2; ++n) f[n] = *reinterpret_cast<const bf16x8*>(Bc + bo + n * 32 * ROWB);
-    };
     [[maybe_unused]] bf16x8 am0[4], ah0[4];
     bf16x8 bh0[2];
-    if constexpr (W2) rd_a(0, ah0);
-    else rd_a(4, am0);
-    rd_b(0, bh0);
+    if constexpr (W2) a_frags(Ac, 0, ah0);
+    else a_frags(Ac, 4, am0);
+    b_frags(Bc, 0, bh0);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (DENSE) {            // 64 channels per step: the previous step's channels 32..63 (two deferred groups) first, a DMA piece after each of the first 8
 #pragma unroll
@@ -142,18 +118,18 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
       }
       __builtin_amdgcn_sched_barrier(0);
       bf16x8 a2[4], b2[2];
-      rd_a(2, a2);
-      rd_b(2, b2);
+      a_frags(Ac, 2, a2);
+      b_frags(Bc, 2, b2);
       __builtin_amdgcn_sched_barrier(0);
-      mfma8(ah0, bh0);                // channels 0..15
+      mfma8<W2>(acc, ah0, bh0);                // channels 0..15
       __builtin_amdgcn_sched_barrier(0);
-      rd_a(4, p_ah);
-      rd_b(4, p_bh);
+      a_frags(Ac, 4, p_ah);
+      b_frags(Bc, 4, p_bh);
       __builtin_amdgcn_sched_barrier(0);
-      mfma8(a2, b2);                  // channels 16..31; 32..47 (p_ah x p_bh) and 48..63 (p_a6 x p_bm) after the next barrier
+      mfma8<W2>(acc, a2, b2);                  // channels 16..31; 32..47 (p_ah x p_bh) and 48..63 (p_a6 x p_bm) after the next barrier
       __builtin_amdgcn_sched_barrier(0);
-      rd_a(6, p_a6);
-      rd_b(6, p_bm);
+      a_frags(Ac, 6, p_a6);
+      b_frags(Bc, 6, p_bm);
       __builtin_amdgcn_sched_barrier(0);
       return;
     }
@@ -166,10 +142,10 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
         if (more) piece(An, Bn, c + 1, i);   // wave-uniform branch
         __builtin_amdgcn_sched_barrier(0);
       }
-      mfma8(ah0, bh0);                // k-step 0 now; the second k-step's group (p_ah x p_bh) after the next barrier
+      mfma8<W2>(acc, ah0, bh0);                // k-step 0 now; the second k-step's group (p_ah x p_bh) after the next barrier
       __builtin_amdgcn_sched_barrier(0);
-      rd_a(2, p_ah);
-      rd_b(2, p_bh);
+      a_frags(Ac, 2, p_ah);
+      b_frags(Bc, 2, p_bh);
       __builtin_amdgcn_sched_barrier(0);
       return;
     }
@@ -186,36 +162,36 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (W2) {   // hi x hi, hi x lo of k-step 0 now; the second k-step's two groups (p_ah x p_bm, p_ah x p_bh) after the next barrier
       bf16x8 bm0[2];
-      rd_b(4, bm0);
+      b_frags(Bc, 4, bm0);
       __builtin_amdgcn_sched_barrier(0);
-      mfma8(ah0, bh0);
+      mfma8<W2>(acc, ah0, bh0);
       __builtin_amdgcn_sched_barrier(0);
-      rd_a(2, p_ah);
-      rd_b(2, p_bh);
+      a_frags(Ac, 2, p_ah);
+      b_frags(Bc, 2, p_bh);
       __builtin_amdgcn_sched_barrier(0);
-      mfma8(ah0, bm0);
+      mfma8<W2>(acc, ah0, bm0);
       __builtin_amdgcn_sched_barrier(0);
-      rd_b(6, p_bm);
+      b_frags(Bc, 6, p_bm);
       __builtin_amdgcn_sched_barrier(0);
       return;
     }
     bf16x8 bm0[2], am1[4], bh1[2];
-    rd_a(0, ah0);
-    rd_b(4, bm0);
+    a_frags(Ac, 0, ah0);
+    b_frags(Bc, 4, bm0);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(am0, bh0);
+    mfma8<W2>(acc, am0, bh0);
     __builtin_amdgcn_sched_barrier(0);
-    rd_a(6, am1);
-    rd_b(2, bh1);
+    a_frags(Ac, 6, am1);
+    b_frags(Bc, 2, bh1);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(ah0, bm0);
+    mfma8<W2>(acc, ah0, bm0);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(ah0, bh0);
+    mfma8<W2>(acc, ah0, bh0);
     __builtin_amdgcn_sched_barrier(0);
-    rd_a(2, p_ah);
-    rd_b(6, p_bm);
+    a_frags(Ac, 2, p_ah);
+    b_frags(Bc, 6, p_bm);
     __builtin_amdgcn_sched_barrier(0);
-    mfma8(am1, bh1);
+    mfma8<W2>(acc, am1, bh1);
 #pragma unroll
     for (int n = 0; n < 2; ++n) p_bh[n] = bh1[n];
     __builtin_amdgcn_sched_barrier(0);
@@ -227,9 +203,9 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
     step(A0, B0, A1, B1, c, true);
     step(A1, B1, A0, B0, c + 1, c + 2 < kchunks);
   }
-  if constexpr (!ONE) mfma8(p_ah, p_bm);
-  mfma8(p_ah, p_bh);
-  if constexpr (DENSE) mfma8(p_a6, p_bm);   // channels 48..63 of the last step, after its 32..47: every accumulator takes its products in channel order
+  if constexpr (!ONE) mfma8<W2>(acc, p_ah, p_bm);
+  mfma8<W2>(acc, p_ah, p_bh);
+  if constexpr (DENSE) mfma8<W2>(acc, p_a6, p_bm);   // channels 48..63 of the last step, after its 32..47: every accumulator takes its products in channel order
 
   // ---- epilogue: four passes of 64 rows (accumulator block m = q of every wave: tile rows 128 wm + 32 q + (0..31) -> staging row 32 wm + ..),
   // staged as fp32 [64][256] in alternating 64-KB halves of the operand memory, then processed row-contiguously
@@ -238,37 +214,8 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
   __builtin_amdgcn_s_barrier();   // everyone is done reading the operand buffers
   const int st_wr = (32 * wm + 4 * lh) * (BN * 4) + (64 * wn + l31) * 4;   // + rr * BN * 4 (+ 128 for n = 1)
   if constexpr (EPI == SS_HEPI_STORE) {
-    float* Cb = (float*)a.C + (int64_t)b * a.c_batch_stride;
-    const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(Cb), 0, __builtin_amdgcn_readfirstlane((int)((int64_t)a.T * a.ldc * 4)), 0x00020000);
-    const int c4 = (tid & 63) * 4;                 // this thread's 4 columns in every row it handles
-    const int dead = c4 < a.N ? 0 : (int)0x80000000;   // N is a multiple of 4
-    float bs[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bs[e] = (biasg && !dead) ? biasg[c4 + e] : 0.f;
-    const bool relu = a.act == SS_ACT_RELU;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      char* St = smem_t256 + (q & 1) * 64 * 1024;
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) *reinterpret_cast<float*>(St + st_wr + ((r & 3) + 8 * (r >> 2)) * (BN * 4) + n * 128) = acc[q][n][r];
-      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): my staging writes are done
-      __builtin_amdgcn_s_barrier();         // the staging tile of pass q is complete (pass q-1's tile, the other half, is being read at most)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {         // 64 rows x 64 float4 = 4096 pieces, eight per thread: piece p = (row p >> 6, columns 4 (p & 63))
-        const int k = (tid >> 6) + 8 * j;   // staging row of piece tid + 512 j
-        const int grow = t0 + 128 * (k >> 5) + 32 * q + (k & 31);
-        float4 v = *reinterpret_cast<const float4*>(St + k * (BN * 4) + c4 * 4);
-        if constexpr (W2) v = make_float4(fmaf(v.x, a.out_scale, bs[0]), fmaf(v.y, a.out_scale, bs[1]), fmaf(v.z, a.out_scale, bs[2]), fmaf(v.w, a.out_scale, bs[3]));
-        else { v.x += bs[0]; v.y += bs[1]; v.z += bs[2]; v.w += bs[3]; }
-        if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-        if (grow >= row_lim) v = make_float4(0.f, 0.f, 0.f, 0.f);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_c, (grow * a.ldc + c4) * 4 | dead, 0, 0);   // rows >= T dropped
-      }
-      // (no barrier here: pass q+1 writes the OTHER half, and pass q+2's writes to this half come after pass q+1's barrier, which every
-      // thread reaches only after its pass-q reads)
-    }
+    char* const smem = smem_t256;
+#include "tile256_store_epilogue.h"
   } else {   // SS_HEPI_RESX on the pair-only stream: Y = pair(x + cur_bias) is read, x updated, Y = pair(x_new + next_bias) rewritten in place
     const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(a.Y + (int64_t)b * a.y_batch_stride), 0, __builtin_amdgcn_readfirstlane((int)((int64_t)a.T * a.ldy * 2)), 0x00020000);
@@ -357,55 +304,49 @@ __global__ __launch_bounds__(512, 2) void tile256s_kernel(const ss_gemm_bf16_arg
 
 bool ss_gemm_bf16_tile256_rounds_ok(int B, int T) { return (long)ss_cdiv(T, BM) * B >= 2L * ss_n_cu(); }
 
-// 1 if ss_gemm_bf16 should hand this launch to the 256-row kernel: split operands, one tap, STORE or RESX on the pair-only stream, N <= 256,
-// an even number of 32-channel chunks, and at least two rounds of 256-row tiles
+// The launch contract: nullptr, or the first rule the launch breaks (the launcher puts the kernel's name in front). ss_gemm_bf16_tile256_ok asks it, so a launch that misses a rule takes the
+// generic kernel instead of failing; ss_gemm_bf16_tile256 refuses with the same message.
+static const char* tile256_contract(const ss_gemm_bf16_args& a) {
+  if (!(a.A && a.W && (a.split == 1 || a.split == 2) && a.ntaps == 1 && a.tap_off[0] == 0)) return "split operands, one tap at offset 0";
+  if (!(a.split != 2 || ss_out_scale_ok(a.out_scale))) return "split = 2 needs 0 < out_scale <= 1";
+  if (!(!(a.a_compact || a.one_product == 2) || (a.split == 2 && a.epi == SS_HEPI_STORE)))
+    return "a_compact / one_product = 2 are the fp16 (split = 2) STORE form only";
+  if (!(a.one_product >= 0 && a.one_product <= 2)) return "one_product = 0 | 1 | 2";
+  if (!(a.N > 0 && a.N <= BN && a.Np >= a.N && (a.K % 64) == 0 && a.lda >= (a.a_compact ? 1 : 2) * a.K && (a.lda % 8) == 0))
+    return "N <= 256, K % 64 == 0, lda % 8 == 0 and >= 2 K (K with a_compact)";
+  if (!(ss_aligned16(a.A) && ss_aligned16(a.W) && (a.a_batch_stride & 7) == 0)) return "A/W must be 16-byte aligned";
+  if (!(ss_fits_i31(a.T, a.lda, 2) && ss_fits_i31(a.Np, a.K, 4))) return "item too large for 32-bit offsets";
+  if (a.epi == SS_HEPI_STORE) {
+    if (!(a.C && (a.N % 4) == 0 && (a.ldc % 4) == 0 && ss_fits_i31(a.T, a.ldc, 4) && (a.act == SS_ACT_NONE_ || a.act == SS_ACT_RELU_)))
+      return "STORE needs C, N % 4 == 0, ldc % 4 == 0, act none | relu";
+  } else if (!(a.epi == SS_HEPI_RESX && a.X == nullptr && a.Y && a.cur_bias && (a.N % 32) == 0 && a.ldy >= 2 * a.N && (a.ldy % 8) == 0 && ss_fits_i31(a.T, a.ldy, 2))) {
+    return "STORE, or RESX on the pair-only stream (X = NULL, Y, cur_bias), N % 32 == 0, ldy % 8 == 0 and >= 2 N";
+  }
+  return nullptr;
+}
+
+// 1 if ss_gemm_bf16 should hand this launch to the 256-row kernel: the contract holds (split operands, one tap, STORE or RESX on the pair-only
+// stream, N <= 256, an even number of 32-channel chunks) and there are at least two rounds of 256-row tiles
 extern "C" int ss_gemm_bf16_tile256_ok(const ss_gemm_bf16_args* a) {
-  if (!a || (a->split != 1 && a->split != 2) || a->ntaps != 1 || a->tap_off[0] != 0) return 0;
-  if (a->epi == SS_HEPI_RESX ? !(a->X == nullptr && a->Y && a->cur_bias && (a->N % 32) == 0 && a->ldy >= 2 * a->N) : a->epi != SS_HEPI_STORE) return 0;
-  if (a->epi == SS_HEPI_STORE && ((a->N % 4) != 0 || (a->ldc % 4) != 0 || (a->act != SS_ACT_NONE_ && a->act != SS_ACT_RELU_))) return 0;
-  if ((a->a_compact || a->one_product == 2) && !(a->split == 2 && a->epi == SS_HEPI_STORE)) return 0;
-  if (a->N > BN || (a->K % 64) != 0 || a->lda < (a->a_compact ? 1 : 2) * a->K || (a->lda % 8) != 0) return 0;
-  if ((int64_t)a->T * a->lda * 2 >= (1ll << 31) || (int64_t)a->T * a->ldc * 4 >= (1ll << 31) || (int64_t)a->T * a->ldy * 2 >= (1ll << 31) ||
-      (int64_t)a->Np * a->K * 4 >= (1ll << 31)) return 0;
+  if (!a || tile256_contract(*a)) return 0;
+  // as before, the predicate (not the launcher) also wants the range of the row stride the launch's epilogue does not use
+  if (!(ss_fits_i31(a->T, a->ldc, 4) && ss_fits_i31(a->T, a->ldy, 2))) return 0;
   return ss_gemm_bf16_tile256_rounds_ok(a->B, a->T) ? 1 : 0;
 }
 
 extern "C" int ss_gemm_bf16_tile256(const ss_gemm_bf16_args* args, void* stream) {
   SS_CHECK_ARG(args != nullptr, "ss_gemm_bf16_tile256: null args");
   const ss_gemm_bf16_args& a = *args;
-  SS_CHECK_ARG(a.A && a.W && (a.split == 1 || a.split == 2) && a.ntaps == 1 && a.tap_off[0] == 0, "ss_gemm_bf16_tile256: split operands, one tap at offset 0");
-  SS_CHECK_ARG(a.split != 2 || (a.out_scale > 0.f && a.out_scale <= 1.f), "ss_gemm_bf16_tile256: split = 2 needs 0 < out_scale <= 1");
-  SS_CHECK_ARG(!(a.a_compact || a.one_product == 2) || (a.split == 2 && a.epi == SS_HEPI_STORE),
-               "ss_gemm_bf16_tile256: a_compact / one_product = 2 are the fp16 (split = 2) STORE form only");
-  SS_CHECK_ARG(a.one_product >= 0 && a.one_product <= 2, "ss_gemm_bf16_tile256: one_product = 0 | 1 | 2");
-  SS_CHECK_ARG(a.N > 0 && a.N <= BN && a.Np >= a.N && (a.K % 64) == 0 && a.lda >= (a.a_compact ? 1 : 2) * a.K && (a.lda % 8) == 0,
-               "ss_gemm_bf16_tile256: N <= 256, K %% 64 == 0, lda >= 2 K (K with a_compact)");
-  SS_CHECK_ARG((((uintptr_t)a.A) & 15) == 0 && (((uintptr_t)a.W) & 15) == 0 && (a.a_batch_stride & 7) == 0, "ss_gemm_bf16_tile256: A/W must be 16-byte aligned");
-  SS_CHECK_ARG((int64_t)a.T * a.lda * 2 < (1ll << 31) && (int64_t)a.Np * a.K * 4 < (1ll << 31), "ss_gemm_bf16_tile256: item too large for 32-bit offsets");
+  const char* why = tile256_contract(a);
+  SS_CHECK_ARG(!why, "ss_gemm_bf16_tile256: %s", why);
   const int m_tiles_per_item = ss_cdiv(a.T, BM);
   const int m_tiles = m_tiles_per_item * a.B;
-  const size_t lds = (size_t)128 * 1024;
   // both operands compact and K a multiple of 128: 64 channels per step (tile256s_kernel<.., DENSE>); knob "skip_dense" = 0 keeps 32-channel steps (A/B)
   const bool dense = a.epi == SS_HEPI_STORE && a.split == 2 && a.a_compact && a.one_product == 2 && (a.K % 128) == 0 && g_ss_tuning.skip_dense != 0;
-  auto go = [&](auto kern) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      ss_set_error("ss_gemm_bf16_tile256: hipFuncSetAttribute(%d bytes of LDS): %s", (int)lds, hipGetErrorString(e));
-      return SS_ERR_HIP;
-    }
-    hipLaunchKernelGGL(kern, dim3(m_tiles), dim3(512), lds, (hipStream_t)stream, a, m_tiles_per_item, m_tiles, a.K / (dense ? 64 : 32));
-    return SS_OK;
-  };
-  if (a.epi == SS_HEPI_STORE) {
-    SS_CHECK_ARG(a.C && (a.N % 4) == 0 && (a.ldc % 4) == 0 && (int64_t)a.T * a.ldc * 4 < (1ll << 31) && (a.act == SS_ACT_NONE_ || a.act == SS_ACT_RELU_),
-                 "ss_gemm_bf16_tile256: STORE needs C, N %% 4 == 0, ldc %% 4 == 0, act none | relu");
-    SS_PROPAGATE(a.split == 2 ? (dense ? go(&tile256s_kernel<SS_HEPI_STORE, true, true, true>) : a.one_product ? go(&tile256s_kernel<SS_HEPI_STORE, true, true>) : go(&tile256s_kernel<SS_HEPI_STORE, true>))
-                              : go(&tile256s_kernel<SS_HEPI_STORE, false>));
-  } else {
-    SS_CHECK_ARG(a.epi == SS_HEPI_RESX && a.X == nullptr && a.Y && a.cur_bias && (a.N % 32) == 0 && a.ldy >= 2 * a.N && (a.ldy % 8) == 0 &&
-                     (int64_t)a.T * a.ldy * 2 < (1ll << 31), "ss_gemm_bf16_tile256: RESX on the pair-only stream (X = NULL, Y, cur_bias), N %% 32 == 0");
-    SS_PROPAGATE(a.split == 2 ? go(&tile256s_kernel<SS_HEPI_RESX, true>) : go(&tile256s_kernel<SS_HEPI_RESX, false>));
-  }
-  SS_CHECK_LAUNCH("ss_gemm_bf16_tile256");
-  return SS_OK;
+  const bool w2 = a.split == 2;
+  const auto kern = a.epi == SS_HEPI_STORE ? (w2 ? (dense ? &tile256s_kernel<SS_HEPI_STORE, true, true, true> : a.one_product ? &tile256s_kernel<SS_HEPI_STORE, true, true>
+                                                                                                                               : &tile256s_kernel<SS_HEPI_STORE, true>)
+                                                  : &tile256s_kernel<SS_HEPI_STORE, false>)
+                                           : (w2 ? &tile256s_kernel<SS_HEPI_RESX, true> : &tile256s_kernel<SS_HEPI_RESX, false>);
+  return ss_launch_lds("ss_gemm_bf16_tile256", kern, m_tiles, 512, (size_t)128 * 1024, stream, a, m_tiles_per_item, m_tiles, a.K / (dense ? 64 : 32));
 }

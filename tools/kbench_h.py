@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--which", default="all")
     ap.add_argument("--split", action="store_true", help="bf16x2: (hi, mid) operand pairs, three products (ss_gemm_bf16_args.split)")
     ap.add_argument("--f16", action="store_true", help="fp16x2: fp16 terms, weights-only split, two products (ss_gemm_bf16_args.split = 2); implies --split")
-    ap.add_argument("--q4", action="store_true", help="with --f16: the gate on ss_gemm_bf16_gate128q (fp16q4: second product on the block-scaled fp4 instruction; NOT yet validated)")
+    ap.add_argument("--q4", action="store_true", help="with --f16: the gate on ss_gemm_bf16_gate128q (fp16q4: second product on the block-scaled fp4 instruction)")
     ap.add_argument("--gate128", action="store_true", help="with --f16: the gate on ss_gemm_bf16_gate128 (256 x 128 tiles, two workgroups per CU)")
     ap.add_argument("--pair-only", action="store_true", help="res with --split: the pair-only residual stream (X = NULL, Y read + rewritten in place)")
     ap.add_argument("--no-e", action="store_true", help="gate without the conditioner addend (what-if: how much of the launch is the addend?)")
