@@ -805,6 +805,38 @@ int ss_pitch_post(const float* f0_a, const int32_t* uv_a, const float* f0_b, con
  * branch (uv[midi == 0] = 1, :288,296) is NOT applied: the reference does not apply it to a given contour. */
 int ss_pitch_given(const float* f0_log2, const float* uv, const int64_t* mel2ph, float* pitch_pred /*[n][2]*/, float* f0_denorm,
                    int64_t* pitch_coarse, int n, void* stream);
+/* Pitch expression controls (forward(pitch_correct=, vibrato_scale=, vibrato_add=); csrc/pitch_edit.hip; definition: `pitch_edit` in
+ * stylesinger_amd/pitch.py, float64): an edit of the merged log2-f0 between the pitch tail and pitch_embed (additive exports, ABI 20). Per item b
+ * with n = lens[b] <= T frames (a DEVICE array, NULL = T; frames >= n count as rests), f [B][ld] fp32 log2 Hz, midi [B][ldm] the score's note per
+ * frame (what ss_gather_expand_i64(note, mel2ph) gives):
+ *   sung     midi[t] > 0, key[t] = min(midi[t], 127); a REGION is a maximal run of sung frames, a HELD RUN [a, e) a maximal run of sung frames
+ *            of equal key;
+ *   cents    x[t] = 1200 (double) f[t]; c[t] = K0 + 100 (key[t] - 69), K0 = 1200 log2(440) passed in;
+ *   window   K(t) = {k : |k| <= W, every frame between t and t + k is sung}: cut at rests and at the item's ends; w [2 W + 1] doubles is an INPUT,
+ *            by convention w[k + W] = 0.5 (1 + cos(pi k / (W + 1))) computed on the host (pitch.edit_weights);
+ *   trend    m[t] = (sum_K w_k x[t + k]) / (sum_K w_k), target nbar[t] the same average of c; all three sums in ascending k, product then sum (no
+ *            contraction);
+ *   vibrato  (vib_depth > 0) on a held run with e - a >= vib_delay + 2 vib_fade, o = a + vib_delay, for t >= o:
+ *            s[t] = vib_depth min(1, (t - o + 1) / vib_fade) min(1, (e - t) / vib_fade) sin((t - o) vib_omega); elsewhere s = 0;
+ *   result   x' = ((m + alpha (nbar - m)) + kappa (x - m)) + s; f_out[t] = (float) (x' / 1200) on sung frames, f_out[t] = f_in[t] bit for bit on
+ *            every other frame of the T columns. alpha = 0, kappa = 1, vib_depth = 0 writes f_in's bits everywhere.
+ * ss_pitch_edit_runs: run_lo / run_hi [B][T] int32 (dense) = a / e of the frame's held run, -1 on every frame that is not sung. One workgroup per
+ *   item: a segmented max scan forward and a segmented min scan backward over chunks of the item, the carry across chunks in a register. Any T.
+ * ss_pitch_edit: tiles of SS_PITCH_EDIT_TILE frames over a grid of ceil(T / SS_PITCH_EDIT_TILE) x B workgroups; a tile with its W halo of x, c and
+ *   the sung flags in LDS, one thread per frame. u [B][ld] fp32 (> 0 = unvoiced) only selects the frames of the statistics; f_in, u and f_out share
+ *   the row stride ld >= T, f_out must not alias f_in. stats [B][6] doubles over the VOICED sung frames (sung and not u > 0): their count; rms of
+ *   x - m; mean of m - nbar; mean of |m - nbar|; max |x' - x| over ALL sung frames; count of voiced sung frames with s != 0 (means and rms 0 for
+ *   a count of 0). stats_partial [B][ceil(T / SS_PITCH_EDIT_TILE)][6] doubles is scratch: every tile writes its sums (a fixed butterfly inside a
+ *   wave, the waves in ascending order), a second small launch adds them per item in ascending tile order. W > SS_PITCH_EDIT_MAX_W is refused
+ *   before anything is launched, never truncated.
+ * No atomics, no allocation, no sync: graph-capturable; an item's results do not depend on B, T, the strides, the other items, or on what the rows
+ * hold at and past lens[b]. */
+#define SS_PITCH_EDIT_TILE 256
+#define SS_PITCH_EDIT_MAX_W 255
+int ss_pitch_edit_runs(const int64_t* midi, int64_t ldm, const int32_t* lens, int32_t* run_lo, int32_t* run_hi, int T, int B, void* stream);
+int ss_pitch_edit(const float* f_in, int64_t ld, const int64_t* midi, int64_t ldm, const float* u, const int32_t* lens, const int32_t* run_lo,
+                  const int32_t* run_hi, const double* w, int W, double K0, double alpha, double kappa, double vib_depth, double vib_omega,
+                  int vib_delay, int vib_fade, float* f_out, double* stats_partial, double* stats, int T, int B, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * HiFi-GAN-NSF vocoder (modules/hifigan/hifigan_nsf.py:105-169, modules/parallel_wavegan/models/source.py:311-531)

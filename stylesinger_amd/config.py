@@ -71,6 +71,11 @@ DEFAULT_HPARAMS = dict(
     # (DPM-Solver++ multistep); mel_sample_steps = network times of the strided samplers; mel_sample_order 1 | 2 (dpmpp); mel_sample_spacing
     # None = the sampler's own default ("uniform" for ddim, "logsnr" for dpmpp); mel_sample_eta (ddim)
     mel_sampler=None, mel_sample_steps=None, mel_sample_order=2, mel_sample_spacing=None, mel_sample_eta=0.0,
+    # not reference keys: pitch expression controls between the pitch tail and pitch_embed (pitch.pitch_edit; forward(pitch_correct=, vibrato_scale=,
+    # vibrato_add=, pitch_smooth_ms=)): pull the pitch trend toward the score's notes (0 .. 1), scale what rides on the trend (>= 0), add a synthetic
+    # vibrato (rate_hz, depth_cents[, delay_ms = 250[, fade_ms = 150]]) to held notes; pitch_smooth_ms = length of the trend window (None = 333).
+    # All None = neutral: nothing is launched and every path gives the bits it gave before
+    pitch_correct=None, vibrato_scale=None, vibrato_add=None, pitch_smooth_ms=None,
 )
 
 # The released HiFi-GAN config ships only inside the un-vendored checkpoint

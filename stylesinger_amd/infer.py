@@ -137,6 +137,8 @@ class StyleSingerInfer(ReferenceProducers):
         this method reads the lengths on the host anyway (`out_lufs`), never through a sync of its own. With `pitch_timing` = "guide" the score is
         sung in the contour's timing (forward(pitch_timing=): the contour on the mel hop grid; as many frames come out as the contour has); items
         left to the linear stretch (`model_out['pitch_retime_status']` != 0) are named in the same place.
+        Pitch expression controls, with or without a contour: `pitch_correct`, `vibrato_scale`, `vibrato_add`, `pitch_smooth_ms` as forward takes
+        them; res['pitch_edit'] then carries the statistics [B, 6] (float64, on the device).
         `out_lufs`: bring every item of `wav` to this BS.1770 integrated loudness (`_to_lufs`; adds res['lufs'], the loudness before the gain).
         `out_true_peak_db`: hold every item of `wav` under this true-peak ceiling with the look-ahead limiter (`_finish_wav`, `limiter.py`; adds
         res['limiter'] = {min_gain, n_limited} as device tensors); with `out_lufs` too the loudness gain is applied in full (res['loudness_gain'])
@@ -147,7 +149,8 @@ class StyleSingerInfer(ReferenceProducers):
         `spk_embed` / `emo_embed` are then the blended [B, 256] (`model.blend_embeds`)."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
-        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band", "pitch_timing", "ref_weights")
+        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band", "pitch_timing", "ref_weights",
+                                           "pitch_correct", "vibrato_scale", "vibrato_add", "pitch_smooth_ms")
                      if batch.get(k) is not None}
         if batch.get("style_cache") is not None:   # the references' style, encoded once by the caller (model.encode_style; `sing_score`)
             passed_on["style_cache"] = batch["style_cache"]
@@ -156,6 +159,8 @@ class StyleSingerInfer(ReferenceProducers):
                          infer=True, note=batch["note"], note_dur=batch["note_dur"], note_type=batch["note_type"], noise=noise, seed=seed,
                          plan_slot=plan_slot, **passed_on)
         res = dict(mel=out["mel_out"], f0=out["f0_denorm"], lens=out["lens"], model_out=out)
+        if "pitch_edit" in out:   # the statistics of the pitch edit, float64 [B, 6] on the device (forward: pitch_correct / vibrato_scale / vibrato_add)
+            res["pitch_edit"] = out["pitch_edit"]
         if vocode:
             res["wav"] = self.vocode(out["mel_out"], out["f0_denorm"], out["lens"], noise=vocoder_noise, seed=seed + 101)
             if out_lufs is not None or out_true_peak_db is not None:
@@ -418,7 +423,9 @@ def main(argv=None):
     `python inference/StyleSinger.py` (StyleSingerInfer.example_run). `--pitch-audio guide.wav | --pitch-npy contour.npy [--pitch-shift semitones]`:
     sing the score on a given pitch contour instead of the predicted one; `--pitch-align dtw [--pitch-align-band-s 2.0]`: the contour is a guide
     with its own timing, warp it onto the score's notes (band in seconds around the linear fit, 0 = full) instead of scaling it linearly; `--pitch-timing guide`: the
-    other way round - lay the score out on the guide's frames (note onsets where the guide has them) so that the result is in sync with the take. `--loud-norm`: loudness-normalise the reference audio as a model trained with
+    other way round - lay the score out on the guide's frames (note onsets where the guide has them) so that the result is in sync with the take.
+    `--pitch-correct A`, `--vibrato-scale K`, `--vibrato-add RATE_HZ DEPTH_CENTS [--vibrato-delay-ms 250] [--vibrato-fade-ms 150]`, `--pitch-smooth-ms 333`:
+    the pitch expression controls of forward (pull the pitch toward the notes, scale the vibrato, add one to held notes), with or without a contour. `--loud-norm`: loudness-normalise the reference audio as a model trained with
     hparams['loud_norm'] expects; `--out-lufs X`: write the result at X LUFS; `--out-true-peak DB [--out-lookahead-ms 2]`: hold the result under DB dBFS
     true peak with the look-ahead limiter (with --out-lufs the loudness gain is then applied in full instead of being divided by the peak); `--vocoder-denoise-c V`: the reference's vocoder output denoise (spectral
     subtraction of V, e.g. 0.1) after the generator, before the loudness target and the writer.
@@ -450,6 +457,13 @@ def main(argv=None):
     ap.add_argument("--pitch-align-band-s", type=float, help="--pitch-align: half-width of the band around the linear fit, seconds (default 2.0; 0 = full)")
     ap.add_argument("--pitch-timing", choices=["guide"], help="sing in the given contour's timing instead of the score's: note onsets where the guide "
                     "has them, as many frames as the contour has (pitch-only alignment: no timing information inside a held or repeated note)")
+    ap.add_argument("--pitch-correct", type=float, metavar="A", help="pull the pitch trend toward the score's notes: 0 = as sung ... 1 = on the notes "
+                    "(with or without a given contour; this project's own trend / vibrato split, rendered quality unassessed)")
+    ap.add_argument("--vibrato-scale", type=float, metavar="K", help="scale what rides on the pitch trend: 0 = flat, 1 = as sung, 2 = twice the vibrato")
+    ap.add_argument("--vibrato-add", type=float, nargs=2, metavar=("RATE_HZ", "DEPTH_CENTS"), help="put a synthetic vibrato on held notes")
+    ap.add_argument("--vibrato-delay-ms", type=float, metavar="MS", help="--vibrato-add: onset after the start of a held note (default 250)")
+    ap.add_argument("--vibrato-fade-ms", type=float, metavar="MS", help="--vibrato-add: fade in and out (default 150)")
+    ap.add_argument("--pitch-smooth-ms", type=float, metavar="MS", help="length of the window that defines the pitch trend (default 333)")
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
@@ -504,6 +518,25 @@ def main(argv=None):
         pitch["pitch_align_band_s"] = a.pitch_align_band_s
     if a.pitch_timing is not None:
         pitch["pitch_timing"] = a.pitch_timing
+    for flag, val in (("--vibrato-delay-ms", a.vibrato_delay_ms), ("--vibrato-fade-ms", a.vibrato_fade_ms)):
+        if val is not None and a.vibrato_add is None:
+            ap.error(f"{flag} belongs to --vibrato-add")
+    edit = {}   # the pitch expression controls: they need neither a contour nor, with --score, ph_dur
+    if a.pitch_correct is not None:
+        edit["pitch_correct"] = a.pitch_correct
+    if a.vibrato_scale is not None:
+        edit["vibrato_scale"] = a.vibrato_scale
+    if a.vibrato_add is not None:
+        edit["vibrato_add"] = (a.vibrato_add[0], a.vibrato_add[1], a.vibrato_delay_ms, a.vibrato_fade_ms)
+    if a.pitch_smooth_ms is not None:
+        edit["pitch_smooth_ms"] = a.pitch_smooth_ms
+    if edit:
+        from .config import DEFAULT_HPARAMS
+        from .pitch import resolve_pitch_edit
+        try:   # (against the default frame rate; the instance checks again with the checkpoint's own)
+            resolve_pitch_edit(edit, DEFAULT_HPARAMS)
+        except ValueError as e:
+            ap.error(str(e))
     if a.ref_weight is not None and not a.ref_blend:
         ap.error("--ref-weight is the weight of --ref-audio among --ref-blend references; it needs --ref-blend")
     ref_blend = None
@@ -522,6 +555,7 @@ def main(argv=None):
             ap.error("--score with a pitch flag needs 'ph_dur' (seconds per phone) in the score: without it the segment frame counts are not known "
                      "before rendering")
         score.update(pitch)
+        score.update(edit)   # per segment; no ph_dur needed (song.EDIT_KEYS are not song.PITCH_KEYS)
         from . import song
         try:
             song.check_pitch_keys(score)
@@ -592,7 +626,7 @@ def main(argv=None):
         _score_run(score, hp or None, a.out, segments_out=a.segments_out, vad_flags=False if a.no_vad_trim else a.vad, max_seconds=a.max_seconds,
                    segment_batch=a.segment_batch, fade_ms=a.fade_ms, **ctor)
         return
-    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch=pitch, ref_blend=ref_blend, **ctor)
+    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch={**pitch, **edit}, ref_blend=ref_blend, **ctor)
 
 
 if __name__ == "__main__":

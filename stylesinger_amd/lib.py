@@ -27,6 +27,7 @@ LIB_PATH = os.environ.get("SS_LIB_PATH") or os.path.join(HERE, "libstylesinger_h
 SS_MAX_TAPS, SS_MAX_LAYERS, SS_HG_MAX_UPS, SS_HG_MAX_KERNELS = (abi.DEFINES[n] for n in ("SS_MAX_TAPS", "SS_MAX_LAYERS", "SS_HG_MAX_UPS", "SS_HG_MAX_KERNELS"))
 ABI_VERSION = abi.DEFINES["SS_ABI_VERSION"]
 ALIGN_MAX_T, ALIGN_MAX_LC = abi.DEFINES["SS_ALIGN_MAX_T"], abi.DEFINES["SS_ALIGN_MAX_LC"]   # size caps of ss_contour_align (pitch.contour_align_device)
+PITCH_EDIT_TILE, PITCH_EDIT_MAX_W = abi.DEFINES["SS_PITCH_EDIT_TILE"], abi.DEFINES["SS_PITCH_EDIT_MAX_W"]   # frames per workgroup / widest half-window of ss_pitch_edit
 EPI_STORE, EPI_GATE, EPI_RESSKIP, EPI_DDPM = (abi.ENUMS["SS_EPI_" + n] for n in ("STORE", "GATE", "RESSKIP", "DDPM"))
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_MISH, ACT_TANH, ACT_LRELU = (abi.ENUMS[f"SS_ACT_{n}_"] for n in ("NONE", "RELU", "GELU", "MISH", "TANH", "LRELU"))
 HEPI_STORE, HEPI_GATE, HEPI_RESX = (abi.ENUMS["SS_HEPI_" + n] for n in ("STORE", "GATE", "RESX"))

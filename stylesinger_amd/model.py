@@ -415,7 +415,20 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         `pitch_pred`, `f0_denorm`, `f0_denorm_pred` (= `f0_denorm`, as stylesinger.py:241 yields for a given contour) and `pitch_coarse`, and
         no `f0_a` / `uv_a` / `f0_b` / `uv_b`. The note-rest rule (uv[midi == 0] = 1) belongs to the predicted branch and is not applied. The
         reference's `mdiff*` / `gdiff*` / `nll*` on this branch are training losses of the f0 nets (:305-307): they are not produced. A
-        recorded `noise` dict needs no `f0_a` / `f0_b` entries in these forms."""
+        recorded `noise` dict needs no `f0_a` / `f0_b` entries in these forms.
+
+        Pitch expression controls, in every branch above (predicted, `f0=` / `uv=`, `pitch_hz` fitted, aligned or in the guide's timing):
+        `pitch_correct=a` in [0, 1] pulls the pitch trend toward the score's notes, `vibrato_scale=k` >= 0 scales what rides on the trend (0 = flat,
+        1 = as sung), `vibrato_add=(rate_hz, depth_cents[, delay_ms = 250[, fade_ms = 150]])` puts a synthetic vibrato on held notes long enough for
+        delay + two fades, `pitch_smooth_ms` (default 333) is the length of the Hann window that defines the trend (pitch.pitch_edit: this project's own
+        definition). Defaults: hparams of the same names; an explicit value wins over hparams, hparams over neutral. The edit sits between the pitch
+        tail and `pitch_embed` (`ss_pitch_edit_runs` + `ss_pitch_edit`, then `ss_pitch_given` on the edited contour with the merged voicing), so the
+        decoder, the mel diffusion and the vocoder's source all see the edited contour. `ret` gains `pitch_pred_raw` / `f0_denorm_raw` (the
+        unedited ones) and `pitch_edit` [B, 6] float64 (voiced sung frames; rms of the vibrato in cents; mean and mean absolute distance of the trend
+        from the notes; largest change in cents; frames carrying synthetic vibrato). No host sync. Neutral or absent (0, 1, no vibrato_add or depth
+        0): no launch, no allocation, no new keys, the bits as before. ValueError before anything is launched on `pitch_correct` outside [0, 1],
+        `vibrato_scale` < 0, a rate outside (0, fps / 4], a depth outside [0, 1200] cents, negative times, or a window beyond the kernel's cap.
+        `pitch_correct=1, vibrato_scale=0` is the hard-tuned effect by construction; what a checkpoint renders from an edited contour is unassessed."""
         if not infer:
             raise NotImplementedError("StyleSingerHIP implements the inference path only (infer=True)")
         pitch_hz, pitch_shift = kwargs.get("pitch_hz"), kwargs.get("pitch_shift")
@@ -447,6 +460,8 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with pitch_timing (a pitch_hz contour) they do not run")
         f0_ts, f0_eta = self._f0_sampler_args(kwargs, f0 is not None or pitch_hz is not None)
         mel_sampler = self._mel_sampler_args(kwargs)
+        from .pitch import resolve_pitch_edit
+        pitch_edit = resolve_pitch_edit(kwargs, self.hp)   # None = neutral or absent: nothing is launched; refusals here, before anything ran
         pooled = ref_mels is not None and ref_mels.dim() == 4
         if pooled and (ref_f0 is None or ref_f0.dim() != 3):
             raise ValueError(f"forward: ref_mels {tuple(ref_mels.shape)} is a pool of references per item; ref_f0 must then be [B, R, Tr]")
@@ -461,7 +476,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, noise=kwargs.get("noise"), seed=int(kwargs.get("seed", self.hp["seed"])),
                                   kwargs=kwargs)
         c.f32 = dict(device=c.dev, dtype=torch.float32)
-        c.f0_ts, c.f0_eta, c.mel_sampler = f0_ts, f0_eta, mel_sampler
+        c.f0_ts, c.f0_eta, c.mel_sampler, c.pitch_edit, c.midi = f0_ts, f0_eta, mel_sampler, pitch_edit, None
         self._encode_text(c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed)
         self._regulate_length(c, mel2ph, f0, uv)
         self._align_style(c, ref_mels, ref_f0)
@@ -715,6 +730,8 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             self._pitch_given(c, f0, uv, pitch_hz, pitch_shift, out)
         else:
             self._pitch_predicted(c, out)
+        if c.pitch_edit is not None:
+            out = self._pitch_edit(c, out)
         pitch_pred, f0_denorm, coarse = out
         ret["pitch_pred"], ret["f0_denorm"], ret["f0_denorm_pred"] = pitch_pred, f0_denorm, f0_denorm
         ret["pitch_coarse"] = coarse
@@ -723,6 +740,24 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c.dec_inp = dec_inp = torch.empty(B, T, H, **f32)
         L.ops.ss_add_bcast_mask(c.dec, c.spk, pitch_emb, c.emo, c.style, dec_inp, B, T, H, c.lens_t)
         ret["decoder_inp"] = dec_inp
+
+    def _pitch_edit(self, c, out):
+        """Pitch expression controls (pitch.pitch_edit; c.pitch_edit from resolve_pitch_edit): the merged log2-f0 of either branch, corrected toward
+        the score's note per frame / its vibrato scaled / a synthetic one added (ss_pitch_edit_runs + ss_pitch_edit), then the pitch tail again
+        on the edited contour (ss_pitch_given: x/2 + x/2 is exact, the voicing is the merged one) -> the new (pitch_pred, f0_denorm, coarse). The
+        unedited pair stays in ret as pitch_pred_raw / f0_denorm_raw, the statistics [B, 6] as pitch_edit. No host sync."""
+        from .pitch import pitch_edit_device
+        B, T, dev, pe = c.B, c.T, c.dev, c.pitch_edit
+        raw_pred, raw_denorm, _ = out
+        if c.midi is None:   # the branch did not build it (a given f0 / uv, the linear fit, the guide's timing: its midi is on the score's axis)
+            c.midi = torch.empty(B, T, device=dev, dtype=torch.int64)
+            L.ops.ss_gather_expand_i64(c.note, c.mel2ph, c.midi, B, c.Tp, T)
+        f, u = raw_pred[:, :, 0].contiguous(), raw_pred[:, :, 1].contiguous()
+        f_e, stats, _, _ = pitch_edit_device(f, u, c.midi, c.lens_t, pe["W"], pe["alpha"], pe["kappa"], pe["vibrato"], fps=pe["fps"])
+        new = (torch.empty(B, T, 2, **c.f32), torch.empty(B, T, **c.f32), torch.empty(B, T, device=dev, dtype=torch.int64))
+        L.ops.ss_pitch_given(f_e, u, c.mel2ph, *new, B * T)
+        c.ret["pitch_pred_raw"], c.ret["f0_denorm_raw"], c.ret["pitch_edit"] = raw_pred, raw_denorm, stats
+        return new
 
     def _pitch_given(self, c, f0, uv, pitch_hz, pitch_shift, out):
         """A given contour: no clamp bounds, no f0 pair loop (pl.graphs["f0"] stays untouched); the mel loop's Philox keys are per call site
@@ -737,7 +772,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
                 hz = contour_fit_device(pitch_hz[0].to(dev), pitch_hz[1], lens_t, T, shift)
             else:   # "dtw": warp the guide onto the score's note per frame (the midi of _pitch_predicted)
                 from .pitch import contour_align_device
-                midi = torch.empty(B, T, device=dev, dtype=torch.int64)
+                c.midi = midi = torch.empty(B, T, device=dev, dtype=torch.int64)
                 L.ops.ss_gather_expand_i64(c.note, c.mel2ph, midi, B, c.Tp, T)
                 hz, a_idx, a_cost, a_status = contour_align_device(pitch_hz[0].to(dev), pitch_hz[1], midi, lens_t, T,
                                                                    band=c.kwargs.get("pitch_align_band"), shift=shift)
@@ -754,7 +789,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         """The f0 pair loop (a8: agnostic + specific denoiser, one grouped loop) and ss_pitch_post (a9)."""
         ret, pl = c.ret, c.pl
         B, T, Tp, H, dev, lens_t, mel2ph = c.B, c.T, c.Tp, self.hp["hidden_size"], c.dev, c.lens_t, c.mel2ph
-        midi = torch.empty(B, T, device=dev, dtype=torch.int64)
+        c.midi = midi = torch.empty(B, T, device=dev, dtype=torch.int64)
         L.ops.ss_gather_expand_i64(c.note, mel2ph, midi, B, Tp, T)
         pl.lens2[B:].copy_(lens_t)
         L.ops.ss_f0_bounds(midi, pl.lo2, pl.hi2, B * T)
@@ -878,7 +913,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             raise L.StyleSingerHipError("non-finite mel after the diffusion loop")
 
     _FRAME_KEYS = ("mel2ph", "style", "pitch_pred", "f0_denorm", "f0_denorm_pred", "pitch_coarse", "f0_a", "uv_a", "f0_b", "uv_b",
-                   "decoder_inp", "decoder_out", "fs2_mel", "x_mask", "diff_cond", "mel_out", "pitch_align_idx")
+                   "decoder_inp", "decoder_out", "fs2_mel", "x_mask", "diff_cond", "mel_out", "pitch_align_idx", "pitch_pred_raw", "f0_denorm_raw")
 
     @classmethod
     def _crop_frames(cls, ret, T, T_out):

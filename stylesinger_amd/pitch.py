@@ -16,6 +16,12 @@ A guide vocal does not: `contour_align` (definition, integer arithmetic) / `cont
 the contour onto the score's per-frame notes by dynamic time warping (forward(pitch_align="dtw")). The reverse direction - the score laid out on the
 GUIDE's frames, so that the render is in sync with the take - is `retime_to_guide` (definition, integers only) / `retime_device` (`ss_retime_mel2ph`,
 csrc/retime.hip): the alignment's path turned into a new mel2ph of the guide's length (forward(pitch_timing="guide")).
+
+Pitch expression controls (forward(pitch_correct=, vibrato_scale=, vibrato_add=, pitch_smooth_ms=)): an edit of the merged log2-f0 of ANY branch,
+predicted or given, between the pitch tail and pitch_embed. `pitch_edit` is the float64 definition (a Hann moving average splits the contour into a
+trend and what rides on it; the trend is pulled toward the score's notes, the rest scaled, a synthetic vibrato added to held notes),
+`pitch_edit_device` the kernels (`ss_pitch_edit_runs`, `ss_pitch_edit`, csrc/pitch_edit.hip), `resolve_pitch_edit` the argument rules every entry
+point shares.
 """
 import numpy as np
 import torch
@@ -364,3 +370,238 @@ def retime_device(mel2ph, lens_t, midi, idx, status_align, lens_c, Lc):
     n_spans = torch.empty(B, device=dev, dtype=torch.int32)
     L.ops.ss_retime_mel2ph(mp, mp.stride(0), md, md.stride(0), ix, sa, lt, lc, out, out.stride(0), src, status, n_spans, T, Lc, B)
     return out, src, status, n_spans
+
+
+# ---- pitch expression controls (forward(pitch_correct=, vibrato_scale=, vibrato_add=, pitch_smooth_ms=)) ------------------------------------------
+# The trend / vibrato split below is this project's own definition - a Hann moving average over the sung neighbourhood of a frame - not any tool's.
+EDIT_K0 = float(1200.0 * np.log2(440.0))   # cents of A4 on the 1200 log2(Hz) axis: passed to the kernel, not restated there
+EDIT_TILE, EDIT_MAX_W = L.PITCH_EDIT_TILE, L.PITCH_EDIT_MAX_W   # frames per workgroup / the widest half-window the kernel's LDS halo holds
+EDIT_SMOOTH_MS = 333.0                     # default pitch_smooth_ms: at 187.5 frames/s (W = 31) the window passes 1 Hz and drops 5-7 Hz
+VIBRATO_DELAY_MS, VIBRATO_FADE_MS = 250.0, 150.0
+EDIT_KEYS = ("pitch_correct", "vibrato_scale", "vibrato_add", "pitch_smooth_ms")
+
+
+def edit_fps(hparams):
+    return float(hparams["audio_sample_rate"]) / float(hparams["hop_size"])
+
+
+def edit_window_frames(smooth_ms, hparams):
+    """Half-width W of the trend window in frames: max(1, round(smooth_ms * 1e-3 * fps / 2)), fps = audio_sample_rate / hop_size."""
+    smooth_ms = float(smooth_ms)
+    if not smooth_ms >= 0 or not np.isfinite(smooth_ms):
+        raise ValueError(f"pitch_smooth_ms={smooth_ms}: milliseconds >= 0")
+    return max(1, int(round(smooth_ms * 1e-3 * edit_fps(hparams) / 2)))
+
+
+def edit_weights(W):
+    """w_k = 0.5 (1 + cos(pi k / (W + 1))), k = -W .. W, float64 [2 W + 1]: a Hann window without its zero end points."""
+    k = np.arange(-int(W), int(W) + 1, dtype=np.float64)
+    return 0.5 * (1.0 + np.cos(np.pi * k / (int(W) + 1)))
+
+
+def _runs_of(key):
+    """(lo, hi) int64 [n]: bounds [lo, hi) of the maximal run of equal `key` around every frame."""
+    n = len(key)
+    if n == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    starts = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+    ends = np.concatenate([starts[1:], [n]])
+    return np.repeat(starts, ends - starts), np.repeat(ends, ends - starts)
+
+
+def held_runs(midi):
+    """run_lo / run_hi int32 [n] (= a, e of the held run [a, e): a maximal run of sung frames with equal min(midi, 127)); -1 on unsung frames."""
+    m = np.asarray(midi, dtype=np.int64)
+    key = np.where(m > 0, np.minimum(m, 127), 0)
+    lo, hi = _runs_of(key)
+    return np.where(key > 0, lo, -1).astype(np.int32), np.where(key > 0, hi, -1).astype(np.int32)
+
+
+def pitch_edit_parts(f, midi, W, alpha=0.0, kappa=1.0, vibrato=None, fps=None, descending=False, cents=None):
+    """Every intermediate of `pitch_edit` (one item, float64 [n] each): x, c, m, nbar, s, xe (= x'), the bool mask `sung`, run_lo / run_hi.
+    descending=True adds the window sums in descending k instead (tests: how much the order of the sums can move a result); cents = x given
+    directly in float64 instead of 1200 f (the window's response to a pure tone, free of the input's fp32 grid; `pitch_edit` never passes it)."""
+    f = np.asarray(f, dtype=np.float32)
+    md = np.asarray(midi, dtype=np.int64)
+    n, W = len(f), int(W)
+    if len(md) != n or W < 1:
+        raise ValueError(f"pitch_edit: {n} frames, {len(md)} notes, W={W}")
+    if not 0.0 <= float(alpha) <= 1.0 or not float(kappa) >= 0.0:
+        raise ValueError(f"pitch_edit: alpha={alpha} outside [0, 1] or kappa={kappa} < 0")
+    alpha, kappa = np.float64(alpha), np.float64(kappa)
+    key = np.where(md > 0, np.minimum(md, 127), 0)
+    sung = key > 0
+    t = np.arange(n, dtype=np.int64)
+    reg_lo, reg_hi = _runs_of(sung)
+    run_lo, run_hi = held_runs(md)
+    x = np.where(sung, 1200.0 * f.astype(np.float64) if cents is None else np.asarray(cents, dtype=np.float64), 0.0)
+    c = EDIT_K0 + 100.0 * (key - 69).astype(np.float64)
+    left, right = np.minimum(W, t - reg_lo), np.minimum(W, reg_hi - 1 - t)   # how far the window reaches inside the region
+    w = edit_weights(W)
+    xp, cp = np.pad(x, W), np.pad(c, W)
+    sx, sc, sw = np.zeros(n), np.zeros(n), np.zeros(n)
+    for k in (range(W, -W - 1, -1) if descending else range(-W, W + 1)):
+        on = sung & (k >= -left) & (k <= right)
+        wk = w[k + W]
+        sx = np.where(on, sx + wk * xp[W + k:W + k + n], sx)
+        sc = np.where(on, sc + wk * cp[W + k:W + k + n], sc)
+        sw = np.where(on, sw + wk, sw)
+    den = np.where(sung, sw, 1.0)
+    m, nbar = sx / den, sc / den
+    s = np.zeros(n)
+    if vibrato is not None and float(vibrato[1]) > 0:
+        rate_hz, depth, delay, fade = float(vibrato[0]), np.float64(vibrato[1]), int(vibrato[2]), int(vibrato[3])
+        if fps is None or delay < 0 or fade < 1:
+            raise ValueError(f"pitch_edit: vibrato = (rate_hz, depth_cents, delay_frames >= 0, fade_frames >= 1) and fps (got {vibrato}, fps={fps})")
+        omega = vibrato_omega(rate_hz, fps)
+        a, e = run_lo.astype(np.int64), run_hi.astype(np.int64)
+        o = a + delay
+        on = sung & (e - a >= delay + 2 * fade) & (t >= o)
+        up = np.minimum(1.0, (t - o + 1).astype(np.float64) / np.float64(fade))
+        down = np.minimum(1.0, (e - t).astype(np.float64) / np.float64(fade))
+        s = np.where(on, depth * up * down * np.sin((t - o).astype(np.float64) * omega), 0.0)
+    xe = ((m + alpha * (nbar - m)) + kappa * (x - m)) + s
+    return dict(x=x, c=c, m=m, nbar=nbar, s=s, xe=xe, sung=sung, run_lo=run_lo, run_hi=run_hi)
+
+
+def vibrato_omega(rate_hz, fps):
+    """Radians per frame of the synthetic vibrato, float64: what the host passes to the kernel."""
+    return float(2.0 * np.pi * float(rate_hz) / float(fps))
+
+
+def pitch_edit(f, midi, W, alpha=0.0, kappa=1.0, vibrato=None, u=None, fps=None):
+    """The definition of the pitch edit (one item, float64): f fp32 [n] = log2 Hz (pitch_pred[..., 0]: continuous through unvoiced frames), midi int64
+    [n] = the score's note per frame (0 = rest), W >= 1 the half-width of the trend window in frames, alpha in [0, 1] the correction, kappa >= 0 the
+    vibrato scale, vibrato = None | (rate_hz, depth_cents, delay_frames, fade_frames >= 1) with fps = frames per second, u [n] (> 0 = unvoiced; None:
+    all voiced) for the statistics only.
+      * a frame is SUNG when midi[t] > 0, and VOICED when additionally not u[t] > 0; a REGION is a maximal run of sung frames, a HELD RUN [a, e) a
+        maximal run of sung frames with equal min(midi, 127);
+      * cents x[t] = 1200 float64(f[t]); note cents c[t] = EDIT_K0 + 100 (min(midi[t], 127) - 69);
+      * weights w_k = 0.5 (1 + cos(pi k / (W + 1))), k = -W .. W (`edit_weights`); window K(t) = {k : |k| <= W and t + k in the region of t}: cut at
+        rests and item ends, renormalised by the weights present;
+      * trend m[t] = sum_K w_k x[t + k] / sum_K w_k, target nbar[t] the same average of c (it glides over the window instead of stepping at note
+        changes); all sums in ascending k;
+      * synthetic vibrato: on a held run with e - a >= delay + 2 fade, o = a + delay, for t >= o:
+        s[t] = depth min(1, (t - o + 1) / fade) min(1, (e - t) / fade) sin((t - o) omega), omega = 2 pi rate_hz / fps; elsewhere s = 0;
+      * x'[t] = m + alpha (nbar - m) + kappa (x - m) + s; f'[t] = fl32(x'[t] / 1200) on sung frames, f'[t] = f[t] bit for bit elsewhere. With
+        alpha = 0, kappa = 1 and no vibrato f' = f bit for bit: m + (x - m) is within 2^-52 relative of the fp32 value it came from;
+      * stats float64 [6] over the voiced sung frames: their count; rms of x - m (vibrato depth, cents); mean of m - nbar (sharp / flat); mean of
+        |m - nbar|; max |x' - x| over ALL sung frames; count of voiced sung frames with s != 0.
+    -> (f' fp32 [n], stats float64 [6], run_lo int32 [n], run_hi int32 [n]) (the held-run bounds, -1 on unsung frames)."""
+    f = np.asarray(f, dtype=np.float32)
+    p = pitch_edit_parts(f, midi, W, alpha, kappa, vibrato, fps)
+    sung = p["sung"]
+    out = f.copy()
+    out[sung] = (p["xe"][sung] / 1200.0).astype(np.float32)
+    voiced = sung if u is None else sung & ~(np.asarray(u) > 0)
+    cnt = int(voiced.sum())
+    d, q = (p["x"] - p["m"])[voiced], (p["m"] - p["nbar"])[voiced]
+    stats = np.array([cnt, np.sqrt(np.sum(d * d) / cnt) if cnt else 0.0, np.sum(q) / cnt if cnt else 0.0, np.sum(np.abs(q)) / cnt if cnt else 0.0,
+                      np.max(np.abs(p["xe"] - p["x"])[sung], initial=0.0), int((p["s"][voiced] != 0).sum())], dtype=np.float64)
+    return out, stats, p["run_lo"], p["run_hi"]
+
+
+def resolve_pitch_edit(kwargs, hparams):
+    """The pitch edit a call asks for: kwargs['pitch_correct' | 'vibrato_scale' | 'vibrato_add' | 'pitch_smooth_ms'] where given (not None), else the
+    same keys of hparams, else neutral. vibrato_add = (rate_hz, depth_cents[, delay_ms = 250[, fade_ms = 150]]).
+    -> None for a neutral edit (pitch_correct 0, vibrato_scale 1, no vibrato_add or depth 0), else dict(W, alpha, kappa, vibrato = None |
+    (rate_hz, depth_cents, delay_frames, fade_frames), fps). ValueError on pitch_correct outside [0, 1], vibrato_scale < 0, a rate outside
+    (0, fps / 4], a depth outside [0, 1200], negative times, a window beyond EDIT_MAX_W. Touches no device."""
+    get = lambda k: kwargs.get(k) if kwargs.get(k) is not None else hparams.get(k)
+    alpha, kappa, vib, ms = get("pitch_correct"), get("vibrato_scale"), get("vibrato_add"), get("pitch_smooth_ms")
+    fps = edit_fps(hparams)
+    alpha = 0.0 if alpha is None else float(alpha)
+    kappa = 1.0 if kappa is None else float(kappa)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"pitch_correct={alpha}: inside [0, 1] (0 = as sung, 1 = the score's notes)")
+    if not (kappa >= 0.0 and np.isfinite(kappa)):
+        raise ValueError(f"vibrato_scale={kappa}: >= 0 (0 = flat, 1 = as sung)")
+    W = edit_window_frames(EDIT_SMOOTH_MS if ms is None else ms, hparams)
+    if W > EDIT_MAX_W:
+        raise ValueError(f"pitch_smooth_ms={ms}: a half-window of {W} frames exceeds the kernel's cap of {EDIT_MAX_W} (refused, never truncated)")
+    vibrato = None
+    if vib is not None:
+        if not isinstance(vib, (tuple, list)) or not 2 <= len(vib) <= 4:
+            raise ValueError(f"vibrato_add={vib!r}: (rate_hz, depth_cents[, delay_ms[, fade_ms]])")
+        rate, depth = float(vib[0]), float(vib[1])
+        delay_ms = VIBRATO_DELAY_MS if len(vib) < 3 or vib[2] is None else float(vib[2])
+        fade_ms = VIBRATO_FADE_MS if len(vib) < 4 or vib[3] is None else float(vib[3])
+        if not 0.0 < rate <= fps / 4:
+            raise ValueError(f"vibrato_add: rate {rate} Hz outside (0, fps / 4 = {fps / 4:g}]")
+        if not 0.0 <= depth <= 1200.0:
+            raise ValueError(f"vibrato_add: depth {depth} cents outside [0, 1200]")
+        if not (delay_ms >= 0.0 and fade_ms >= 0.0 and np.isfinite(delay_ms) and np.isfinite(fade_ms)):
+            raise ValueError(f"vibrato_add: delay {delay_ms} ms / fade {fade_ms} ms: times >= 0")
+        if depth > 0.0:
+            vibrato = (rate, depth, int(round(delay_ms * 1e-3 * fps)), max(1, int(round(fade_ms * 1e-3 * fps))))
+    if alpha == 0.0 and kappa == 1.0 and vibrato is None:
+        return None
+    return dict(W=W, alpha=alpha, kappa=kappa, vibrato=vibrato, fps=fps)
+
+
+def edit_inputs(inp, hparams=None):
+    """The pitch-edit entries of an input dict as `infer_batch` / forward take them ({} when it has none); with hparams they are checked here
+    (`resolve_pitch_edit`), before anything is loaded or rendered. They need neither a contour nor ph_dur."""
+    out = {k: (tuple(inp[k]) if k == "vibrato_add" else float(inp[k])) for k in EDIT_KEYS if inp.get(k) is not None}
+    if out and hparams is not None:
+        resolve_pitch_edit(out, hparams)
+    return out
+
+
+_edit_tables = {}
+
+
+def _edit_weights_device(W, dev):
+    key = (int(W), str(dev))
+    if key not in _edit_tables:
+        _edit_tables[key] = torch.from_numpy(edit_weights(W)).to(dev)
+    return _edit_tables[key]
+
+
+@torch.no_grad()
+def pitch_edit_device(f, u, midi, lens, W, alpha, kappa, vibrato=None, fps=None):
+    """f fp32 [B, T] (log2 Hz), u fp32 [B, T] (> 0 = unvoiced), midi int64 [B, >= T] (the score's note per frame), lens int32 [B] ON THE DEVICE (None
+    = T): `pitch_edit` of every item (`ss_pitch_edit_runs` + `ss_pitch_edit`). vibrato = None | (rate_hz, depth_cents, delay_frames, fade_frames)
+    with fps. -> (f' fp32 [B, T], stats float64 [B, 6], run_lo int32 [B, T], run_hi int32 [B, T]). Rows may be strided (f and u with the same
+    row stride; f' then has it too). No host sync; the weight table of a W is uploaded once per device. A NEUTRAL edit (alpha = 0, kappa = 1, no
+    vibrato or depth 0) launches and allocates nothing: (f, None, None, None). ValueError on bad arguments, before anything is launched."""
+    if not all(torch.is_tensor(t) and t.device.type == "cuda" for t in (f, u, midi)):
+        raise L.StyleSingerHipError("pitch_edit_device needs device tensors: there is no CPU path")
+    W, alpha, kappa = int(W), float(alpha), float(kappa)
+    if f.dim() != 2 or tuple(u.shape) != tuple(f.shape):
+        raise ValueError(f"pitch_edit_device: f {tuple(f.shape)} and u {tuple(u.shape)}: expected [B, T] twice")
+    B, T = f.shape
+    if midi.dim() != 2 or midi.shape[0] != B or midi.shape[1] < T:
+        raise ValueError(f"pitch_edit_device: midi {tuple(midi.shape)} for {B} items and {T} frames")
+    if not 1 <= W <= EDIT_MAX_W:
+        raise ValueError(f"pitch_edit_device: W={W} outside [1, {EDIT_MAX_W}] (refused, never truncated)")
+    if not 0.0 <= alpha <= 1.0 or not (kappa >= 0.0 and np.isfinite(kappa)):
+        raise ValueError(f"pitch_edit_device: alpha={alpha} outside [0, 1] or kappa={kappa} < 0")
+    depth, omega, delay, fade = 0.0, 0.0, 0, 1
+    if vibrato is not None:
+        rate, depth, delay, fade = float(vibrato[0]), float(vibrato[1]), int(vibrato[2]), int(vibrato[3])
+        if fps is None or not rate > 0 or not 0.0 <= depth <= 1200.0 or delay < 0 or fade < 1:
+            raise ValueError(f"pitch_edit_device: vibrato = (rate_hz > 0, depth_cents in [0, 1200], delay_frames >= 0, fade_frames >= 1) and fps "
+                             f"(got {vibrato}, fps={fps})")
+        omega = vibrato_omega(rate, fps)
+    if lens is not None and (not torch.is_tensor(lens) or lens.numel() != B):
+        raise ValueError(f"pitch_edit_device: lens must be a device tensor of {B} lengths")
+    if alpha == 0.0 and kappa == 1.0 and depth == 0.0:
+        return f, None, None, None
+    dev = f.device
+    rows = lambda t, dt: t.dtype == dt and t.stride(1) == 1 and t.stride(0) >= t.shape[1]
+    if not (rows(f, torch.float32) and rows(u, torch.float32) and f.stride(0) == u.stride(0)):
+        f, u = f.float().contiguous(), u.float().contiguous()
+    md = midi if rows(midi, torch.int64) else midi.long().contiguous()
+    lt = None if lens is None else lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    ld = f.stride(0)
+    out = torch.empty(B, ld, device=dev, dtype=torch.float32)[:, :T]
+    run_lo = torch.empty(B, T, device=dev, dtype=torch.int32)
+    run_hi = torch.empty(B, T, device=dev, dtype=torch.int32)
+    n_tiles = (T + EDIT_TILE - 1) // EDIT_TILE
+    partial = torch.empty(B, n_tiles, 6, device=dev, dtype=torch.float64)
+    stats = torch.empty(B, 6, device=dev, dtype=torch.float64)
+    L.ops.ss_pitch_edit_runs(md, md.stride(0), lt, run_lo, run_hi, T, B)
+    L.ops.ss_pitch_edit(f, ld, md, md.stride(0), u, lt, run_lo, run_hi, _edit_weights_device(W, dev), W, EDIT_K0, alpha, kappa, depth, omega, delay, fade,
+                        out, partial, stats, T, B)
+    return out, stats, run_lo, run_hi

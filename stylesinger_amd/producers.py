@@ -368,7 +368,8 @@ class ReferenceProducers:
         inp['pitch_align_band_s'], seconds, default ALIGN_BAND_S, 0 = full) asks for the warp of forward(pitch_align=): -> `pitch_align` and
         `pitch_align_band` = round(s * audio_sample_rate / hop_size) guide frames. inp['pitch_timing'] = "guide" asks for forward(pitch_timing=):
         the score sung in the guide's timing (the contour must be on the mel hop grid, as a tracked `pitch_audio` is) -> `pitch_timing` and the
-        band. -> {} when `inp` has none of them."""
+        band. inp['pitch_correct' | 'vibrato_scale' | 'vibrato_add' | 'pitch_smooth_ms'] (the pitch expression controls of forward; they need no
+        contour) pass through after `pitch.resolve_pitch_edit` has checked them. -> {} when `inp` has none of them."""
         if inp.get("pitch_hz") is not None and inp.get("pitch_audio") is not None:
             raise ValueError("preprocess_input: give inp['pitch_hz'] or inp['pitch_audio'], not both")
         out = {}
@@ -391,6 +392,8 @@ class ReferenceProducers:
                 raise ValueError("preprocess_input: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
             out["pitch_shift"] = float(inp["pitch_shift"])
         out.update(align_inputs(inp, "pitch_hz" in out, int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])))
+        from .pitch import edit_inputs
+        out.update(edit_inputs(inp, self.hparams))   # pitch_correct / vibrato_scale / vibrato_add / pitch_smooth_ms: no contour needed, checked here
         return out
 
     @torch.no_grad()

@@ -36,6 +36,7 @@ from . import lib as L
 from .producers import align_inputs, has_features, row
 
 PITCH_KEYS = ("pitch_hz", "pitch_audio", "pitch_shift", "pitch_align", "pitch_align_band_s", "pitch_timing")
+EDIT_KEYS = ("pitch_correct", "vibrato_scale", "vibrato_add", "pitch_smooth_ms")   # per-segment pitch edits (pitch.pitch_edit): no contour, no ph_dur
 NO_PH_DUR = ("song-level pitch control ({keys}) needs inp['ph_dur'] (seconds per phone): without it the durations are the model's own, so the "
              "segment frame counts are not known before rendering and the contour cannot be cut into per-segment slices")
 
@@ -129,7 +130,8 @@ def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_enco
     """inp: the reference's input dict at any length - `ph` (or `ph_token`), `note`, `note_dur`, `note_type`, optionally `ph_dur`, `pitch_hz`
     (a 1-D contour in Hz over the whole song, any length), `pitch_shift`, `pitch_align` ("dtw": each segment warps its slice of the contour onto its
     own notes; the cut between segments stays linear) with `pitch_align_band_s`, `pitch_timing` ("guide": each segment is sung in the timing of
-    its slice). -> SongPlan."""
+    its slice). `pitch_correct`, `vibrato_scale`, `vibrato_add`, `pitch_smooth_ms` (EDIT_KEYS: the pitch expression controls of forward) apply per
+    segment, are copied into every batch and need neither a contour nor ph_dur. -> SongPlan."""
     keys = check_pitch_keys(inp)
     if "pitch_audio" in keys:
         raise ValueError("plan_song: the planner runs on the host; track inp['pitch_audio'] first and give its contour as inp['pitch_hz'] "
@@ -137,6 +139,8 @@ def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_enco
     if "pitch_shift" in keys and "pitch_hz" not in keys:
         raise ValueError("plan_song: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
     align = align_inputs(inp, "pitch_hz" in keys, sr, hop)   # {} | pitch_align / pitch_timing + pitch_align_band (frames); refusals as preprocess_input
+    from .pitch import edit_inputs
+    edit = edit_inputs({k: inp.get(k) for k in EDIT_KEYS}, dict(audio_sample_rate=sr, hop_size=hop))   # {} | the edit keys, checked; every segment gets them
     if inp.get("ph_token") is not None:
         tokens = np.asarray(inp["ph_token"], dtype=np.int64)
     elif ph_encoder is not None and inp.get("ph") is not None:
@@ -180,7 +184,7 @@ def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_enco
         idx = order[i:i + int(segment_batch)]
         Tp = max(segments[s]["last"] - segments[s]["first"] for s in idx)
         b = dict(txt_tokens=torch.zeros(len(idx), Tp, dtype=torch.long), note=torch.zeros(len(idx), Tp, dtype=torch.long),
-                 note_dur=torch.zeros(len(idx), Tp, dtype=torch.float32), note_type=torch.zeros(len(idx), Tp, dtype=torch.long))
+                 note_dur=torch.zeros(len(idx), Tp, dtype=torch.float32), note_type=torch.zeros(len(idx), Tp, dtype=torch.long), **edit)
         if bounds is not None:
             T = max(segments[s]["n_frames"] for s in idx)
             b["mel2ph"] = torch.zeros(len(idx), T, dtype=torch.long)
@@ -322,6 +326,10 @@ def sing_score(ins, inp, max_seconds=12.0, segment_batch=8, fade_ms=5.0, in_flig
                                     "batches disagree")
     F = starts[-1]
     out = dict(wav=wav[:F * hop], mel=mel[:F * 80].view(F, 80), f0=f0[:F], plan=plan, segments=[])
+    if any("pitch_edit" in res for res in results):   # the pitch edit's statistics per segment, song order, on the device
+        out["pitch_edit"] = torch.zeros(S, 6, device=d, dtype=torch.float64)
+        for rows, res in zip(rows_dev, results):
+            out["pitch_edit"].index_copy_(0, rows, res["pitch_edit"])
     for s, g in enumerate(plan.segments):
         g["start_frame"], g["n_frames"] = starts[s], starts[s + 1] - starts[s]
         out["segments"].append({k: g[k] for k in ("first", "last", "start_frame", "n_frames", "batch", "row")})
