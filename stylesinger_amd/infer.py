@@ -22,8 +22,9 @@ import warnings
 import numpy as np
 import torch
 
+from . import controls
 from . import lib as L
-from .config import make_hparams, make_vocoder_config
+from .config import DEFAULT_HPARAMS, make_hparams, make_vocoder_config
 from .model import StyleSingerHIP
 from .producers import ReferenceProducers, has_features, row
 from .vocoder import get_vocoder_cls
@@ -149,11 +150,7 @@ class StyleSingerInfer(ReferenceProducers):
         `spk_embed` / `emo_embed` are then the blended [B, 256] (`model.blend_embeds`)."""
         hp = self.hparams
         seed = hp["seed"] if seed is None else seed
-        passed_on = {k: batch[k] for k in ("pitch_hz", "pitch_shift", "pitch_align", "pitch_align_band", "pitch_timing", "ref_weights",
-                                           "pitch_correct", "vibrato_scale", "vibrato_add", "pitch_smooth_ms")
-                     if batch.get(k) is not None}
-        if batch.get("style_cache") is not None:   # the references' style, encoded once by the caller (model.encode_style; `sing_score`)
-            passed_on["style_cache"] = batch["style_cache"]
+        passed_on = controls.given(**{k: batch.get(k) for k in controls.BATCH_KEYS})   # (style_cache: the references' style, encoded once by the caller)
         out = self.model(batch["txt_tokens"], mel2ph=batch.get("mel2ph"), spk_embed=batch["spk_embed"], emo_embed=batch["emo_embed"],
                          ref_mels=batch["ref_mels"], ref_f0=batch["ref_f0"], f0=batch.get("f0"), uv=batch.get("uv"), global_steps=320000,
                          infer=True, note=batch["note"], note_dur=batch["note_dur"], note_type=batch["note_type"], noise=noise, seed=seed,
@@ -389,7 +386,7 @@ class StyleSingerInfer(ReferenceProducers):
             inp["ref_audios"], inp["ref_weights"] = list(ref_blend[0]), list(ref_blend[1])
         else:
             inp["ref_audio"] = ref_audio
-        inp.update(pitch or {})   # pitch control: pitch_hz | pitch_audio, pitch_shift (`_pitch_inputs`)
+        inp.update(pitch or {})   # the contour and edit controls in their input-dict form (`controls.CONTOUR_KEYS`, `EDIT_KEYS`)
         ins = _instance(cls, hparams, ctor)
         out = ins.infer_once(inp, vad_flags=vad_flags)
         if ins.hparams.get("out_loudness_lufs") is not None or ins.hparams.get("out_true_peak_db") is not None:
@@ -449,21 +446,7 @@ def main(argv=None):
     ap.add_argument("--vad", choices=["webrtc", "lrt"], help="the voice-activity decision inside trim_long_silences: webrtc = the reference's (the "
                     "webrtcvad package on the host; the default), lrt = this project's own likelihood-ratio decision on the device (not webrtcvad's; "
                     "constants unassessed on recordings)")
-    ap.add_argument("--pitch-audio", help="sing on the pitch of this guide vocal (a WAV file, tracked on the device, 80-800 Hz) instead of the predicted f0")
-    ap.add_argument("--pitch-npy", help="sing on this contour: a .npy file holding a 1-D array of Hz at the mel hop, 0 = unvoiced")
-    ap.add_argument("--pitch-shift", type=float, help="transpose the given contour by this many semitones")
-    ap.add_argument("--pitch-align", choices=["dtw"], help="warp the given contour onto the score's notes by dynamic time warping (a guide vocal "
-                    "with a timing of its own) instead of scaling it linearly")
-    ap.add_argument("--pitch-align-band-s", type=float, help="--pitch-align: half-width of the band around the linear fit, seconds (default 2.0; 0 = full)")
-    ap.add_argument("--pitch-timing", choices=["guide"], help="sing in the given contour's timing instead of the score's: note onsets where the guide "
-                    "has them, as many frames as the contour has (pitch-only alignment: no timing information inside a held or repeated note)")
-    ap.add_argument("--pitch-correct", type=float, metavar="A", help="pull the pitch trend toward the score's notes: 0 = as sung ... 1 = on the notes "
-                    "(with or without a given contour; this project's own trend / vibrato split, rendered quality unassessed)")
-    ap.add_argument("--vibrato-scale", type=float, metavar="K", help="scale what rides on the pitch trend: 0 = flat, 1 = as sung, 2 = twice the vibrato")
-    ap.add_argument("--vibrato-add", type=float, nargs=2, metavar=("RATE_HZ", "DEPTH_CENTS"), help="put a synthetic vibrato on held notes")
-    ap.add_argument("--vibrato-delay-ms", type=float, metavar="MS", help="--vibrato-add: onset after the start of a held note (default 250)")
-    ap.add_argument("--vibrato-fade-ms", type=float, metavar="MS", help="--vibrato-add: fade in and out (default 150)")
-    ap.add_argument("--pitch-smooth-ms", type=float, metavar="MS", help="length of the window that defines the pitch trend (default 333)")
+    controls.add_flags(ap)   # the render controls: contour, pitch edit, f0 and mel sampler
     ap.add_argument("--loud-norm", action="store_true", help="hparams['loud_norm'] with loudness='bs1770': bring the reference audio to -22 LUFS first "
                     "(this project's BS.1770 meter; parity with pyloudnorm unpinned)")
     ap.add_argument("--out-lufs", type=float, help="write the result at this BS.1770 integrated loudness (hparams['out_loudness_lufs'])")
@@ -473,17 +456,6 @@ def main(argv=None):
                     "default 2)")
     ap.add_argument("--vocoder-denoise-c", type=float, help="spectral subtraction of this magnitude on the vocoder's output "
                     "(hparams['vocoder_denoise_c'], e.g. 0.1; 0 = off)")
-    ap.add_argument("--f0-steps", type=int, help="sample the two f0 / uv diffusions at this many of their f0_timesteps network times "
-                    "(hparams['f0_sample_steps']; default: every one, the reference's loop)")
-    ap.add_argument("--f0-eta", type=float, help="--f0-steps: 0 = deterministic Gaussian half ... 1 = ancestral (hparams['f0_sample_eta'], default 1)")
-    ap.add_argument("--mel-sampler", choices=["ddpm", "ddim", "plms", "dpmpp"], help="how the shallow mel diffusion is sampled (hparams['mel_sampler']): "
-                    "ddpm = the reference's ancestral loop, plms = its PLMS sampler (stride: hparams['pndm_speedup']), ddim / dpmpp = --mel-steps network "
-                    "times, first order / DPM-Solver++ multistep (default: the checkpoint's own choice)")
-    ap.add_argument("--mel-steps", type=int, help="--mel-sampler ddim | dpmpp: at most this many network times (hparams['mel_sample_steps'])")
-    ap.add_argument("--mel-order", type=int, choices=[1, 2], help="--mel-sampler dpmpp: 2 = the 2M multistep update (default), 1 = first order")
-    ap.add_argument("--mel-spacing", choices=["uniform", "logsnr"], help="--mel-steps: the times uniform in t or in the log-SNR "
-                    "(hparams['mel_sample_spacing']; default: uniform for ddim, logsnr for dpmpp)")
-    ap.add_argument("--mel-eta", type=float, help="--mel-sampler ddim: 0 = deterministic (default) ... 1 = ancestral (hparams['mel_sample_eta'])")
     ap.add_argument("--score", help="a score of any length as JSON (the keys of example_input.json, optionally ph_dur = seconds per phone): split at "
                     "its rests, rendered in batches, stitched on the device")
     ap.add_argument("--max-seconds", type=float, default=12.0, help="--score: longest merged segment")
@@ -493,50 +465,12 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.vad and a.no_vad_trim:
         ap.error("--vad and --no-vad-trim exclude each other")
-    if a.pitch_audio and a.pitch_npy:
-        ap.error("--pitch-audio and --pitch-npy exclude each other")
-    if a.pitch_shift is not None and not (a.pitch_audio or a.pitch_npy):
-        ap.error("--pitch-shift needs --pitch-audio or --pitch-npy")
-    if a.pitch_align is not None and not (a.pitch_audio or a.pitch_npy):
-        ap.error("--pitch-align needs --pitch-audio or --pitch-npy")
-    if a.pitch_timing is not None and not (a.pitch_audio or a.pitch_npy):
-        ap.error("--pitch-timing needs --pitch-audio or --pitch-npy")
-    if a.pitch_align_band_s is not None and a.pitch_align is None and a.pitch_timing is None:
-        ap.error("--pitch-align-band-s needs --pitch-align")
-    if a.pitch_align_band_s is not None and not a.pitch_align_band_s >= 0:
-        ap.error("--pitch-align-band-s: seconds >= 0 (0 = full)")
-    pitch = {}
-    if a.pitch_audio:
-        pitch["pitch_audio"] = a.pitch_audio
-    if a.pitch_npy:
-        pitch["pitch_hz"] = np.load(a.pitch_npy)
-    if a.pitch_shift is not None:
-        pitch["pitch_shift"] = a.pitch_shift
-    if a.pitch_align is not None:
-        pitch["pitch_align"] = a.pitch_align
-    if a.pitch_align_band_s is not None:
-        pitch["pitch_align_band_s"] = a.pitch_align_band_s
-    if a.pitch_timing is not None:
-        pitch["pitch_timing"] = a.pitch_timing
-    for flag, val in (("--vibrato-delay-ms", a.vibrato_delay_ms), ("--vibrato-fade-ms", a.vibrato_fade_ms)):
-        if val is not None and a.vibrato_add is None:
-            ap.error(f"{flag} belongs to --vibrato-add")
-    edit = {}   # the pitch expression controls: they need neither a contour nor, with --score, ph_dur
-    if a.pitch_correct is not None:
-        edit["pitch_correct"] = a.pitch_correct
-    if a.vibrato_scale is not None:
-        edit["vibrato_scale"] = a.vibrato_scale
-    if a.vibrato_add is not None:
-        edit["vibrato_add"] = (a.vibrato_add[0], a.vibrato_add[1], a.vibrato_delay_ms, a.vibrato_fade_ms)
-    if a.pitch_smooth_ms is not None:
-        edit["pitch_smooth_ms"] = a.pitch_smooth_ms
-    if edit:
-        from .config import DEFAULT_HPARAMS
-        from .pitch import resolve_pitch_edit
-        try:   # (against the default frame rate; the instance checks again with the checkpoint's own)
-            resolve_pitch_edit(edit, DEFAULT_HPARAMS)
-        except ValueError as e:
-            ap.error(str(e))
+    try:   # (against the default hparams; the instance checks again with the checkpoint's own)
+        pitch, hp = controls.from_flags(a, DEFAULT_HPARAMS)
+    except ValueError as e:
+        ap.error(str(e).removeprefix("forward: "))
+    if "pitch_hz" in pitch:
+        pitch["pitch_hz"] = np.load(pitch["pitch_hz"])
     if a.ref_weight is not None and not a.ref_blend:
         ap.error("--ref-weight is the weight of --ref-audio among --ref-blend references; it needs --ref-blend")
     ref_blend = None
@@ -551,11 +485,10 @@ def main(argv=None):
     if a.score:
         with open(a.score) as fh:
             score = {k: v for k, v in json.load(fh).items() if k != "source"}
-        if pitch and score.get("ph_dur") is None:
+        if any(k in pitch for k in controls.CONTOUR_KEYS) and score.get("ph_dur") is None:
             ap.error("--score with a pitch flag needs 'ph_dur' (seconds per phone) in the score: without it the segment frame counts are not known "
                      "before rendering")
-        score.update(pitch)
-        score.update(edit)   # per segment; no ph_dur needed (song.EDIT_KEYS are not song.PITCH_KEYS)
+        score.update(pitch)   # (the edit keys apply per segment and need no ph_dur)
         from . import song
         try:
             song.check_pitch_keys(score)
@@ -572,7 +505,6 @@ def main(argv=None):
         ref_blend = ([a.ref_audio] + [p for p, _ in a.ref_blend], weights)
     emo = torch.load(a.emotion_ckpt, map_location="cpu", weights_only=False)
     spk = torch.load(a.speaker_ckpt, map_location="cpu", weights_only=False)
-    hp = {}
     if a.loud_norm:
         hp["loud_norm"] = True
     if a.out_lufs is not None:
@@ -590,43 +522,13 @@ def main(argv=None):
             hp["out_limiter_lookahead_ms"] = a.out_lookahead_ms
     if a.vocoder_denoise_c is not None:
         hp["vocoder_denoise_c"] = a.vocoder_denoise_c
-    if a.f0_steps is not None:
-        if a.f0_steps < 1:
-            ap.error("--f0-steps: at least 1")
-        hp["f0_sample_steps"] = a.f0_steps
-    if a.f0_eta is not None:
-        if a.f0_steps is None:
-            ap.error("--f0-eta belongs to --f0-steps")
-        if not 0.0 <= a.f0_eta <= 1.0:
-            ap.error("--f0-eta: inside [0, 1]")
-        hp["f0_sample_eta"] = a.f0_eta
-    for flag, val in (("--mel-steps", a.mel_steps), ("--mel-order", a.mel_order), ("--mel-spacing", a.mel_spacing), ("--mel-eta", a.mel_eta)):
-        if val is not None and a.mel_sampler is None:
-            ap.error(f"{flag} belongs to --mel-sampler")
-    if a.mel_sampler is not None:
-        strided = a.mel_sampler in ("ddim", "dpmpp")
-        if strided and a.mel_steps is None:
-            ap.error(f"--mel-sampler {a.mel_sampler} needs --mel-steps")
-        if a.mel_steps is not None and (not strided or a.mel_steps < 1):
-            ap.error("--mel-steps: at least 1, with --mel-sampler ddim or dpmpp")
-        if a.mel_spacing is not None and not strided:
-            ap.error("--mel-spacing belongs to --mel-sampler ddim or dpmpp")
-        if a.mel_order is not None and a.mel_sampler != "dpmpp":
-            ap.error("--mel-order belongs to --mel-sampler dpmpp")
-        if a.mel_eta is not None and (a.mel_sampler != "ddim" or not 0.0 <= a.mel_eta <= 1.0):
-            ap.error("--mel-eta: inside [0, 1], with --mel-sampler ddim")
-        hp["mel_sampler"] = a.mel_sampler
-        for key, val in (("mel_sample_steps", a.mel_steps), ("mel_sample_order", a.mel_order), ("mel_sample_spacing", a.mel_spacing),
-                         ("mel_sample_eta", a.mel_eta)):
-            if val is not None:
-                hp[key] = val
     ctor = dict(exp_dir=a.exp_dir, vocoder_dir=a.vocoder_dir, emotion_state=emo.get("model_state", emo),
                 speaker_state=spk.get("model_state", spk), phone_set=a.phone_set, loudness="bs1770" if a.loud_norm else None)
     if score is not None:
         _score_run(score, hp or None, a.out, segments_out=a.segments_out, vad_flags=False if a.no_vad_trim else a.vad, max_seconds=a.max_seconds,
                    segment_batch=a.segment_batch, fade_ms=a.fade_ms, **ctor)
         return
-    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch={**pitch, **edit}, ref_blend=ref_blend, **ctor)
+    StyleSingerInfer.example_run(hp or None, a.ref_audio, a.out, vad_flags=False if a.no_vad_trim else a.vad, pitch=pitch, ref_blend=ref_blend, **ctor)
 
 
 if __name__ == "__main__":

@@ -14,11 +14,12 @@ import types
 
 import torch
 
+from . import controls
 from . import lib as L
 from . import spec as _spec
 from .config import make_hparams
 from .packing import Packing, _sin_table
-from .plans import MEL_SAMPLERS, MEL_SPACING_DEFAULT, MEL_SPACINGS, Plans, logsnr_timesteps
+from .plans import Plans, logsnr_timesteps
 
 
 def _pad_frames(x, T, dim=-1):
@@ -352,7 +353,6 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         return out
 
     @torch.no_grad()
-    @torch.no_grad()
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, emo_embed=None, ref_mels=None, ref_f0=None, f0=None, uv=None,
                 skip_decoder=False, global_steps=0, infer=False, note=None, note_dur=None, note_type=None, **kwargs):
         """Mirror of StyleSinger.forward (modules/StyleSinger/stylesinger.py:119-187), inference branch only.
@@ -366,14 +366,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         for bit; deterministic after q_sample; "logsnr" spaces the times uniformly in the half log-SNR (`plans.logsnr_timesteps`: the list may be
         shorter than n) and is this sampler's default, `sampler="ddim"` honours `mel_spacing` too and defaults to "uniform"; `mel_steps` is
         also read by "ddim" where `ddim_steps` is absent). Without `sampler` the hparams decide: `mel_sampler` / `mel_sample_steps` /
-        `mel_sample_order` / `mel_sample_spacing` / `mel_sample_eta`, then `pndm_speedup`, then the reference's loop; `mel_sampler` other than
-        "plms" together with `pndm_speedup` is a ValueError, as are an unknown sampler or spacing, mel_steps < 1 and an order outside {1, 2}.
+        `mel_sample_order` / `mel_sample_spacing` / `mel_sample_eta`, then `pndm_speedup`, then the reference's loop.
         `ret["mel_sampler"]` = dict(name, ts, order) names the list whenever a strided sampler ran. What a checkpoint renders at a given n is
         unassessed,
         `f0_steps=n, f0_eta=1.0` (strided sampler of the two f0 / uv diffusions: n of the f0_timesteps network times, `ss_f0diff_sample_strided`;
         f0_eta = 0 deterministic Gaussian half ... 1 ancestral, n = f0_timesteps with f0_eta = 1 IS the reference's loop to fp32 rounding of the
-        coefficients; defaults hparams['f0_sample_steps'] = None - the reference's full loop, unchanged - and hparams['f0_sample_eta'];
-        ValueError together with a given contour),
+        coefficients; defaults hparams['f0_sample_steps'] = None - the reference's full loop, unchanged - and hparams['f0_sample_eta']),
         `sampler="plms", plms_interval=n` (the reference's PLMS sampler, hparams['pndm_speedup'],
         shallow_diffusion_tts.py:165-197), `plan_slot` (workspace/graph set to use: give concurrent forwards on different streams
         different slots), `style_cache` (the dict encode_style() returned for these references: skips
@@ -383,7 +381,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         [B, R] host values >= 0) is a weighted pool - `encode_style_blend` encodes every reference on its own and the style-to-content attention
         runs over all of them at once with log(weight) added to the scores (`ss_attention_seg`): priors on the attention, not a linear mix of
         outputs. A `style_cache` from `encode_style_blend` does the same without the encoder. `spk_embed` / `emo_embed` stay [B, 256]: blend
-        them with `blend_embeds` (unassessed on a checkpoint). 3-D `ref_mels` behave exactly as before; `ref_weights` with them is a ValueError.
+        them with `blend_embeds` (unassessed on a checkpoint). 3-D `ref_mels` behave exactly as before.
 
         Pitch control (infer=True only): sing on a GIVEN f0 contour instead of the two f0 diffusions' output. Two forms:
           * `f0=, uv=` [B, T_out] - the reference's own form (hparams['use_gt_f0'], tasks/StyleSinger/stylesinger.py:176-188): what
@@ -409,7 +407,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             beyond the item), `pitch_retime_status` [B] (1 = not retimed, the linear stretch: the alignment refused the item, or the guide has fewer
             frames than the score has pitch changes) and `pitch_align_idx` / `_cost` / `_status` on the SCORE's frame axis. The alignment is
             pitch-only: it carries no timing information inside a held note or between repeated equal notes, where the phones are spread linearly.
-            ValueError with `f0=` / `uv=` and with `f0_steps`. Default `None`: the paths above, bit for bit.
+            Default `None`: the paths above, bit for bit.
         Both skip `ss_f0_bounds` and the f0 pair loop (and its hipGraph) and run `ss_pitch_given` in place of `ss_pitch_post`; everything from
         `pitch_embed` on is unchanged, and the mel loop draws the same noise as a predicted-f0 forward with the same `seed`. `ret` carries
         `pitch_pred`, `f0_denorm`, `f0_denorm_pred` (= `f0_denorm`, as stylesinger.py:241 yields for a given contour) and `pitch_coarse`, and
@@ -426,61 +424,23 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         decoder, the mel diffusion and the vocoder's source all see the edited contour. `ret` gains `pitch_pred_raw` / `f0_denorm_raw` (the
         unedited ones) and `pitch_edit` [B, 6] float64 (voiced sung frames; rms of the vibrato in cents; mean and mean absolute distance of the trend
         from the notes; largest change in cents; frames carrying synthetic vibrato). No host sync. Neutral or absent (0, 1, no vibrato_add or depth
-        0): no launch, no allocation, no new keys, the bits as before. ValueError before anything is launched on `pitch_correct` outside [0, 1],
-        `vibrato_scale` < 0, a rate outside (0, fps / 4], a depth outside [0, 1200] cents, negative times, or a window beyond the kernel's cap.
-        `pitch_correct=1, vibrato_scale=0` is the hard-tuned effect by construction; what a checkpoint renders from an edited contour is unassessed."""
+        0): no launch, no allocation, no new keys, the bits as before.
+        `pitch_correct=1, vibrato_scale=0` is the hard-tuned effect by construction; what a checkpoint renders from an edited contour is unassessed.
+
+        Which combinations and values of these controls are refused (ValueError, before anything is launched): `controls.py`."""
         if not infer:
             raise NotImplementedError("StyleSingerHIP implements the inference path only (infer=True)")
-        pitch_hz, pitch_shift = kwargs.get("pitch_hz"), kwargs.get("pitch_shift")
-        if (f0 is None) != (uv is None):
-            raise ValueError(f"forward: f0 and uv go together (got {'f0' if uv is None else 'uv'} without {'uv' if uv is None else 'f0'})")
-        if pitch_hz is not None and f0 is not None:
-            raise ValueError("forward: give either pitch_hz (a contour in Hz to fit) or f0 / uv (the normalised contour), not both")
-        if pitch_shift is not None and pitch_hz is None:
-            raise ValueError("forward: pitch_shift transposes the pitch_hz contour; it needs pitch_hz")
-        if pitch_hz is not None and not (isinstance(pitch_hz, (tuple, list)) and len(pitch_hz) == 2):
-            raise ValueError("forward: pitch_hz = (contour_hz [B, Lc], lens_c)")
-        pitch_align, pitch_align_band = kwargs.get("pitch_align"), kwargs.get("pitch_align_band")
-        if pitch_align is not None and pitch_align != "dtw":
-            raise ValueError(f"forward: pitch_align={pitch_align!r}: None (the linear fit) or 'dtw'")
-        if pitch_align is not None and pitch_hz is None:
-            raise ValueError("forward: pitch_align warps the pitch_hz contour onto the score; it needs pitch_hz"
-                             + (" (f0 / uv are taken as they are)" if f0 is not None else ""))
-        if pitch_align_band is not None and pitch_align is None and kwargs.get("pitch_timing") is None:   # pitch_timing aligns too
-            raise ValueError("forward: pitch_align_band is the band of pitch_align='dtw'; it needs pitch_align")
-        if pitch_align_band is not None and int(pitch_align_band) < 0:
-            raise ValueError(f"forward: pitch_align_band={pitch_align_band}: guide frames >= 0 (0 or None = the full matrix)")
-        pitch_timing = kwargs.get("pitch_timing")
-        if pitch_timing is not None and pitch_timing != "guide":
-            raise ValueError(f"forward: pitch_timing={pitch_timing!r}: None (the score's timing) or 'guide'")
-        if pitch_timing is not None and pitch_hz is None:
-            raise ValueError("forward: pitch_timing lays the score out on the pitch_hz contour's frames; it needs pitch_hz"
-                             + (" (f0 / uv are taken as they are)" if f0 is not None else ""))
-        if pitch_timing is not None and kwargs.get("f0_steps") is not None:
-            raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with pitch_timing (a pitch_hz contour) they do not run")
-        f0_ts, f0_eta = self._f0_sampler_args(kwargs, f0 is not None or pitch_hz is not None)
-        mel_sampler = self._mel_sampler_args(kwargs)
-        from .pitch import resolve_pitch_edit
-        pitch_edit = resolve_pitch_edit(kwargs, self.hp)   # None = neutral or absent: nothing is launched; refusals here, before anything ran
-        pooled = ref_mels is not None and ref_mels.dim() == 4
-        if pooled and (ref_f0 is None or ref_f0.dim() != 3):
-            raise ValueError(f"forward: ref_mels {tuple(ref_mels.shape)} is a pool of references per item; ref_f0 must then be [B, R, Tr]")
-        if kwargs.get("ref_weights") is not None:
-            if kwargs.get("style_cache") is not None:
-                raise ValueError("forward: ref_weights are part of the style_cache (encode_style_blend(..., ref_weights)); give them there")
-            if not pooled:
-                raise ValueError("forward: ref_weights weigh a pool of references: ref_mels [B, R, Tr, 80] and ref_f0 [B, R, Tr]")
-            resolve_ref_weights(kwargs["ref_weights"], ref_mels.shape[0], ref_mels.shape[1])   # refused here, before anything is launched
+        ctl = controls.resolve(kwargs, self.hp, self.f0_strided_timesteps, f0, uv, ref_mels, ref_f0)   # refusals here, before anything is launched
+        if ctl.ref_weights is not None:
+            resolve_ref_weights(ctl.ref_weights, ref_mels.shape[0], ref_mels.shape[1])
         self._ensure_packed()
         # c: the per-call state the stages share (shapes, lengths, intermediate activations, the plan) and the result dict
-        c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, noise=kwargs.get("noise"), seed=int(kwargs.get("seed", self.hp["seed"])),
-                                  kwargs=kwargs)
+        c = types.SimpleNamespace(ret={}, dev=txt_tokens.device, ctl=ctl, midi=None)
         c.f32 = dict(device=c.dev, dtype=torch.float32)
-        c.f0_ts, c.f0_eta, c.mel_sampler, c.pitch_edit, c.midi = f0_ts, f0_eta, mel_sampler, pitch_edit, None
         self._encode_text(c, txt_tokens, note, note_dur, note_type, spk_embed, emo_embed)
         self._regulate_length(c, mel2ph, f0, uv)
         self._align_style(c, ref_mels, ref_f0)
-        self._pitch(c, f0, uv, pitch_hz, pitch_shift)
+        self._pitch(c, f0, uv)
         if not skip_decoder:
             if self.prodiff:
                 self._decode_prodiff(c)
@@ -495,74 +455,10 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         return ret
 
     def _f0_sampler_args(self, kwargs, contour_given):
-        """(network times or None, eta) of the f0 pair loop: forward(f0_steps=, f0_eta=), else hparams['f0_sample_steps'] / ['f0_sample_eta'];
-        None = the reference's full ancestral loop (ss_f0diff_sample). Raises ValueError on a bad value; touches no device."""
-        steps, eta = kwargs.get("f0_steps"), kwargs.get("f0_eta")
-        if steps is not None and contour_given:
-            raise ValueError("forward: f0_steps chooses how the f0 / uv diffusions are sampled; with a given contour (f0 / uv or pitch_hz) they do not run")
-        if contour_given:   # the hparams defaults are simply unused
-            return None, 1.0
-        if steps is None:
-            steps = self.hp.get("f0_sample_steps")
-        if eta is None:
-            eta = self.hp.get("f0_sample_eta", 1.0)
-        if steps is not None and int(steps) < 1:
-            raise ValueError(f"forward: f0_steps={steps}: at least 1 (more than f0_timesteps = {self.hp['f0_timesteps']} means all of them)")
-        eta = float(eta)
-        if not 0.0 <= eta <= 1.0:
-            raise ValueError(f"forward: f0_eta={eta}: 0 (deterministic Gaussian half) ... 1 (ancestral)")
-        return (None if steps is None else self.f0_strided_timesteps(int(steps))), eta
+        return controls.f0_sampler(kwargs, self.hp, contour_given, self.f0_strided_timesteps)
 
     def _mel_sampler_args(self, kwargs, use_hparams=True):
-        """How the mel loop is sampled: forward(sampler=, mel_steps= / ddim_steps=, mel_order=, mel_spacing=, eta=, plms_interval=), else
-        hparams['mel_sampler'] / ['mel_sample_steps'] / ['mel_sample_order'] / ['mel_sample_spacing'] / ['mel_sample_eta'], else the reference's
-        own choice: PLMS under hparams['pndm_speedup'], otherwise its ancestral loop ("ddpm"). Returns a namespace (name, steps, order, spacing,
-        eta, interval); `mel_timesteps` turns steps and spacing into network times once the schedule is packed. Raises ValueError on a bad value;
-        touches no device. `use_hparams=False` (mel_stage, whose `sampler` argument always has a value) reads the arguments alone."""
-        hp = self.hp if use_hparams else {}
-        pndm = hp.get("pndm_speedup")
-        name = kwargs.get("sampler")
-        if name is None:
-            name = hp.get("mel_sampler")
-            if name is not None and name != "plms" and pndm:
-                raise ValueError(f"hparams: mel_sampler={name!r} together with pndm_speedup={pndm} (the reference's PLMS sampler): set one of them")
-        if name is None:
-            name = "plms" if pndm else "ddpm"
-        if name not in MEL_SAMPLERS:
-            raise ValueError(f"mel sampler {name!r}: one of {', '.join(MEL_SAMPLERS)}")
-        spacing = kwargs.get("mel_spacing")
-        if spacing is None:
-            spacing = hp.get("mel_sample_spacing")
-        if spacing is not None and spacing not in MEL_SPACINGS:
-            raise ValueError(f"mel_spacing={spacing!r}: one of {', '.join(MEL_SPACINGS)} (None = the sampler's own default)")
-        order = kwargs.get("mel_order")
-        if order is None:
-            order = hp.get("mel_sample_order", 2)
-        if order not in (1, 2):
-            raise ValueError(f"mel_order={order!r}: 1 (first order: DDIM with eta = 0) or 2 (DPM-Solver++ 2M)")
-        eta = kwargs.get("eta")
-        eta = float(hp.get("mel_sample_eta", 0.0) if eta is None else eta)
-        steps = interval = None
-        if name in MEL_SPACING_DEFAULT:   # the strided samplers
-            steps = kwargs.get("mel_steps")
-            if steps is None and name == "ddim":
-                steps = kwargs.get("ddim_steps")
-            if steps is None:
-                steps = hp.get("mel_sample_steps")
-            if steps is None:
-                raise ValueError(f"mel sampler {name!r} needs a number of network times: mel_steps" + (" / ddim_steps" if name == "ddim" else "")
-                                 + " or hparams['mel_sample_steps']")
-            if int(steps) < 1:
-                raise ValueError(f"mel_steps={steps}: at least 1 (more than K_step = {self.hp['K_step']} means all of them)")
-            steps, spacing = int(steps), spacing or MEL_SPACING_DEFAULT[name]
-        elif name == "plms":
-            interval = kwargs.get("plms_interval")
-            if interval is None:
-                interval = pndm
-            if not interval:
-                raise ValueError("mel sampler 'plms' needs its stride: plms_interval or hparams['pndm_speedup']")
-            interval = int(interval)
-        return types.SimpleNamespace(name=name, steps=steps, order=int(order), spacing=spacing, eta=eta, interval=interval)
+        return controls.mel_sampler(kwargs, self.hp, use_hparams)
 
     def mel_timesteps(self, n, spacing="uniform"):
         """n network times of the shallow mel loop, K_step-1 ... 0: "uniform" in t (`ddim_timesteps`) or "logsnr" (`plans.logsnr_timesteps` over
@@ -634,7 +530,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             T = mel2ph.shape[1]
             ret["dur"] = logdur
         c.score_axis = {}   # results that stay on the score's frame axis when the render does not (pitch_timing="guide")
-        if c.kwargs.get("pitch_timing") is not None:
+        if c.ctl.timing is not None:
             mel2ph, T = self._retime_to_guide(c, mel2ph, T)   # from here on as if the caller had passed this mel2ph: T = the contour's width
         # hipGraph bucket: run the frame axis padded to a multiple of t_bucket (padding = mel2ph 0 -> masked like any
         # batch padding); the plan/graph cache is then keyed by the bucket and every frame-level output is cropped back.
@@ -656,16 +552,16 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         the score's note per frame (ss_contour_align, with pitch_align_band / pitch_shift as for pitch_align="dtw"), then ss_retime_mel2ph puts the
         note onsets where the guide has them (pitch.retime_to_guide). Lengths stay on the device; Lc is the contour's shape: no host sync."""
         from .pitch import contour_align_device, retime_device
-        hz, lens_c = c.kwargs["pitch_hz"]
+        hz, lens_c = c.ctl.pitch_hz
         B, dev = c.B, c.dev
         if hz.dim() != 2 or hz.shape[0] != B:
             raise ValueError(f"forward: pitch_hz contour {tuple(hz.shape)} for a batch of {B}: expected [{B}, Lc]")
         hz, Lc = hz.to(dev), hz.shape[1]
-        shift = c.kwargs.get("pitch_shift")
+        shift = c.ctl.pitch_shift
         L.ops.ss_count_nonzero_i64(mel2ph, c.lens_t, B, T)
         midi = torch.empty(B, T, device=dev, dtype=torch.int64)
         L.ops.ss_gather_expand_i64(c.note, mel2ph, midi, B, c.Tp, T)
-        _, a_idx, a_cost, a_status = contour_align_device(hz, lens_c, midi, c.lens_t, T, band=c.kwargs.get("pitch_align_band"),
+        _, a_idx, a_cost, a_status = contour_align_device(hz, lens_c, midi, c.lens_t, T, band=c.ctl.align_band,
                                                           shift=0.0 if shift is None else float(shift))
         out, src, status, _ = retime_device(mel2ph, c.lens_t, midi, a_idx, a_status, lens_c, Lc)
         c.score_axis = dict(mel2ph_score=mel2ph, pitch_align_idx=a_idx, pitch_align_cost=a_cost, pitch_align_status=a_status)
@@ -676,10 +572,10 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         """Residual Style Adaptor (a5,a6; encode_style, or the caller's style_cache) + style-to-content attention (a7) -> c.style [B,T,H]."""
         pk, ret, f32 = self._pk, c.ret, c.f32
         B, T, H = c.B, c.T, self.hp["hidden_size"]
-        sc = c.kwargs.get("style_cache")
+        sc = c.ctl.style_cache
         if sc is None:
             if ref_mels.dim() == 4:   # a pool of references per item (checked by forward): the weighted blend
-                sc = self.encode_style_blend(ref_mels, ref_f0, c.kwargs.get("ref_weights"))
+                sc = self.encode_style_blend(ref_mels, ref_f0, c.ctl.ref_weights)
             else:
                 sc = self.encode_style(ref_mels, ref_f0)
         seg_lens = sc.get("seg_lens")   # a blend cache (encode_style_blend): R segments of Ts key rows, one ss_attention_seg launch per layer
@@ -715,22 +611,22 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         ret["style"] = c.style = xs
         ret["gloss"] = 0.0
 
-    def _pitch(self, c, f0, uv, pitch_hz, pitch_shift):
+    def _pitch(self, c, f0, uv):
         """Pitch: a given contour, or the two joint Gaussian/multinomial diffusions (a8) + post-processing (a9); then the pitch
         embedding and decoder_inp -> c.dec_inp [B,T,H]. Opens the call's diffusion plan (c.pl, c.graphs)."""
         ret = c.ret
         B, T, H, dev, f32 = c.B, c.T, self.hp["hidden_size"], c.dev, c.f32
-        c.pl = pl = self._plan(B, T, dev, int(c.kwargs.get("plan_slot", 0)))
+        c.pl = pl = self._plan(B, T, dev, c.ctl.plan_slot)
         pl.uses += 1
         pl.lens2[:B].copy_(c.lens_t)
-        pl.seed.fill_(c.seed)
-        c.graphs = c.noise is None and self._want_graphs(pl)
+        pl.seed.fill_(c.ctl.seed)
+        c.graphs = c.ctl.noise is None and self._want_graphs(pl)
         out = (torch.empty(B, T, 2, **f32), torch.empty(B, T, **f32), torch.empty(B, T, device=dev, dtype=torch.int64))
-        if f0 is not None or pitch_hz is not None:
-            self._pitch_given(c, f0, uv, pitch_hz, pitch_shift, out)
+        if f0 is not None or c.ctl.pitch_hz is not None:
+            self._pitch_given(c, f0, uv, out)
         else:
             self._pitch_predicted(c, out)
-        if c.pitch_edit is not None:
+        if c.ctl.edit is not None:
             out = self._pitch_edit(c, out)
         pitch_pred, f0_denorm, coarse = out
         ret["pitch_pred"], ret["f0_denorm"], ret["f0_denorm_pred"] = pitch_pred, f0_denorm, f0_denorm
@@ -742,12 +638,12 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         ret["decoder_inp"] = dec_inp
 
     def _pitch_edit(self, c, out):
-        """Pitch expression controls (pitch.pitch_edit; c.pitch_edit from resolve_pitch_edit): the merged log2-f0 of either branch, corrected toward
+        """Pitch expression controls (pitch.pitch_edit; c.ctl.edit from controls.resolve_pitch_edit): the merged log2-f0 of either branch, corrected toward
         the score's note per frame / its vibrato scaled / a synthetic one added (ss_pitch_edit_runs + ss_pitch_edit), then the pitch tail again
         on the edited contour (ss_pitch_given: x/2 + x/2 is exact, the voicing is the merged one) -> the new (pitch_pred, f0_denorm, coarse). The
         unedited pair stays in ret as pitch_pred_raw / f0_denorm_raw, the statistics [B, 6] as pitch_edit. No host sync."""
         from .pitch import pitch_edit_device
-        B, T, dev, pe = c.B, c.T, c.dev, c.pitch_edit
+        B, T, dev, pe = c.B, c.T, c.dev, c.ctl.edit
         raw_pred, raw_denorm, _ = out
         if c.midi is None:   # the branch did not build it (a given f0 / uv, the linear fit, the guide's timing: its midi is on the score's axis)
             c.midi = torch.empty(B, T, device=dev, dtype=torch.int64)
@@ -759,23 +655,23 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         c.ret["pitch_pred_raw"], c.ret["f0_denorm_raw"], c.ret["pitch_edit"] = raw_pred, raw_denorm, stats
         return new
 
-    def _pitch_given(self, c, f0, uv, pitch_hz, pitch_shift, out):
+    def _pitch_given(self, c, f0, uv, out):
         """A given contour: no clamp bounds, no f0 pair loop (pl.graphs["f0"] stays untouched); the mel loop's Philox keys are per call site
         (constant + pl.seed) and its counters per (step, element), so it draws what a predicted-f0 forward with this seed draws."""
-        B, T, T_out, dev, lens_t = c.B, c.T, c.T_out, c.dev, c.lens_t
+        B, T, T_out, dev, lens_t, pitch_hz = c.B, c.T, c.T_out, c.dev, c.lens_t, c.ctl.pitch_hz
         if pitch_hz is not None:
             from .pitch import contour_fit_device, norm_interp_f0_device
             if pitch_hz[0].dim() != 2 or pitch_hz[0].shape[0] != B:
                 raise ValueError(f"forward: pitch_hz contour {tuple(pitch_hz[0].shape)} for a batch of {B}: expected [{B}, Lc]")
-            shift = 0.0 if pitch_shift is None else float(pitch_shift)
-            if c.kwargs.get("pitch_align") is None or c.kwargs.get("pitch_timing") is not None:   # retimed: the frames ARE the guide's, a 1:1 copy
+            shift = 0.0 if c.ctl.pitch_shift is None else float(c.ctl.pitch_shift)
+            if c.ctl.align is None or c.ctl.timing is not None:   # retimed: the frames ARE the guide's, a 1:1 copy
                 hz = contour_fit_device(pitch_hz[0].to(dev), pitch_hz[1], lens_t, T, shift)
             else:   # "dtw": warp the guide onto the score's note per frame (the midi of _pitch_predicted)
                 from .pitch import contour_align_device
                 c.midi = midi = torch.empty(B, T, device=dev, dtype=torch.int64)
                 L.ops.ss_gather_expand_i64(c.note, c.mel2ph, midi, B, c.Tp, T)
                 hz, a_idx, a_cost, a_status = contour_align_device(pitch_hz[0].to(dev), pitch_hz[1], midi, lens_t, T,
-                                                                   band=c.kwargs.get("pitch_align_band"), shift=shift)
+                                                                   band=c.ctl.align_band, shift=shift)
                 c.ret["pitch_align_idx"], c.ret["pitch_align_cost"], c.ret["pitch_align_status"] = a_idx, a_cost, a_status
             f0_g, uv_g = norm_interp_f0_device(hz, lens_t, self.hp)   # frames >= lens_t[b]: f0 = 0, uv = 0 - masked by mel2ph == 0 below
         else:  # bucket padding: f0 = 0, uv = 1 (mel2ph is 0 there anyway)
@@ -798,7 +694,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
         pl.cond_a.copy_(c.dec)  # = decoder_inp * tgt_nonpadding (the gather already wrote 0 on padding)
         L.ops.ss_add_bcast_mask(c.dec, c.spk, None, c.emo, c.style, pl.cond_b, B, T, H, lens_t)
 
-        ts, eta = c.f0_ts, c.f0_eta   # None: the reference's full loop; else the strided sampler (its tapes: the same [S]... layout, row = network time)
+        ts, eta = c.ctl.f0_ts, c.ctl.f0_eta   # None: the reference's full loop; else the strided sampler (its tapes: the same [S]... layout, row = network time)
 
         def run(noise=None):
             if noise is None:
@@ -813,7 +709,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
             self._run_f0_pair(pl, (zs, us), ts=ts, eta=eta)
         # uv2 is reset outside the graph: before the capture (its warm-up and recording passes accumulate into it) and before every run.
         # One captured graph per sampler: "f0" = the default loop, ("f0", number of steps, eta) = a strided one
-        self._run_loop(pl, "f0" if ts is None else ("f0", len(ts), eta), run, tape=c.noise, graphs=c.graphs, prepare=pl.uv2.zero_)
+        self._run_loop(pl, "f0" if ts is None else ("f0", len(ts), eta), run, tape=c.ctl.noise, graphs=c.graphs, prepare=pl.uv2.zero_)
         f0_a, uv_a, f0_b, uv_b = pl.f0[0].clone(), pl.uv[0].clone(), pl.f0[1].clone(), pl.uv[1].clone()
         ret["gdiff1"] = ret["mdiff1"] = ret["gdiff2"] = ret["mdiff2"] = 0.0
         pitch_pred, f0_denorm, coarse = out
@@ -837,7 +733,7 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
                 zs = _noise_btm(noise["mel"]["z_steps"], c.dev, (S, B, M, c.T_out), T)
             L.ops.ss_prodiff_sample(pk["mel"]["net"], pl.xm, pl.cond_mel, pl.lens, B, T, zs, 37, pl.seed, S, sch["c1"], sch["c2"], sch["sigma"], 1,
                                     wsp, wsb)
-        self._run_loop(pl, "mel", run, tape=c.noise, graphs=c.graphs)
+        self._run_loop(pl, "mel", run, tape=c.ctl.noise, graphs=c.graphs)
         mel_out = torch.empty(B, T, M, **c.f32)
         # the reference leaves padded frames unmasked (prodiff.py:219-220); frames past lens[b] are written as 0 here
         L.ops.ss_add_bcast_mask(pl.xm, None, None, None, None, mel_out, B, T, M, c.lens_t)
@@ -862,13 +758,13 @@ class StyleSingerHIP(Packing, Plans, torch.nn.Module):
 
     def _refine_mel(self, c):
         """Condition projection (a11) + shallow mel diffusion (a12): DDPM by default, `sampler="ddim"` / `"plms"` on request."""
-        hp, pk, ret, pl, kwargs = self.hp, self._pk, c.ret, c.pl, c.kwargs
-        B, T, M, K, dev, noise = c.B, c.T, hp["audio_num_mel_bins"], hp["K_step"], c.dev, c.noise
+        hp, pk, ret, pl = self.hp, self._pk, c.ret, c.pl
+        B, T, M, K, dev, noise = c.B, c.T, hp["audio_num_mel_bins"], hp["K_step"], c.dev, c.ctl.noise
         gcat = torch.cat([c.coarse_mel, c.dec_inp, c.spk[:, None, :].expand(-1, T, -1), c.emo[:, None, :].expand(-1, T, -1), c.style], -1).contiguous()
         self._gemm(gcat, pk["ln_proj"], pl.cond_mel, B, T, mask_rows=False)
         ret["diff_cond"] = pl.cond_mel.clone()
         pl.coarse_mel.copy_(c.coarse_mel)
-        sm = c.mel_sampler   # resolved and checked by forward before anything ran (_mel_sampler_args)
+        sm = c.ctl.mel   # resolved and checked by forward before anything ran (controls.mel_sampler)
         eta = sm.eta
         ts = self.mel_timesteps(sm.steps, sm.spacing) if sm.steps is not None else None
         if ts is not None:

@@ -20,13 +20,14 @@ csrc/retime.hip): the alignment's path turned into a new mel2ph of the guide's l
 Pitch expression controls (forward(pitch_correct=, vibrato_scale=, vibrato_add=, pitch_smooth_ms=)): an edit of the merged log2-f0 of ANY branch,
 predicted or given, between the pitch tail and pitch_embed. `pitch_edit` is the float64 definition (a Hann moving average splits the contour into a
 trend and what rides on it; the trend is pulled toward the score's notes, the rest scaled, a synthetic vibrato added to held notes),
-`pitch_edit_device` the kernels (`ss_pitch_edit_runs`, `ss_pitch_edit`, csrc/pitch_edit.hip), `resolve_pitch_edit` the argument rules every entry
-point shares.
+`pitch_edit_device` the kernels (`ss_pitch_edit_runs`, `ss_pitch_edit`, csrc/pitch_edit.hip), `controls.resolve_pitch_edit` the argument rules every
+entry point shares.
 """
 import numpy as np
 import torch
 
 from . import lib as L
+from .controls import EDIT_SMOOTH_MS, edit_window_frames, resolve_pitch_edit  # noqa: F401  (the edit's window and argument rules: part of this module's surface)
 
 
 def norm_f0(f0, uv, hparams):
@@ -376,21 +377,6 @@ def retime_device(mel2ph, lens_t, midi, idx, status_align, lens_c, Lc):
 # The trend / vibrato split below is this project's own definition - a Hann moving average over the sung neighbourhood of a frame - not any tool's.
 EDIT_K0 = float(1200.0 * np.log2(440.0))   # cents of A4 on the 1200 log2(Hz) axis: passed to the kernel, not restated there
 EDIT_TILE, EDIT_MAX_W = L.PITCH_EDIT_TILE, L.PITCH_EDIT_MAX_W   # frames per workgroup / the widest half-window the kernel's LDS halo holds
-EDIT_SMOOTH_MS = 333.0                     # default pitch_smooth_ms: at 187.5 frames/s (W = 31) the window passes 1 Hz and drops 5-7 Hz
-VIBRATO_DELAY_MS, VIBRATO_FADE_MS = 250.0, 150.0
-EDIT_KEYS = ("pitch_correct", "vibrato_scale", "vibrato_add", "pitch_smooth_ms")
-
-
-def edit_fps(hparams):
-    return float(hparams["audio_sample_rate"]) / float(hparams["hop_size"])
-
-
-def edit_window_frames(smooth_ms, hparams):
-    """Half-width W of the trend window in frames: max(1, round(smooth_ms * 1e-3 * fps / 2)), fps = audio_sample_rate / hop_size."""
-    smooth_ms = float(smooth_ms)
-    if not smooth_ms >= 0 or not np.isfinite(smooth_ms):
-        raise ValueError(f"pitch_smooth_ms={smooth_ms}: milliseconds >= 0")
-    return max(1, int(round(smooth_ms * 1e-3 * edit_fps(hparams) / 2)))
 
 
 def edit_weights(W):
@@ -499,53 +485,6 @@ def pitch_edit(f, midi, W, alpha=0.0, kappa=1.0, vibrato=None, u=None, fps=None)
     stats = np.array([cnt, np.sqrt(np.sum(d * d) / cnt) if cnt else 0.0, np.sum(q) / cnt if cnt else 0.0, np.sum(np.abs(q)) / cnt if cnt else 0.0,
                       np.max(np.abs(p["xe"] - p["x"])[sung], initial=0.0), int((p["s"][voiced] != 0).sum())], dtype=np.float64)
     return out, stats, p["run_lo"], p["run_hi"]
-
-
-def resolve_pitch_edit(kwargs, hparams):
-    """The pitch edit a call asks for: kwargs['pitch_correct' | 'vibrato_scale' | 'vibrato_add' | 'pitch_smooth_ms'] where given (not None), else the
-    same keys of hparams, else neutral. vibrato_add = (rate_hz, depth_cents[, delay_ms = 250[, fade_ms = 150]]).
-    -> None for a neutral edit (pitch_correct 0, vibrato_scale 1, no vibrato_add or depth 0), else dict(W, alpha, kappa, vibrato = None |
-    (rate_hz, depth_cents, delay_frames, fade_frames), fps). ValueError on pitch_correct outside [0, 1], vibrato_scale < 0, a rate outside
-    (0, fps / 4], a depth outside [0, 1200], negative times, a window beyond EDIT_MAX_W. Touches no device."""
-    get = lambda k: kwargs.get(k) if kwargs.get(k) is not None else hparams.get(k)
-    alpha, kappa, vib, ms = get("pitch_correct"), get("vibrato_scale"), get("vibrato_add"), get("pitch_smooth_ms")
-    fps = edit_fps(hparams)
-    alpha = 0.0 if alpha is None else float(alpha)
-    kappa = 1.0 if kappa is None else float(kappa)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"pitch_correct={alpha}: inside [0, 1] (0 = as sung, 1 = the score's notes)")
-    if not (kappa >= 0.0 and np.isfinite(kappa)):
-        raise ValueError(f"vibrato_scale={kappa}: >= 0 (0 = flat, 1 = as sung)")
-    W = edit_window_frames(EDIT_SMOOTH_MS if ms is None else ms, hparams)
-    if W > EDIT_MAX_W:
-        raise ValueError(f"pitch_smooth_ms={ms}: a half-window of {W} frames exceeds the kernel's cap of {EDIT_MAX_W} (refused, never truncated)")
-    vibrato = None
-    if vib is not None:
-        if not isinstance(vib, (tuple, list)) or not 2 <= len(vib) <= 4:
-            raise ValueError(f"vibrato_add={vib!r}: (rate_hz, depth_cents[, delay_ms[, fade_ms]])")
-        rate, depth = float(vib[0]), float(vib[1])
-        delay_ms = VIBRATO_DELAY_MS if len(vib) < 3 or vib[2] is None else float(vib[2])
-        fade_ms = VIBRATO_FADE_MS if len(vib) < 4 or vib[3] is None else float(vib[3])
-        if not 0.0 < rate <= fps / 4:
-            raise ValueError(f"vibrato_add: rate {rate} Hz outside (0, fps / 4 = {fps / 4:g}]")
-        if not 0.0 <= depth <= 1200.0:
-            raise ValueError(f"vibrato_add: depth {depth} cents outside [0, 1200]")
-        if not (delay_ms >= 0.0 and fade_ms >= 0.0 and np.isfinite(delay_ms) and np.isfinite(fade_ms)):
-            raise ValueError(f"vibrato_add: delay {delay_ms} ms / fade {fade_ms} ms: times >= 0")
-        if depth > 0.0:
-            vibrato = (rate, depth, int(round(delay_ms * 1e-3 * fps)), max(1, int(round(fade_ms * 1e-3 * fps))))
-    if alpha == 0.0 and kappa == 1.0 and vibrato is None:
-        return None
-    return dict(W=W, alpha=alpha, kappa=kappa, vibrato=vibrato, fps=fps)
-
-
-def edit_inputs(inp, hparams=None):
-    """The pitch-edit entries of an input dict as `infer_batch` / forward take them ({} when it has none); with hparams they are checked here
-    (`resolve_pitch_edit`), before anything is loaded or rendered. They need neither a contour nor ph_dur."""
-    out = {k: (tuple(inp[k]) if k == "vibrato_add" else float(inp[k])) for k in EDIT_KEYS if inp.get(k) is not None}
-    if out and hparams is not None:
-        resolve_pitch_edit(out, hparams)
-    return out
 
 
 _edit_tables = {}

@@ -122,11 +122,6 @@ def logsnr_timesteps(ac64, K, n):
     return sorted({int(np.argmin(np.abs(lam - g))) for g in grid} | {K - 1, 0}, reverse=True)
 
 
-MEL_SAMPLERS = ("ddpm", "ddim", "plms", "dpmpp")
-MEL_SPACINGS = ("uniform", "logsnr")
-MEL_SPACING_DEFAULT = {"ddim": "uniform", "dpmpp": "logsnr"}   # each strided sampler's own default
-
-
 class Plans:
     """Mixin of StyleSingerHIP: the plan cache and the sampler loops that run on a plan."""
 

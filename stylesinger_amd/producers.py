@@ -10,6 +10,7 @@ import torch
 
 from . import lib as L
 from .audiofile import as_waveform
+from .controls import from_input
 from .resample import out_len, resample_batch
 
 
@@ -23,37 +24,7 @@ def row(x, dtype):
     return torch.as_tensor(np.asarray(x), dtype=dtype)[None]
 
 
-ALIGN_BAND_S = 2.0   # default half-width of the pitch_align band, seconds around the linear fit
-
-
-def align_inputs(inp, has_contour, sr, hop):
-    """The alignment keys of `inp` (host only, no device): inp['pitch_align'] (None | "dtw") and inp['pitch_align_band_s'] (seconds >= 0; default
-    ALIGN_BAND_S; 0 = the full matrix) -> {} or {pitch_align: "dtw", pitch_align_band: round(s * sr / hop) guide frames (0 = full)}. Refused: another
-    mode, a band without pitch_align, either without a contour (`has_contour`: inp gave pitch_hz or pitch_audio).
-    inp['pitch_timing'] (None | "guide": forward(pitch_timing=), the score sung in the guide's timing) aligns too: it takes the band with or without
-    pitch_align, needs a contour like it, and adds pitch_timing = "guide" to the result."""
-    mode, band_s, timing = inp.get("pitch_align"), inp.get("pitch_align_band_s"), inp.get("pitch_timing")
-    if timing is not None and timing != "guide":
-        raise ValueError(f"preprocess_input: inp['pitch_timing'] = {timing!r}: None (the score's timing) or 'guide'")
-    if timing is not None and not has_contour:
-        raise ValueError("preprocess_input: inp['pitch_timing'] lays the score out on the frames of inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
-    if mode is None and timing is None:
-        if band_s is not None:
-            raise ValueError("preprocess_input: inp['pitch_align_band_s'] is the band of inp['pitch_align'] = 'dtw'; it needs pitch_align")
-        return {}
-    if mode is not None and mode != "dtw":
-        raise ValueError(f"preprocess_input: inp['pitch_align'] = {mode!r}: None (the linear fit) or 'dtw'")
-    if not has_contour:
-        raise ValueError("preprocess_input: inp['pitch_align'] warps inp['pitch_hz'] / inp['pitch_audio'] onto the score; it needs one of them")
-    band_s = ALIGN_BAND_S if band_s is None else float(band_s)
-    if not band_s >= 0:
-        raise ValueError(f"preprocess_input: inp['pitch_align_band_s'] = {band_s}: seconds >= 0 (0 = the full matrix)")
-    out = dict(pitch_align_band=int(round(band_s * sr / hop)))
-    if mode is not None:
-        out["pitch_align"] = mode
-    if timing is not None:
-        out["pitch_timing"] = timing
-    return out
+align_inputs = lambda inp, has_contour, sr, hop: from_input(inp, (sr, hop), has_contour)   # `controls.from_input` with the frame rate spelled out
 
 
 class ReferenceProducers:
@@ -365,14 +336,12 @@ class ReferenceProducers:
         """The pitch-control entries of `inp` as `infer_batch` takes them: inp['pitch_hz'] (a 1-D contour in Hz at the mel hop, 0 = unvoiced) or
         inp['pitch_audio'] (a WAV path or a (waveform, sample_rate) pair: a guide vocal, resampled like `ref_audio` and tracked on the device as
         `preprocess_batch` tracks the reference audio, 80-800 Hz), and inp['pitch_shift'] (semitones). inp['pitch_align'] = "dtw" (+
-        inp['pitch_align_band_s'], seconds, default ALIGN_BAND_S, 0 = full) asks for the warp of forward(pitch_align=): -> `pitch_align` and
+        inp['pitch_align_band_s'], seconds, default controls.ALIGN_BAND_S, 0 = full) asks for the warp of forward(pitch_align=): -> `pitch_align` and
         `pitch_align_band` = round(s * audio_sample_rate / hop_size) guide frames. inp['pitch_timing'] = "guide" asks for forward(pitch_timing=):
         the score sung in the guide's timing (the contour must be on the mel hop grid, as a tracked `pitch_audio` is) -> `pitch_timing` and the
         band. inp['pitch_correct' | 'vibrato_scale' | 'vibrato_add' | 'pitch_smooth_ms'] (the pitch expression controls of forward; they need no
-        contour) pass through after `pitch.resolve_pitch_edit` has checked them. -> {} when `inp` has none of them."""
-        if inp.get("pitch_hz") is not None and inp.get("pitch_audio") is not None:
-            raise ValueError("preprocess_input: give inp['pitch_hz'] or inp['pitch_audio'], not both")
-        out = {}
+        contour) pass through. The rules and the mapping are `controls.from_input`'s; the tracking and the upload are done here. -> {} when `inp` has none of them."""
+        out = from_input(inp, self.hparams, inp.get("pitch_hz") is not None or inp.get("pitch_audio") is not None)   # the rules, before any tracking
         if inp.get("pitch_hz") is not None:
             hz = torch.as_tensor(np.asarray(inp["pitch_hz"], dtype=np.float32))
             if hz.dim() != 1 or hz.numel() == 0:
@@ -387,13 +356,6 @@ class ReferenceProducers:
             n_mel = n // hop + 1
             wav16, wav16_lens = self.process_audio_wav(gv, [n_mel], [n])
             out["pitch_hz"] = (track_f0_device(wav16, wav16_lens, n_mel, sr=sr, hop_size=hop), [n_mel])
-        if inp.get("pitch_shift") is not None:
-            if "pitch_hz" not in out:
-                raise ValueError("preprocess_input: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
-            out["pitch_shift"] = float(inp["pitch_shift"])
-        out.update(align_inputs(inp, "pitch_hz" in out, int(self.hparams["audio_sample_rate"]), int(self.hparams["hop_size"])))
-        from .pitch import edit_inputs
-        out.update(edit_inputs(inp, self.hparams))   # pitch_correct / vibrato_scale / vibrato_add / pitch_smooth_ms: no contour needed, checked here
         return out
 
     @torch.no_grad()

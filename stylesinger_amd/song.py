@@ -33,10 +33,9 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .producers import align_inputs, has_features, row
+from .controls import CONTOUR_KEYS, EDIT_KEYS, PLAN, from_input
+from .producers import has_features, row
 
-PITCH_KEYS = ("pitch_hz", "pitch_audio", "pitch_shift", "pitch_align", "pitch_align_band_s", "pitch_timing")
-EDIT_KEYS = ("pitch_correct", "vibrato_scale", "vibrato_add", "pitch_smooth_ms")   # per-segment pitch edits (pitch.pitch_edit): no contour, no ph_dur
 NO_PH_DUR = ("song-level pitch control ({keys}) needs inp['ph_dur'] (seconds per phone): without it the durations are the model's own, so the "
              "segment frame counts are not known before rendering and the contour cannot be cut into per-segment slices")
 
@@ -120,7 +119,7 @@ class SongPlan:
 
 def check_pitch_keys(inp):
     """Song-level pitch keys without ph_dur are refused, with the reason (before anything is loaded or rendered)."""
-    keys = [k for k in PITCH_KEYS if inp.get(k) is not None]
+    keys = [k for k in CONTOUR_KEYS if inp.get(k) is not None]
     if keys and inp.get("ph_dur") is None:
         raise ValueError("plan_song: " + NO_PH_DUR.format(keys=", ".join(keys)))
     return keys
@@ -130,17 +129,14 @@ def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_enco
     """inp: the reference's input dict at any length - `ph` (or `ph_token`), `note`, `note_dur`, `note_type`, optionally `ph_dur`, `pitch_hz`
     (a 1-D contour in Hz over the whole song, any length), `pitch_shift`, `pitch_align` ("dtw": each segment warps its slice of the contour onto its
     own notes; the cut between segments stays linear) with `pitch_align_band_s`, `pitch_timing` ("guide": each segment is sung in the timing of
-    its slice). `pitch_correct`, `vibrato_scale`, `vibrato_add`, `pitch_smooth_ms` (EDIT_KEYS: the pitch expression controls of forward) apply per
+    its slice). `pitch_correct`, `vibrato_scale`, `vibrato_add`, `pitch_smooth_ms` (controls.EDIT_KEYS: the pitch expression controls of forward) apply per
     segment, are copied into every batch and need neither a contour nor ph_dur. -> SongPlan."""
     keys = check_pitch_keys(inp)
     if "pitch_audio" in keys:
         raise ValueError("plan_song: the planner runs on the host; track inp['pitch_audio'] first and give its contour as inp['pitch_hz'] "
                          "(StyleSingerInfer.sing_score does)")
-    if "pitch_shift" in keys and "pitch_hz" not in keys:
-        raise ValueError("plan_song: inp['pitch_shift'] transposes inp['pitch_hz'] / inp['pitch_audio']; it needs one of them")
-    align = align_inputs(inp, "pitch_hz" in keys, sr, hop)   # {} | pitch_align / pitch_timing + pitch_align_band (frames); refusals as preprocess_input
-    from .pitch import edit_inputs
-    edit = edit_inputs({k: inp.get(k) for k in EDIT_KEYS}, dict(audio_sample_rate=sr, hop_size=hop))   # {} | the edit keys, checked; every segment gets them
+    ctl = from_input(inp, (sr, hop), "pitch_hz" in keys, PLAN)   # the batch form, checked: the edit keys (every segment gets them), with a contour the rest
+    edit = {k: ctl.pop(k) for k in EDIT_KEYS if k in ctl}
     if inp.get("ph_token") is not None:
         tokens = np.asarray(inp["ph_token"], dtype=np.int64)
     elif ph_encoder is not None and inp.get("ph") is not None:
@@ -190,9 +186,7 @@ def plan_song(inp, sr=48000, hop=256, max_seconds=12.0, segment_batch=8, ph_enco
             b["mel2ph"] = torch.zeros(len(idx), T, dtype=torch.long)
             if contour is not None:
                 b["pitch_hz"] = (torch.zeros(len(idx), T, dtype=torch.float32), [segments[s]["n_frames"] for s in idx])
-                if inp.get("pitch_shift") is not None:
-                    b["pitch_shift"] = float(inp["pitch_shift"])
-                b.update(align)
+                b.update(ctl)
         for r, s in enumerate(idx):
             first, last = segments[s]["first"], segments[s]["last"]
             segments[s]["batch"], segments[s]["row"] = len(batches), r

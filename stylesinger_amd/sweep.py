@@ -15,6 +15,7 @@ keeps the per-reference cache local to one GPU:
 """
 import torch
 
+from .controls import given
 from .dist import shard_indices
 
 
@@ -94,9 +95,7 @@ def style_transfer_sweep(infer, refs, targets, rank=0, world=1, batch=32, ddim_s
                     emo_embed=torch.stack([refs[i]["emo_embed"] for i in ref_idxs]).to(dev),
                     ref_mels=None, ref_f0=None, global_steps=infer.hparams.get("diff_start", 0) + 1, infer=True,
                     note=rep(tgt["note"]), note_dur=rep(tgt["note_dur"]), note_type=rep(tgt["note_type"]),
-                    style_cache=sc, sampler=mel_sampler, **({"ddim_steps": ddim_steps} if mel_sampler == "ddim" else {"mel_steps": ddim_steps}),
-                    **({} if mel_spacing is None else {"mel_spacing": mel_spacing}), **({} if seed is None else {"seed": seed}),
-                    **({} if f0_steps is None else {"f0_steps": f0_steps}))
+                    style_cache=sc, **given(sampler=mel_sampler, mel_steps=ddim_steps, mel_spacing=mel_spacing, seed=seed, f0_steps=f0_steps))
         mel, f0, lens = out["mel_out"], out["f0_denorm"], out["lens"]
         wav = infer.vocode(mel, f0, lens) if vocode else None
         n_pairs += nb

@@ -223,8 +223,8 @@ def test_align_inputs_and_pitch_inputs():
 
 
 def test_plan_song_copies_the_alignment_keys_into_every_segment_batch():
-    from stylesinger_amd import song
-    assert "pitch_align" in song.PITCH_KEYS and "pitch_align_band_s" in song.PITCH_KEYS
+    from stylesinger_amd import controls, song
+    assert "pitch_align" in controls.CONTOUR_KEYS and "pitch_align_band_s" in controls.CONTOUR_KEYS
     P_ = 8
     inp = dict(ph_token=list(range(1, P_ + 1)), note=[60, 62, 0, 64, 65, 0, 67, 69], note_dur=[0.3] * P_, note_type=[2, 2, 1, 2, 2, 1, 2, 2],
                ph_dur=[0.3] * P_, pitch_hz=np.full(100, 220.0), pitch_shift=1.0, pitch_align="dtw", pitch_align_band_s=0.5)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import pitch_edit_cases as C
-from stylesinger_amd import abi, config
+from stylesinger_amd import abi, config, controls
 from stylesinger_amd import lib
 from stylesinger_amd import pitch as P
 
@@ -226,7 +226,7 @@ def test_forward_refuses_bad_edits_before_any_device_work():
                      (dict(pitch_correct=0.5, pitch_smooth_ms=1e5), "cap")):
         with pytest.raises(ValueError, match=word):
             m(txt, infer=True, **kw)
-    for k in P.EDIT_KEYS:
+    for k in controls.EDIT_KEYS:
         assert k in config.DEFAULT_HPARAMS and config.DEFAULT_HPARAMS[k] is None
 
 
@@ -275,17 +275,17 @@ def test_planner_producers_and_cli_carry_the_keys_without_ph_dur(capsys, monkeyp
     import json
     import torch
     from stylesinger_amd import infer, producers, song
-    assert song.EDIT_KEYS == P.EDIT_KEYS and not set(song.EDIT_KEYS) & set(song.PITCH_KEYS)
+    assert not set(controls.EDIT_KEYS) & set(controls.CONTOUR_KEYS)
     n = 8
     inp = dict(ph_token=list(range(1, n + 1)), note=[60, 62, 0, 64, 65, 0, 67, 69], note_dur=[0.3] * n, note_type=[2, 2, 1, 2, 2, 1, 2, 2],
                pitch_correct=0.8, vibrato_scale=0.5, vibrato_add=[5.5, 30.0], pitch_smooth_ms=250)
     assert song.check_pitch_keys(inp) == []                                           # no ph_dur needed
     plan = song.plan_song(inp, sr=48000, hop=256, max_seconds=1.0, segment_batch=2)
-    plain = song.plan_song({k: v for k, v in inp.items() if k not in song.EDIT_KEYS}, sr=48000, hop=256, max_seconds=1.0, segment_batch=2)
+    plain = song.plan_song({k: v for k, v in inp.items() if k not in controls.EDIT_KEYS}, sr=48000, hop=256, max_seconds=1.0, segment_batch=2)
     assert len(plan.batches) >= 2
     for b, q in zip(plan.batches, plain.batches):
         assert b["pitch_correct"] == 0.8 and b["vibrato_scale"] == 0.5 and b["vibrato_add"] == (5.5, 30.0) and b["pitch_smooth_ms"] == 250.0
-        assert not set(song.EDIT_KEYS) & set(q) and "mel2ph" not in b
+        assert not set(controls.EDIT_KEYS) & set(q) and "mel2ph" not in b
     with_dur = song.plan_song(dict(inp, ph_dur=[0.3] * n), sr=48000, hop=256, max_seconds=1.0, segment_batch=2)
     assert all(b["pitch_correct"] == 0.8 and "mel2ph" in b for b in with_dur.batches)
     with pytest.raises(ValueError, match="pitch_correct"):

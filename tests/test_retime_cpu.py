@@ -194,8 +194,8 @@ def test_align_inputs_and_pitch_inputs_carry_pitch_timing():
 
 
 def test_plan_song_copies_pitch_timing_into_every_segment_batch_and_needs_ph_dur():
-    from stylesinger_amd import song
-    assert "pitch_timing" in song.PITCH_KEYS
+    from stylesinger_amd import controls, song
+    assert "pitch_timing" in controls.CONTOUR_KEYS
     n = 8
     inp = dict(ph_token=list(range(1, n + 1)), note=[60, 62, 0, 64, 65, 0, 67, 69], note_dur=[0.3] * n, note_type=[2, 2, 1, 2, 2, 1, 2, 2],
                ph_dur=[0.3] * n, pitch_hz=np.full(100, 220.0), pitch_timing="guide")

@@ -41,7 +41,7 @@ def main():
     passthrough = {k: torch.zeros(B, 1, device=dev) for k in ("ref_f0", "style_pre_rq", "rq_codes", "style_rq")}
 
     def stage(cache):
-        c = types.SimpleNamespace(ret={}, dev=dev, kwargs=dict(style_cache=cache), B=B, T=T, dec=dec, f32=dict(device=dev, dtype=torch.float32))
+        c = types.SimpleNamespace(ret={}, dev=dev, ctl=types.SimpleNamespace(style_cache=cache, ref_weights=None), B=B, T=T, dec=dec, f32=dict(device=dev, dtype=torch.float32))
         model._align_style(c, None, None)
         return c.style
 
